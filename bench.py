@@ -26,10 +26,6 @@ import os
 import sys
 import time
 
-# The library runs up to seven HIP streams (two batches in flight + three side streams of a POA call + the caller's); a
-# ROCm process gets four hardware queues unless this is set before the runtime initialises
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "8")
-
 import numpy as np
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
@@ -457,6 +453,37 @@ C3_REPLICAS = 20           # 100 Mbp of draft = 20 x the windows of the 5 Mbp ru
 C3_CONTIGS, C3_CONTIG_BASES, C3_K = 100, 1_000_000, 13     # -s 100m => k = 13
 
 
+DUMP_BYTES = 64 << 20      # --dump-outputs: all arrays of one run together
+
+
+def dump_outputs(out_dir, batch, scans, prefix="", budget=DUMP_BYTES):
+    """--dump-outputs: what the last timed step handed its caller, as DIR/<prefix><name>.npy in float32 / float64, every value
+    exact.  POA batch: the consensus bases of all windows back to back (ASCII codes), their lengths and statuses.  Scans (one
+    after the other): the solid-position bit words as their low and high 32-bit halves, the solid k-mer ids (below 4^k, k <= 26),
+    the rank directory and the solid counts.  An array larger than its share of `budget` is written as a sample of its elements
+    at fixed-seed positions.  Returns {name: [elements, elements written]}."""
+    bases, off, ln, st = batch.results()
+    o64 = off[:-1].astype(np.int64)
+    l64 = np.minimum(ln.astype(np.int64), np.diff(off).astype(np.int64))
+    idx = np.repeat(o64, l64) + (np.arange(int(l64.sum()), dtype=np.int64) - np.repeat(np.cumsum(l64) - l64, l64))
+    res = [s.results() for s in scans]
+    arrays = [("poa_consensus", bases[idx], np.float32, 24), ("poa_length", ln, np.float64, 4), ("poa_status", st, np.float32, 2),
+              ("scan_words", np.concatenate([r[0].view(np.uint32) for r in res]), np.float64, 8),
+              ("scan_kids", np.concatenate([r[1] for r in res]), np.float64, 16),
+              ("scan_rank", np.concatenate([r[2] for r in res]), np.float64, 4),
+              ("scan_n_solid", np.array([r[3] for r in res], dtype=np.uint64), np.float64, 1)]     # shares: 59 of 64 MB
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for i, (name, a, dtype, share_mb) in enumerate(arrays):
+        cap = (budget * share_mb // 64) // np.dtype(dtype).itemsize
+        n = a.size
+        if n > cap:
+            a = a[np.sort(np.random.default_rng(i).choice(n, cap, replace=False))]
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a.astype(dtype))
+        written[prefix + name] = [int(n), int(a.size)]
+    return written
+
+
 def timed(fn, steps, fence):
     fence()
     t0 = time.perf_counter()
@@ -490,6 +517,8 @@ def main():
     ap.add_argument("--t1-pin", type=int, default=int(os.environ.get("HYPO_BENCH_T1_PIN", "150")),
                     help="contigs of the T1 run (fixed-seed sample) that also go through the reference compiled in place and are compared record by record (0 = none)")
     ap.add_argument("--no-extras", action="store_true", help="skip value_at_0p5pct / value_at_1pct / value_dense / value_c4mix and host_api")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last of them computed to DIR/<name>.npy "
+                                                          "(float32 / float64, at most 64 MB; names and sizes in the result line's `outputs_dumped`)")
     args = ap.parse_args()
 
     import torch
@@ -571,12 +600,14 @@ def main():
         exchange = hd.ConsensusExchange(max_bytes, max_windows, dev)
 
     step_no = [0]
+    last = [db]                                           # the batch of the most recent step (--dump-outputs)
 
     def step():
         for s in scans:
             s.run()
         cur = db if (db_alt is None or step_no[0] % 2 == 0) else db_alt
         step_no[0] += 1
+        last[0] = cur
         cur.run()
         if world > 1:
             exchange.gather(db.bases, db.len[:n_w])
@@ -601,6 +632,9 @@ def main():
         t = torch.tensor([dt], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, last[0], scans, "" if world == 1 else f"rank{rank}_", DUMP_BYTES // world)
 
     prof = gpu.profile_read()
     windows_timed = n_w * args.steps if db_alt is None else n_w * ((args.steps + 1) // 2) + db_alt.host.n_windows * (args.steps // 2)
@@ -988,6 +1022,8 @@ def main():
             out["imbalance"] = imbalance
         if parity_gathered:
             out["parity_gathered"] = parity_gathered
+        if dumped:
+            out["outputs_dumped"] = {"dir": args.dump_outputs, "arrays": dumped}
         out.update(extra)
         print(json.dumps(out))
     if world > 1:

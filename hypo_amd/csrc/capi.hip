@@ -336,13 +336,6 @@ void warm_up(Ctx* c) {
     (void)hipGetLastError();
 }
 
-// Hardware queues.  The library runs up to seven HIP streams (the caller's, three or four side streams of a POA call, a second
-// batch in flight, copies) and a ROCm process gets four hardware queues unless GPU_MAX_HW_QUEUES says otherwise; streams that
-// share a queue serialise (two batches in flight: 4.58 instead of 4.15 ms per C2 batch).  The runtime reads the variable when it
-// initialises, i.e. at the process's first HIP call — the library asks for eight queues when it is LOADED (linked or dlopen'ed),
-// which is earlier unless the host has already used HIP by then; a value the host's environment sets is kept.
-__attribute__((constructor)) void ask_for_hardware_queues() { (void)setenv("GPU_MAX_HW_QUEUES", "8", /*overwrite=*/0); }
-
 }  // namespace
 
 extern "C" {

@@ -2,7 +2,6 @@ set -e
 D=/tmp/c3run; rm -rf $D; mkdir -p $D
 tests/_build/gen_e2e_fast $D 31 100 1000000 13 > /dev/null
 cd $D
-export GPU_MAX_HW_QUEUES=8
 H=$GRAFT_REPO_ROOT/hypo_amd/_build/hypo
 run() { "$@" | grep Overall | sed "s/RESOURCES (\[Hypo:Hypo\]: Overall. ): //"; }
 for t in 8 16 24 32 48; do echo -n "t=$t "; run $H -d draft.fa -r reads.fa -s 100m -c 30 -b sr.sam -t $t -i -p 10; done

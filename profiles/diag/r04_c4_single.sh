@@ -9,7 +9,6 @@ S=$(date +%s.%N)
 tests/_build/gen_e2e_fast $D 77 $N 1000000 $K 30 150 2000 --bam --fast-hash --join --long 40 8000 --gaps 100000 1500
 echo "generated in $(awk -v a=$S -v b=$(date +%s.%N) "BEGIN{print b-a}") s"; ls -la $D
 cd $D
-export GPU_MAX_HW_QUEUES=8
 S=$(date +%s.%N)
 HYPO_HOST_TIMING=1 HYPO_DUMP_LONG=${DUMP_LONG:-} $GRAFT_REPO_ROOT/hypo_amd/_build/hypo -d draft.fa -r reads.fa -s $SZ -c 30 -b sr.bam -B lr.bam -t 64 -i -o out.fa > run.log 2> run.err || { tail -20 run.log run.err; exit 1; }
 echo "process wall $(awk -v a=$S -v b=$(date +%s.%N) "BEGIN{print b-a}") s"

@@ -6,7 +6,6 @@ N=${1:-1000}; K=${K:-15}; SZ=${SZ:-1g}; P=${P:-10}; THREADS=${THREADS:-"64 128"}
 D=/dev/shm/t1ing_$$; rm -rf $D; mkdir -p $D
 tests/_build/gen_e2e_fast $D 91 $N 1000000 $K 30 150 2000 --bam --fast-hash > /dev/null
 cd $D
-export GPU_MAX_HW_QUEUES=8
 IFS="|" read -ra VARR <<< "${VARIANTS:-A=1}"
 for V in "${VARR[@]}"; do
 for T in $THREADS; do
