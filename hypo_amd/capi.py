@@ -27,6 +27,8 @@ EXPORTS = [
     "hypo_gpu_arms_build_long", "hypo_gpu_arms_download_long", "hypo_gpu_arms_poa_long",
     "hypo_gpu_reads_upload", "hypo_gpu_support_kmers", "hypo_gpu_support_minimizers",
     "hypo_gpu_solid_scan_keep", "hypo_gpu_solid_release", "hypo_gpu_support_kmers_kept", "hypo_gpu_host_alloc", "hypo_gpu_host_free", "hypo_gpu_host_register", "hypo_gpu_host_unregister",
+    "hypo_gpu_kmer_count_begin", "hypo_gpu_kmer_count_add", "hypo_gpu_kmer_histogram", "hypo_gpu_solid_set_build",
+    "hypo_gpu_kmer_count_end",
 ]
 
 
@@ -147,6 +149,87 @@ class HypoGpu:
         s = abi.PoaStats()
         self._check(self.lib.hypo_gpu_poa_last_stats(C.byref(s)))
         return _stats_dict(s)
+
+    # ---- the solid k-mer set from the short reads (ABI 9) ---------------------------------------------------------------
+    def kmer_count_begin(self, k: int, coverage: int):
+        self._check(self.lib.hypo_gpu_kmer_count_begin(C.c_uint32(k), C.c_uint32(coverage)))
+        self._kmer_k = k
+
+    def kmer_count_add(self, data):
+        """data: bytes / bytearray / uint8 array of sequence bytes; any byte other than ACGTacgt ends a run of bases"""
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        self._check(self.lib.hypo_gpu_kmer_count_add(_p(a), C.c_uint64(a.size)))
+
+    def kmer_histogram(self, coverage: int) -> np.ndarray:
+        hist = np.zeros(4 * coverage + 1, dtype=np.uint64)
+        self._check(self.lib.hypo_gpu_kmer_histogram(_p(hist), C.c_uint32(hist.size)))
+        return hist
+
+    def solid_set_build(self, lower: int, upper: int, exclude_hp=True):
+        """(bits u64[4^k / 64], set bits, canonical solid k-mers) of the table of the last kmer_count_begin"""
+        bits = np.zeros((1 << (2 * self._kmer_k)) // 64, dtype=np.uint64)
+        nb, nc = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.hypo_gpu_solid_set_build(C.c_uint32(lower), C.c_uint32(upper), C.c_int(1 if exclude_hp else 0),
+                                                      _p(bits), C.byref(nb), C.byref(nc)))
+        return bits, int(nb.value), int(nc.value)
+
+    def kmer_count_end(self):
+        self._check(self.lib.hypo_gpu_kmer_count_end())
+
+    def solid_kmers_build(self, paths_or_bytes, k: int, coverage: int, chunk=None):
+        """The solid k-mer set of a run without -i.  paths_or_bytes: a list of read files (FASTA / FASTQ, plain or gzip; parsed by
+        the host library's streaming parser, SolidBuild.cpp) or sequence bytes (bytes, or a list of byte strings counted one
+        hypo_gpu_kmer_count_add call each; `chunk` cuts one byte string into calls of that many bytes, k - 1 bytes overlapping).
+        Returns a dict: hist, cut = (err, mean, lower, upper) or None when the reference's result is undefined, bits, n_bits,
+        n_canonical (and for files: seq_bytes, file_bytes, times = (parse, count, histogram, set, total) in seconds)."""
+        if isinstance(paths_or_bytes, (str, os.PathLike)) or (isinstance(paths_or_bytes, (list, tuple)) and paths_or_bytes
+                                                             and isinstance(paths_or_bytes[0], (str, os.PathLike))):
+            paths = [paths_or_bytes] if isinstance(paths_or_bytes, (str, os.PathLike)) else list(paths_or_bytes)
+            return self._solid_build_files([os.fspath(p) for p in paths], k, coverage)
+        from .host import LIB_PATH as HOST_LIB
+        host = C.CDLL(HOST_LIB)
+        pieces = [paths_or_bytes] if isinstance(paths_or_bytes, (bytes, bytearray)) else list(paths_or_bytes)
+        self.kmer_count_begin(k, coverage)
+        try:
+            for piece in pieces:
+                if chunk:
+                    at = 0
+                    while True:
+                        self.kmer_count_add(piece[at:at + chunk])
+                        if at + chunk >= len(piece):
+                            break
+                        at += chunk - (k - 1)
+                else:
+                    self.kmer_count_add(piece)
+            hist = self.kmer_histogram(coverage)
+            cut = (C.c_uint32 * 4)()
+            if host.hypo_host_solid_cutoffs(_p(hist), C.c_uint32(hist.size), cut) != 0:
+                return {"hist": hist, "cut": None}
+            cut = tuple(int(x) for x in cut)
+            bits, nb, nc = self.solid_set_build(cut[2], cut[3])
+            return {"hist": hist, "cut": cut, "bits": bits, "n_bits": nb, "n_canonical": nc}
+        finally:
+            self.kmer_count_end()
+
+    def _solid_build_files(self, paths, k, coverage):
+        from .host import LIB_PATH as HOST_LIB
+        host = C.CDLL(HOST_LIB)
+        arr = (C.c_char_p * len(paths))(*[p.encode() for p in paths])
+        words = np.zeros((1 << (2 * k)) // 64, dtype=np.uint64)
+        hist = np.zeros(4 * coverage + 1, dtype=np.uint64)
+        cut = (C.c_uint32 * 4)()
+        counts = (C.c_uint64 * 4)()
+        times = (C.c_double * 5)()
+        err = C.create_string_buffer(512)
+        rc = host.hypo_host_solid_build(arr, C.c_int(len(paths)), C.c_uint32(k), C.c_uint32(coverage), _p(words), _p(hist),
+                                        cut, counts, times, err, C.c_int(512))
+        if rc == 2:
+            return {"hist": hist, "cut": None}
+        if rc != 0:
+            raise HypoGpuError(f"solid k-mer construction failed (rc={rc}): {err.value.decode()}")
+        return {"hist": hist, "cut": tuple(int(x) for x in cut), "bits": words, "n_bits": int(counts[0]),
+                "n_canonical": int(counts[1]), "seq_bytes": int(counts[2]), "file_bytes": int(counts[3]),
+                "times": tuple(float(x) for x in times)}
 
     def solid_scan(self, packed4: np.ndarray, n_bases: int, k: int, bits: np.ndarray, kids_cap=None):
         nw = (n_bases + 63) // 64

@@ -16,6 +16,7 @@
 #include "arms_kernel.hpp"
 #include "support_kernel.hpp"
 #include "scan_kernel.hpp"
+#include "kmer_kernel.hpp"
 
 namespace {
 
@@ -137,6 +138,10 @@ struct Ctx {
         const uint64_t* seq_off = nullptr; const uint8_t* reads2 = nullptr;
     } rr;
     DevBuf solid_set; uint32_t solid_k = 0;            // hypo_gpu_solid_set_upload
+    // hypo_gpu_kmer_count_begin .. _end: the count table (4^k counters of 1 or 2 bytes, exact size), the bytes of the call in hand,
+    // and the histogram / popcount results
+    struct KmerCount { void* table = nullptr; size_t table_bytes = 0; DevBuf in, misc; uint32_t k = 0, cov = 0, sat = 0; int wide = 0; };
+    KmerCount kc;
     // hypo_gpu_solid_scan_keep: the marked positions (contig-local) and their k-mers stay on the device, one pair of exact-size
     // buffers per handle (the caller's contig number); hypo_gpu_support_kmers_kept votes against them
     struct KeptScan { void* kids = nullptr; uint32_t* spos = nullptr; uint64_t n = 0, n_bases = 0; uint32_t k = 0; bool used = false; };
@@ -362,6 +367,8 @@ static void release_ctx(Ctx& c) {
         for (auto& as : c.arms) { for (auto& a : as.arena) a.release(); as.ready = false; }
         c.rr.data.release(); c.rr.work.release(); c.rr.ready = false;
         c.solid_set.release(); c.solid_k = 0;
+        if (c.kc.table) (void)hipFree(c.kc.table);
+        c.kc.in.release(); c.kc.misc.release(); c.kc = Ctx::KmerCount();
         c.bounce.release();
         for (auto& ks : c.kept) { if (ks.kids) (void)hipFree(ks.kids); if (ks.spos) (void)hipFree(ks.spos); }
         c.kept.clear();
@@ -958,6 +965,102 @@ int hypo_gpu_solid_release(uint32_t handle) {
         for (void* p : cx.kept_parked) (void)hipFree(p);
         cx.kept_parked.clear(); cx.kept_parked_bytes = 0;
     }
+    return HYPO_OK;
+}
+
+// ---- the solid k-mer set from the short reads (kmer_kernel.hip; replaces KMC + suk::SolidKmers::initialise) --------------------
+static constexpr uint64_t kKmerPiece = (uint64_t)256 << 20;     // bytes per kernel launch of hypo_gpu_kmer_count_add
+
+int hypo_gpu_kmer_count_begin(uint32_t k, uint32_t coverage) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    if (k < 5 || k > 17) return fail(HYPO_E_INVALID, "k=%u out of range 5..17 (the count table holds 4^k counters: %.1f GiB at k = %u)",
+                                     k, k <= 31 ? (double)(1ull << (2 * k)) / (1 << 30) : 0.0, k);
+    if (coverage < 1 || coverage > HYPO_KMER_MAX_COVERAGE) return fail(HYPO_E_INVALID, "coverage %u out of range 1..%u", coverage, HYPO_KMER_MAX_COVERAGE);
+    Ctx::KmerCount& kc = g_ctx.kc;
+    if (kc.table) { (void)hipFree(kc.table); kc.table = nullptr; }
+    kc.k = 0;
+    kc.sat = 4 * coverage + 1;
+    kc.wide = kc.sat > 255;
+    kc.table_bytes = (size_t)(1ull << (2 * k)) * (kc.wide ? 2 : 1);
+    hipError_t e = hipMalloc(&kc.table, kc.table_bytes);
+    if (e != hipSuccess) { kc.table = nullptr; return fail(HYPO_E_HIP, "hipMalloc of the %.2f GiB count table (k = %u, %d-byte counters): %s",
+                                                           (double)kc.table_bytes / (1 << 30), k, kc.wide ? 2 : 1, hipGetErrorString(e)); }
+    HIP_TRY(kc.misc.alloc((size_t)(kc.sat + 2) * 8));
+    HIP_TRY(hipMemsetAsync(kc.table, 0, kc.table_bytes, g_ctx.stream));
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    kc.k = k; kc.cov = coverage;
+    return HYPO_OK;
+}
+
+int hypo_gpu_kmer_count_add(const char* bytes, uint64_t n) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    Ctx::KmerCount& kc = g_ctx.kc;
+    if (!kc.k) return fail(HYPO_E_INVALID, "no count table (hypo_gpu_kmer_count_begin)");
+    if (!n) return HYPO_OK;
+    if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
+    hipStream_t st = g_ctx.stream;
+    HIP_TRY(kc.in.alloc(n < kKmerPiece ? n : kKmerPiece));
+    // pieces of at most kKmerPiece bytes; each starts k - 1 bytes before the end of the one before, so that the k-mers that did
+    // not end inside a piece are counted (once) by the next
+    for (uint64_t at = 0;;) {
+        const uint64_t m = n - at < kKmerPiece ? n - at : kKmerPiece;
+        HIP_TRY(h2d(kc.in.p, bytes + at, m, st));
+        HIP_TRY(hypo::kmer_count_run((const uint8_t*)kc.in.p, m, kc.k, kc.table, kc.wide, kc.sat, st));
+        HIP_TRY(hipStreamSynchronize(st));                   // (the caller may refill `bytes` when this returns)
+        if (at + m >= n) break;
+        at += m - (kc.k - 1);
+    }
+    return HYPO_OK;
+}
+
+int hypo_gpu_kmer_histogram(uint64_t* hist, uint32_t n_bins) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    Ctx::KmerCount& kc = g_ctx.kc;
+    if (!kc.k) return fail(HYPO_E_INVALID, "no count table (hypo_gpu_kmer_count_begin)");
+    if (!hist || n_bins != 4 * kc.cov + 1) return fail(HYPO_E_INVALID, "hist needs 4c + 1 = %u bins (got %u)", 4 * kc.cov + 1, n_bins);
+    hipStream_t st = g_ctx.stream;
+    HIP_TRY(hypo::kmer_histogram_run(kc.table, kc.k, kc.wide, n_bins, (unsigned long long*)kc.misc.p, st));
+    HIP_TRY(hipMemcpyAsync(hist, kc.misc.p, (size_t)n_bins * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HYPO_OK;
+}
+
+int hypo_gpu_solid_set_build(uint32_t lower, uint32_t upper, int exclude_hp, uint64_t* bits, uint64_t* n_bits, uint64_t* n_canonical) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    Ctx::KmerCount& kc = g_ctx.kc;
+    if (!kc.k) return fail(HYPO_E_INVALID, "no count table (hypo_gpu_kmer_count_begin)");
+    if (!bits) return fail(HYPO_E_INVALID, "NULL buffer");
+    hipStream_t st = g_ctx.stream;
+    const uint64_t n_words = (1ull << (2 * kc.k)) / 64;
+    // the set is written into the context's solid-set buffer: a later hypo_gpu_solid_set_upload of the same words re-fills it
+    g_ctx.solid_k = 0;
+    HIP_TRY(g_ctx.solid_set.alloc(n_words * 8));
+    HIP_TRY(hypo::solid_fill_run(kc.table, kc.k, kc.wide, lower, upper, kc.sat, exclude_hp, (uint64_t*)g_ctx.solid_set.p,
+                                 (unsigned long long*)kc.misc.p, st));
+    uint64_t cnt[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(cnt, kc.misc.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(d2h(bits, g_ctx.solid_set.p, n_words * 8, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n_bits) *n_bits = cnt[0];
+    if (n_canonical) *n_canonical = cnt[1];
+    return HYPO_OK;
+}
+
+int hypo_gpu_kmer_count_end(void) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    Ctx::KmerCount& kc = g_ctx.kc;
+    if (kc.table) HIP_TRY(hipFree(kc.table));
+    kc.in.release(); kc.misc.release();
+    kc = Ctx::KmerCount();
     return HYPO_OK;
 }
 

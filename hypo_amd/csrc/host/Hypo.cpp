@@ -1,6 +1,8 @@
 // Hypo.cpp — orchestration of one polishing run (reference: src/Hypo.cpp).
 #include "Hypo.hpp"
 #include "DeviceArms.hpp"
+#include "SolidBuild.hpp"
+#include <ctime>
 #include <omp.h>
 #include <sys/resource.h>
 #include <thread>
@@ -37,19 +39,44 @@ void Hypo::polish() {
         std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: Stage File (%s) exists but could not be opened!\n", HYPO_STAGEFILE);
         std::exit(1);
     }
-    // ---- solid k-mers: loaded from aux/solid_kmers.bvsd (the KMC-based construction is outside the hot path) ------
+    // ---- solid k-mers: built from the short reads on the device (stage 0), or loaded from aux/solid_kmers.bvsd ------------------
     start();
     SolidKmers sk; sk.k = _cFlags.k;
     if (_cFlags.done_stage < 1) {
-        std::fprintf(stderr, "[Hypo::SolidKmers] Error: this build does not run KMC/suk; provide %s and run with -i "
-                             "(stage file %s with stage 1), as written by the reference or by tests/golden/gen_e2e.py\n", HYPO_SKFILE, HYPO_STAGEFILE);
-        std::exit(1);
+        SolidBuildStats st;
+        std::string err;
+        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err);
+        if (rc == SOLID_E_UNDEFINED) {                   // the reference's own line for a failed initialise (src/Hypo.cpp:53)
+            std::fprintf(stderr, "[Hypo::SolidKmers] Error: %s\n", err.c_str());
+            std::fprintf(stderr, "[Hypo::SolidKmers] Error: KMC Output: Could not have successful run of SUK for computing Solid kmers!\n");
+            std::exit(1);
+        }
+        if (rc != SOLID_OK) {
+            std::fprintf(stderr, "[Hypo::SolidKmers] Error: %s%s\n", rc == SOLID_E_DEVICE ? "device k-mer counting failed: " : "", err.c_str());
+            std::exit(1);
+        }
+        std::fprintf(stderr, "[Hypo::SolidKmers] Info: device construction: %.3f s (parse %.3f s of %.3f GB, count %.3f s of %.3f GB sent, "
+                             "histogram %.3f s, set %.3f s)\n", st.total_s, st.parse_s, st.file_bytes / 1e9, st.count_s, st.seq_bytes / 1e9, st.hist_s, st.fill_s);
+        if (_cFlags.intermed) {
+            if (!sk.store(HYPO_SKFILE)) {
+                std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Saving: Could not store the DS for Solid kmers!\n");
+                std::exit(1);
+            }
+            stop("[Hypo:Hypo]: Computed Solid kmers. ");
+            const std::time_t now = std::time(nullptr);
+            char tm[32];
+            std::strftime(tm, sizeof tm, "%Y-%m-%d %H:%M:%S", std::localtime(&now));
+            stagefile << "Stage:SolidKmers [" << tm << "]\t1" << std::endl;
+        } else {
+            stop("[Hypo:Hypo]: Computed Solid kmers. ");
+        }
+    } else {
+        if (!sk.load(HYPO_SKFILE)) {
+            std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Loading: Could not load the DS for Solid kmers (%s)!\n", HYPO_SKFILE);
+            std::exit(1);
+        }
+        stop("[Hypo:Hypo]: Loaded Solid kmers. ");
     }
-    if (!sk.load(HYPO_SKFILE)) {
-        std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Loading: Could not load the DS for Solid kmers (%s)!\n", HYPO_SKFILE);
-        std::exit(1);
-    }
-    stop("[Hypo:Hypo]: Loaded Solid kmers. ");
     std::fprintf(stdout, "[Hypo::Hypo] Info: Number of (canonical) solid kmers (nonhp) : %lu\n", (unsigned long)sk.num_solid);
 
     // ---- contigs ------------------------------------------------------------------------------------------------------

@@ -7,6 +7,7 @@
 #include "SeqIO.hpp"
 #include "Contig.hpp"
 #include "Window.hpp"
+#include "SolidBuild.hpp"
 
 using namespace hypo;
 
@@ -99,6 +100,37 @@ int hypo_host_read_fastx(const char* path, int line_by_line, char* out, int cap)
         std::memcpy(out + at, r.seq.data(), r.seq.size()); at += r.seq.size(); out[at++] = '\n';
     }
     return (int)at;
+}
+
+// find_cutoffs (SolidBuild.cpp) on hist[0 .. n_bins): out = {err, mean, lower, upper}; 0, or -1 when the reference's result is undefined
+// (no maximum after the error threshold)
+int hypo_host_solid_cutoffs(const uint64_t* hist, uint32_t n_bins, uint32_t* out) {
+    std::vector<uint64_t> h(hist, hist + n_bins);
+    hypo::CutOffs c;
+    if (!hypo::find_cutoffs(h, c)) return -1;
+    out[0] = c.err; out[1] = c.mean; out[2] = c.lower; out[3] = c.upper;
+    return 0;
+}
+
+// the whole construction of a run without -i (build_solid_kmers: parser, device counting, cut-offs, set) over n read files on the
+// calling thread's device context.  words: 4^k / 64 words; hist: 4c + 1 bins; cut: {err, mean, lower, upper}; counts: {set bits,
+// canonical solid k-mers, sequence bytes sent to the device, bytes of the read files}; times: {parse, count, histogram, set, total}
+// in seconds.  Returns SOLID_* (0 = ok, 2 = the cut-offs are undefined); the reason of a failure goes to err (err_cap bytes).
+int hypo_host_solid_build(const char* const* paths, int n, uint32_t k, uint32_t coverage, uint64_t* words, uint64_t* hist,
+                          uint32_t* cut, uint64_t* counts, double* times, char* err, int err_cap) {
+    std::vector<std::string> files(paths, paths + n);
+    hypo::SolidKmers sk;
+    hypo::SolidBuildStats st;
+    std::string e;
+    const int rc = hypo::build_solid_kmers(files, k, coverage, 1, sk, st, e);
+    if (err && err_cap > 0) { std::strncpy(err, e.c_str(), (size_t)err_cap - 1); err[err_cap - 1] = 0; }
+    if (hist) for (size_t i = 0; i < st.hist.size(); ++i) hist[i] = st.hist[i];
+    if (rc != hypo::SOLID_OK) return rc;
+    if (words) std::memcpy(words, sk.words.data(), sk.words.size() * 8);
+    cut[0] = st.cut.err; cut[1] = st.cut.mean; cut[2] = st.cut.lower; cut[3] = st.cut.upper;
+    counts[0] = st.n_bits; counts[1] = st.n_canonical; counts[2] = st.seq_bytes; counts[3] = st.file_bytes;
+    times[0] = st.parse_s; times[1] = st.count_s; times[2] = st.hist_s; times[3] = st.fill_s; times[4] = st.total_s;
+    return rc;
 }
 
 }  // extern "C"

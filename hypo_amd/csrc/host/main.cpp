@@ -35,7 +35,7 @@ const struct option long_options[] = {
 struct HelpEntry { const char* flag; const char* what; const char* dflt; };
 void usage() {
     static const HelpEntry mandatory[] = {
-        {"-r, --reads-short <str>", "Short reads (fasta/fastq, plain or compressed), or @file holding one file name per line. Only its existence is checked: solid k-mers come from aux/solid_kmers.bvsd (see -i).", nullptr},
+        {"-r, --reads-short <str>", "Short reads (fasta/fastq, plain or compressed), or @file holding one file name per line. The solid k-mers are counted from them on the device (k = 5..17); with -i a stored aux/solid_kmers.bvsd is used instead.", nullptr},
         {"-d, --draft <str>", "Draft contigs to polish (fasta/fastq, plain or compressed).", nullptr},
         {"-b, --bam-sr <str>", "Short reads aligned to the draft (bam, or sam plain/gzip; CIGAR required), sorted by coordinate.", nullptr},
         {"-c, --coverage-short <int>", "Approximate mean coverage of the short reads.", nullptr},
@@ -54,7 +54,7 @@ void usage() {
         {"-G, --gap-lr <int>", "Gap penalty, long reads (negative).", "-4"},
         {"-n, --ned-th <int>", "Largest normalised edit distance (in %) of a long arm that may enter a window.", "20"},
         {"-q, --qual-map-th <int>", "Reads mapped with a quality below this are ignored.", "2"},
-        {"-i, --intermed", "Keep and reuse intermediate files (aux/solid_kmers.bvsd). Needed here: k-mer counting (KMC) is not part of this build.", nullptr},
+        {"-i, --intermed", "Keep and reuse intermediate files: the solid k-mer set is stored in aux/solid_kmers.bvsd (and stage 1 in aux/stage.txt) and loaded by later runs.", nullptr},
         {"    --device <int>", "[MI355X build] HIP device to run on.", "0"},
         {"    --gpus <int>", "[MI355X build] Use devices 0..N-1, one context each: the contigs of a batch are dealt out to them (a contig larger than its share is cut into coordinate ranges), every context votes, cuts arms and polishes its own resident windows; windows that exist as host objects are sharded with an RCCL gather.", "1"},
         {"    --devices <list>", "[MI355X build] Comma-separated HIP device ids instead of --device / --gpus.", nullptr},

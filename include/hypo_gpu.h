@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define HYPO_GPU_ABI_VERSION 8
+#define HYPO_GPU_ABI_VERSION 9
 #define HYPO_MAX_DEVICES 16      /* contexts one process can hold (an MI355X node has 8 GPUs) */
 
 /* error codes */
@@ -366,6 +366,29 @@ int hypo_gpu_host_free(void* p);
  * must stay allocated until it is unregistered. */
 int hypo_gpu_host_register(void* p, size_t bytes);
 int hypo_gpu_host_unregister(void* p);
+
+/* ABI 9: the solid k-mer set built from the short reads (replaces KMC -k<k> -ci2 -cs<4c> -cx<4c> and
+ * suk::SolidKmers::initialise, external/suk/src/SolidKmers.cpp:68-208; DESIGN.md "Solid k-mers from the reads").
+ *  - hypo_gpu_kmer_count_begin(k, c): allocates the context's count table, 4^k counters indexed by the canonical code
+ *    min(fwd, rc) (A0 C1 G2 T3, MSB-first), 1 byte each when 4c + 1 <= 255, else 2; k in 5..17, c in 1..HYPO_KMER_MAX_COVERAGE.
+ *    A counter stops at 4c + 1, which stands for "above -cx".
+ *  - hypo_gpu_kmer_count_add(bytes, n): counts every k-mer of the bytes; any byte other than ACGTacgt ends a run of bases (put
+ *    one between two reads).  Calls add up; many small calls count what one large call counts.  Synchronous: `bytes` may be
+ *    reused on return (page-locked memory from hypo_gpu_host_alloc is copied at the link's rate).
+ *  - hypo_gpu_kmer_histogram(hist, 4c + 1): hist[v] = number of canonical k-mers counted v times, 2 <= v <= 4c (-ci2 -cx<4c>);
+ *    hist[0] = hist[1] = 0 (SolidKmers.cpp:129-150).
+ *  - hypo_gpu_solid_set_build(lower, upper, exclude_hp, bits, n_bits, n_canonical): for every canonical k-mer with
+ *    lower <= count <= upper (and 2 <= count <= 4c), and with exclude_hp no homopolymer at either end (s[0] == s[1] or
+ *    s[k-1] == s[k-2]), sets bit fwd and bit rc of the 4^k-bit set (bits: 4^k / 64 host words, all written, sdsl word layout).
+ *    n_bits = set bits (SolidKmers.cpp:204), n_canonical = solid canonical k-mers (SolidKmers::get_num_solid_kmers).
+ *    The set is left in the context's solid-set buffer as well, but is not "uploaded": call hypo_gpu_solid_set_upload as usual.
+ *  - hypo_gpu_kmer_count_end(): frees the table. */
+#define HYPO_KMER_MAX_COVERAGE 4095u
+int hypo_gpu_kmer_count_begin(uint32_t k, uint32_t coverage);
+int hypo_gpu_kmer_count_add(const char* bytes, uint64_t n);
+int hypo_gpu_kmer_histogram(uint64_t* hist, uint32_t n_bins);
+int hypo_gpu_solid_set_build(uint32_t lower, uint32_t upper, int exclude_hp, uint64_t* bits, uint64_t* n_bits, uint64_t* n_canonical);
+int hypo_gpu_kmer_count_end(void);
 
 /* Kernel timing with HIP events on the stream the kernels run on ----------------------------------
  * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each records
