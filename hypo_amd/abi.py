@@ -5,7 +5,7 @@ Reference types mirrored: ScoreParams (include/globalDefs.hpp:58-66), hypo::Wind
 """
 import ctypes as C
 
-ABI_VERSION = 9
+ABI_VERSION = 10
 
 HYPO_OK = 0
 HYPO_E_INVALID = -1
@@ -62,6 +62,11 @@ class PoaStats(C.Structure):
                 ("n_alignments", C.c_uint64), ("alg_bytes", C.c_uint64 * 8),
                 ("n_reused", C.c_uint64), ("n_threaded", C.c_uint64), ("cells_scored", C.c_uint64),
                 ("cells_threaded", C.c_uint64), ("n_carried", C.c_uint64)]
+
+
+class EditBatch(C.Structure):
+    _fields_ = [("n_pairs", C.c_uint32), ("_pad", C.c_uint32), ("a", C.c_void_p), ("a_off", C.c_void_p),
+                ("b", C.c_void_p), ("b_off", C.c_void_p)]
 
 
 # numpy dtype equivalent of HypoWindow (40 bytes, same offsets)

@@ -28,7 +28,7 @@ EXPORTS = [
     "hypo_gpu_reads_upload", "hypo_gpu_support_kmers", "hypo_gpu_support_minimizers",
     "hypo_gpu_solid_scan_keep", "hypo_gpu_solid_release", "hypo_gpu_support_kmers_kept", "hypo_gpu_host_alloc", "hypo_gpu_host_free", "hypo_gpu_host_register", "hypo_gpu_host_unregister",
     "hypo_gpu_kmer_count_begin", "hypo_gpu_kmer_count_add", "hypo_gpu_kmer_histogram", "hypo_gpu_solid_set_build",
-    "hypo_gpu_kmer_count_end",
+    "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts",
 ]
 
 
@@ -210,6 +210,45 @@ class HypoGpu:
             return {"hist": hist, "cut": cut, "bits": bits, "n_bits": nb, "n_canonical": nc}
         finally:
             self.kmer_count_end()
+
+    # ---- edit scripts of replacement units (ABI 10; hypo --vcf) -------------------------------------------------------------
+    def edit_scripts_raw(self, a_list, b_list, runs_cap=None):
+        """(dist u32[n], run_off u64[n + 1], runs u32[]) of hypo_gpu_edit_scripts; runs = (len << 2) | op, op 0..3 = '=XDI'.
+        A first runs_cap that is too small is answered with HYPO_E_WORKSPACE and the call is repeated with the size it reported (the
+        library kept its results: the repeat only copies them out)."""
+        def as_bytes(x):
+            return x.encode() if isinstance(x, str) else bytes(x)
+        a_list, b_list = [as_bytes(x) for x in a_list], [as_bytes(x) for x in b_list]
+        if len(a_list) != len(b_list):
+            raise ValueError("a_list and b_list differ in length")
+        n = len(a_list)
+        a_off = np.zeros(n + 1, dtype=np.uint64)
+        b_off = np.zeros(n + 1, dtype=np.uint64)
+        a_off[1:] = np.cumsum([len(x) for x in a_list], dtype=np.uint64)
+        b_off[1:] = np.cumsum([len(x) for x in b_list], dtype=np.uint64)
+        a = np.frombuffer(b"".join(a_list) + b"\0", dtype=np.uint8)
+        b = np.frombuffer(b"".join(b_list) + b"\0", dtype=np.uint8)
+        batch = abi.EditBatch()
+        batch.n_pairs, batch.a, batch.a_off, batch.b, batch.b_off = n, _p(a), _p(a_off), _p(b), _p(b_off)
+        dist = np.zeros(max(n, 1), dtype=np.uint32)
+        run_off = np.zeros(n + 1, dtype=np.uint64)
+        cap = 4 * n + 16 if runs_cap is None else runs_cap
+        runs = np.zeros(max(cap, 1), dtype=np.uint32)
+        rc = self.lib.hypo_gpu_edit_scripts(C.byref(batch), _p(dist), _p(run_off), _p(runs), C.c_uint64(cap))
+        if rc == abi.HYPO_E_WORKSPACE:
+            cap = int(run_off[n])
+            runs = np.zeros(max(cap, 1), dtype=np.uint32)
+            rc = self.lib.hypo_gpu_edit_scripts(C.byref(batch), _p(dist), _p(run_off), _p(runs), C.c_uint64(cap))
+        self._check(rc)
+        return dist[:n], run_off, runs[:int(run_off[n])]
+
+    def edit_scripts(self, a_list, b_list):
+        """a_list, b_list: bytes (or str).  (dist: u32 array, cigars: list of str) — the canonical unit-cost alignment of every a (draft span) against its b, as
+        extended CIGARs in draft order ('=' match, 'X' substitution, 'D' draft base removed, 'I' base inserted)."""
+        dist, run_off, runs = self.edit_scripts_raw(a_list, b_list)
+        ops = "=XDI"
+        cigars = ["".join(f"{int(r) >> 2}{ops[int(r) & 3]}" for r in runs[int(run_off[i]):int(run_off[i + 1])]) for i in range(len(dist))]
+        return dist, cigars
 
     def _solid_build_files(self, paths, k, coverage):
         from .host import LIB_PATH as HOST_LIB

@@ -6,6 +6,7 @@
 #include <stdio.h>
 #include <string.h>
 #include <dlfcn.h>
+#include <algorithm>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
@@ -17,6 +18,7 @@
 #include "support_kernel.hpp"
 #include "scan_kernel.hpp"
 #include "kmer_kernel.hpp"
+#include "edit_kernel.hpp"
 
 namespace {
 
@@ -142,6 +144,16 @@ struct Ctx {
     // and the histogram / popcount results
     struct KmerCount { void* table = nullptr; size_t table_bytes = 0; DevBuf in, misc; uint32_t k = 0, cov = 0, sat = 0; int wide = 0; };
     KmerCount kc;
+    // hypo_gpu_edit_scripts: the pairs' bytes and offsets, per-pair results, the run pool, the long / wide lists with their counters,
+    // and the move storage (and wide band values) of the pairs that do not fit the fast path's LDS.  Grow-only.
+    // A call that answered HYPO_E_WORKSPACE keeps its results (`kept`: the per-pair results on the host, the runs in `pool`) until
+    // the next call, which copies them out when it names the same batch.
+    struct EditKept {
+        bool valid = false; const char* a = nullptr; const char* b = nullptr; uint64_t a0 = 0, b0 = 0, n_runs = 0;
+        std::vector<uint64_t> aoff, boff; std::vector<uint32_t> res;
+    };
+    struct EditBufs { DevBuf a, b, a_off, b_off, res, pool, lists, ctr, moves, moves_off, vals, vals_off; EditKept kept; };
+    EditBufs ed;
     // hypo_gpu_solid_scan_keep: the marked positions (contig-local) and their k-mers stay on the device, one pair of exact-size
     // buffers per handle (the caller's contig number); hypo_gpu_support_kmers_kept votes against them
     struct KeptScan { void* kids = nullptr; uint32_t* spos = nullptr; uint64_t n = 0, n_bases = 0; uint32_t k = 0; bool used = false; };
@@ -369,6 +381,8 @@ static void release_ctx(Ctx& c) {
         c.solid_set.release(); c.solid_k = 0;
         if (c.kc.table) (void)hipFree(c.kc.table);
         c.kc.in.release(); c.kc.misc.release(); c.kc = Ctx::KmerCount();
+        for (DevBuf* d : {&c.ed.a, &c.ed.b, &c.ed.a_off, &c.ed.b_off, &c.ed.res, &c.ed.pool, &c.ed.lists, &c.ed.ctr, &c.ed.moves, &c.ed.moves_off, &c.ed.vals, &c.ed.vals_off}) d->release();
+        c.ed.kept = Ctx::EditKept();
         c.bounce.release();
         for (auto& ks : c.kept) { if (ks.kids) (void)hipFree(ks.kids); if (ks.spos) (void)hipFree(ks.spos); }
         c.kept.clear();
@@ -1061,6 +1075,146 @@ int hypo_gpu_kmer_count_end(void) {
     if (kc.table) HIP_TRY(hipFree(kc.table));
     kc.in.release(); kc.misc.release();
     kc = Ctx::KmerCount();
+    return HYPO_OK;
+}
+
+// ---- edit scripts of the replacement units (edit_kernel.hip; hypo --vcf) ---------------------------------------------------------
+static constexpr uint64_t kEditChunkBytes = (uint64_t)256 << 20;   // move storage per launch of the long / wide paths (more when one pair needs it)
+
+// Runs the long or the wide list in chunks of at most kEditChunkBytes of move storage.  need(e) = (moves bytes, values bytes).
+}  // extern "C"
+template <class Need, class Launch>
+static int edit_run_list(const uint4* dlist, const std::vector<uint4>& list, Need need, Launch launch) {
+    Ctx::EditBufs& ed = g_ctx.ed;
+    hipStream_t st = g_ctx.stream;
+    std::vector<uint64_t> moff, voff;
+    for (size_t e0 = 0; e0 < list.size();) {
+        moff.clear(); voff.clear();
+        uint64_t mb = 0, vb = 0;
+        size_t e1 = e0;
+        for (; e1 < list.size(); ++e1) {
+            uint64_t m, v;
+            need(list[e1], m, v);
+            if (e1 > e0 && mb + m > kEditChunkBytes) break;
+            moff.push_back(mb); voff.push_back(vb);
+            mb += (m + 15) & ~15ull; vb += (v + 15) & ~15ull;
+        }
+        HIP_TRY(ed.moves.alloc(mb));
+        HIP_TRY(ed.vals.alloc(vb));
+        HIP_TRY(ed.moves_off.alloc(moff.size() * 8));
+        HIP_TRY(ed.vals_off.alloc(voff.size() * 8));
+        HIP_TRY(hipMemcpyAsync(ed.moves_off.p, moff.data(), moff.size() * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemcpyAsync(ed.vals_off.p, voff.data(), voff.size() * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(launch(dlist + e0, (uint32_t)(e1 - e0)));
+        HIP_TRY(hipStreamSynchronize(st));                    // (the offsets' host vectors are refilled for the next chunk)
+        e0 = e1;
+    }
+    return HYPO_OK;
+}
+extern "C" {
+
+int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run_off, uint32_t* runs, uint64_t runs_cap) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    if (!in || !run_off || (in->n_pairs && (!dist || !in->a_off || !in->b_off))) return fail(HYPO_E_INVALID, "NULL buffer");
+    const uint32_t np = in->n_pairs;
+    run_off[0] = 0;
+    if (!np) return HYPO_OK;
+    // offsets rebased to 0 and checked: monotone, every side below 2^30 bytes
+    std::vector<uint64_t> aoff((size_t)np + 1), boff((size_t)np + 1);
+    for (uint32_t p = 0; p <= np; ++p) {
+        aoff[p] = in->a_off[p] - in->a_off[0]; boff[p] = in->b_off[p] - in->b_off[0];
+        if (p && (in->a_off[p] < in->a_off[p - 1] || in->b_off[p] < in->b_off[p - 1] || aoff[p] - aoff[p - 1] >= (1u << 30) || boff[p] - boff[p - 1] >= (1u << 30)))
+            return fail(HYPO_E_INVALID, "pair %u: offsets not monotone or a side of 2^30 bytes or more", p - 1);
+    }
+    if ((aoff[np] && !in->a) || (boff[np] && !in->b)) return fail(HYPO_E_INVALID, "NULL bytes");
+    Ctx::EditBufs& ed = g_ctx.ed;
+    Ctx::EditKept& kept = ed.kept;
+    hipStream_t st = g_ctx.stream;
+    // the retry of a call that answered HYPO_E_WORKSPACE: the same batch (pointers and offsets) copies the kept results out
+    const bool reuse = kept.valid && kept.a == in->a && kept.b == in->b && kept.a0 == in->a_off[0] && kept.b0 == in->b_off[0] &&
+                       kept.aoff == aoff && kept.boff == boff;
+    kept.valid = false;
+    if (!reuse) {
+        HIP_TRY(ed.a.alloc(aoff[np])); HIP_TRY(ed.b.alloc(boff[np]));
+        HIP_TRY(ed.a_off.alloc(((size_t)np + 1) * 8)); HIP_TRY(ed.b_off.alloc(((size_t)np + 1) * 8));
+        HIP_TRY(ed.res.alloc((size_t)np * 12)); HIP_TRY(ed.lists.alloc((size_t)np * 48)); HIP_TRY(ed.ctr.alloc(32));
+        if (aoff[np]) HIP_TRY(h2d(ed.a.p, in->a + in->a_off[0], aoff[np], st));
+        if (boff[np]) HIP_TRY(h2d(ed.b.p, in->b + in->b_off[0], boff[np], st));
+        HIP_TRY(h2d(ed.a_off.p, aoff.data(), aoff.size() * 8, st));
+        HIP_TRY(h2d(ed.b_off.p, boff.data(), boff.size() * 8, st));
+        hypo::EditIO io{};
+        io.a = (const char*)ed.a.p; io.b = (const char*)ed.b.p; io.a_off = (const uint64_t*)ed.a_off.p; io.b_off = (const uint64_t*)ed.b_off.p;
+        io.n_pairs = np;
+        io.dist = (uint32_t*)ed.res.p; io.rstart = io.dist + np; io.rcount = io.rstart + np;
+        io.counters = (unsigned long long*)ed.ctr.p;
+        io.long_list = (uint4*)ed.lists.p; io.wide_list = io.long_list + np; io.wide_list2 = io.wide_list + np;
+        unsigned long long ctr[4] = {0, 0, 0, 0};
+        // the pool starts at 4 runs per pair (the polishing runs measured 2.2 - 2.6) or what the context has; a call that overflows it
+        // (counted, never written past) runs again with the size it reported, and the grown pool stays for the calls after it
+        HIP_TRY(ed.pool.alloc(std::max<size_t>(ed.pool.cap, ((size_t)np * 4 + 1024) * 4)));
+        for (int attempt = 0;; ++attempt) {
+            io.pool = (uint32_t*)ed.pool.p; io.pool_cap = ed.pool.cap / 4;
+            HIP_TRY(hipMemsetAsync(ed.ctr.p, 0, 32, st));
+            HIP_TRY(hypo::edit_fast_run(io, g_ctx.num_cus, st));
+            HIP_TRY(hipMemcpyAsync(ctr, ed.ctr.p, 32, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (ctr[1]) {                                        // pairs whose move codes do not fit in LDS
+                std::vector<uint4> list((size_t)ctr[1]);
+                HIP_TRY(hipMemcpyAsync(list.data(), io.long_list, list.size() * 16, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                const int rc = edit_run_list(io.long_list, list, [&](const uint4& e, uint64_t& mb, uint64_t& vb) {
+                    mb = 16 * (aoff[e.x + 1] - aoff[e.x] + boff[e.x + 1] - boff[e.x] - 2 * e.y + 2); vb = 0;
+                }, [&](const uint4* dl, uint32_t n) { return hypo::edit_long_run(io, dl, n, (uint8_t*)ed.moves.p, (const uint64_t*)ed.moves_off.p, st); });
+                if (rc != HYPO_OK) return rc;
+                HIP_TRY(hipMemcpyAsync(ctr, ed.ctr.p, 32, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+            }
+            // pairs the 128-diagonal band cannot decide (with their d_b), or cannot hold (probes); then the probes that were not exact
+            for (int w = 0; w < 2; ++w) {
+                if (w) { HIP_TRY(hipMemcpyAsync(ctr, ed.ctr.p, 32, hipMemcpyDeviceToHost, st)); HIP_TRY(hipStreamSynchronize(st)); }
+                uint4* dlist = w ? io.wide_list2 : io.wide_list;
+                if (!ctr[2 + w]) continue;
+                std::vector<uint4> list((size_t)ctr[2 + w]);
+                HIP_TRY(hipMemcpyAsync(list.data(), dlist, list.size() * 16, hipMemcpyDeviceToHost, st));
+                HIP_TRY(hipStreamSynchronize(st));
+                const int rc = edit_run_list(dlist, list, [&](const uint4& e, uint64_t& mb, uint64_t& vb) {
+                    const uint32_t n = (uint32_t)(aoff[e.x + 1] - aoff[e.x]) - e.y, m = (uint32_t)(boff[e.x + 1] - boff[e.x]) - e.y;
+                    int64_t lo, hi;
+                    hypo::edit_wide_band(n, m, e.z, lo, hi);
+                    mb = 16 * hypo::edit_wide_groups(lo, hi) * ((uint64_t)n + m + 2);
+                    vb = (uint64_t)(hi - lo + 1) > hypo::EDIT_WIDE_LDS_DIAGS ? 4 * (uint64_t)(hi - lo + 1) : 0;
+                }, [&](const uint4* dl, uint32_t n) {
+                    return hypo::edit_wide_run(io, dl, n, (uint8_t*)ed.moves.p, (const uint64_t*)ed.moves_off.p, (int32_t*)ed.vals.p, (const uint64_t*)ed.vals_off.p, st);
+                });
+                if (rc != HYPO_OK) return rc;
+            }
+            HIP_TRY(hipMemcpyAsync(ctr, ed.ctr.p, 8, hipMemcpyDeviceToHost, st));
+            HIP_TRY(hipStreamSynchronize(st));
+            if (ctr[0] >= (1ull << 32)) return fail(HYPO_E_CAPACITY, "%llu runs in one call: split the batch", ctr[0]);
+            if (ctr[0] <= io.pool_cap) break;
+            if (attempt) return fail(HYPO_E_HIP, "edit run pool overflowed twice (%llu runs, capacity %llu)", ctr[0], (unsigned long long)io.pool_cap);
+            HIP_TRY(ed.pool.alloc((size_t)ctr[0] * 4));
+        }
+        kept.res.resize((size_t)np * 3);
+        HIP_TRY(d2h(kept.res.data(), ed.res.p, kept.res.size() * 4, st));
+        HIP_TRY(hipStreamSynchronize(st));
+        kept.a = in->a; kept.b = in->b; kept.a0 = in->a_off[0]; kept.b0 = in->b_off[0]; kept.n_runs = ctr[0];
+        kept.aoff.swap(aoff); kept.boff.swap(boff);
+    }
+    const uint32_t *rstart = kept.res.data() + np, *rcount = rstart + np;
+    for (uint32_t p = 0; p < np; ++p) run_off[p + 1] = run_off[p] + rcount[p];
+    memcpy(dist, kept.res.data(), (size_t)np * 4);
+    if (runs_cap < run_off[np]) {
+        kept.valid = true;
+        return fail(HYPO_E_WORKSPACE, "runs_cap %llu < %llu runs", (unsigned long long)runs_cap, (unsigned long long)run_off[np]);
+    }
+    if (run_off[np] && !runs) return fail(HYPO_E_INVALID, "NULL runs");
+    std::vector<uint32_t> pool((size_t)kept.n_runs);
+    if (kept.n_runs) HIP_TRY(d2h(pool.data(), ed.pool.p, pool.size() * 4, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t p = 0; p < np; ++p) memcpy(runs + run_off[p], pool.data() + rstart[p], (size_t)rcount[p] * 4);
     return HYPO_OK;
 }
 

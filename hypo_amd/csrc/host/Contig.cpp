@@ -527,24 +527,55 @@ void Contig::release_after_output() {
     _pseq = PackedSeq<4>();
 }
 
+std::vector<uint64_t> Contig::region_starts() const {
+    const size_t num_reg = _reg_type.size() - 1;
+    std::vector<uint64_t> starts;
+    starts.reserve(num_reg + 2);                        // (the borders out of the words of the bit vector: a select() per region was 0.7 of the
+    for (uint64_t wi = 0; wi < _reg_pos.n_words(); ++wi) {             // 0.8 s a 250 Mbp contig with 7 M regions took to write)
+        uint64_t word = _reg_pos.data()[wi];
+        while (word) { starts.push_back(wi * 64 + (uint64_t)__builtin_ctzll(word)); word &= word - 1; }
+    }
+    if (starts.size() < num_reg + 1) { std::fprintf(stderr, "[Hypo::Contig] Error: region table of contig %s is inconsistent (%zu borders for %zu regions)\n", _name.c_str(), starts.size(), num_reg); std::exit(1); }
+    return starts;
+}
+
+void Contig::collect_units(std::vector<EditUnit>& units) const {
+    units.clear();
+    const size_t num_reg = _reg_type.size() - 1;
+    const std::vector<uint64_t> starts = region_starts();
+    bool open = false;
+    uint64_t need_end = 0;                              // the furthest draft position a window of the open unit stands for
+    auto close = [&](uint64_t end) {
+        EditUnit& u = units.back();
+        u.end = (uint32_t)end;
+        if (need_end > end) {
+            std::fprintf(stderr, "[Hypo::Contig] Error: contig %s: a window ending at %llu lies outside its replacement unit [%u, %u)\n", _name.c_str(),
+                         (unsigned long long)need_end, u.beg, u.end);
+            std::exit(1);
+        }
+        open = false;
+    };
+    for (size_t i = 0; i < num_reg; ++i) {
+        const int kd = out_kind(i);
+        if (kd == 0) { if (open) close(starts[i]); continue; }
+        if (!open) { units.emplace_back(); units.back().beg = (uint32_t)starts[i]; open = true; need_end = 0; }
+        if (kd == 1) {
+            units.back().text += _pwindows[i]->consensus_ref();
+            need_end = std::max<uint64_t>(need_end, starts[i] + _pwindows[i]->get_window_len());
+        }
+    }
+    if (open) close(starts[num_reg]);
+}
+
 // ---- operator<< (src/Contig.cpp:345-366): one-line FASTA record -------------------------------------------------------
 std::ostream& operator<<(std::ostream& os, const Contig& ctg) {
     os << ">" << ctg._name << std::endl;
     const size_t num_reg = ctg._reg_type.size() - 1;
     // the record is put together in one string: where every region's text goes is a prefix sum over the regions, the pieces are
     // copied on all threads (the reference streams them one by one; the bytes are the same)
-    std::vector<uint64_t> starts, at(num_reg + 1, 0);
-    starts.reserve(num_reg + 2);                        // (the borders out of the words of the bit vector: a select() per region was 0.7 of the
-    for (uint64_t wi = 0; wi < ctg._reg_pos.n_words(); ++wi) {         // 0.8 s a 250 Mbp contig with 7 M regions took to write)
-        uint64_t word = ctg._reg_pos.data()[wi];
-        while (word) { starts.push_back(wi * 64 + (uint64_t)__builtin_ctzll(word)); word &= word - 1; }
-    }
-    if (starts.size() < num_reg + 1) { std::fprintf(stderr, "[Hypo::Contig] Error: region table of contig %s is inconsistent (%zu borders for %zu regions)\n", ctg._name.c_str(), starts.size(), num_reg); std::exit(1); }
-    auto kind = [&](size_t i) {                        // 0: draft text, 1: consensus, 2: nothing
-        if (ctg._reg_type[i] == RegionType::SR || ctg._reg_type[i] == RegionType::MSR) return 0;
-        if (ctg._pwindows[i]) return 1;
-        return Contig::_no_long_reads ? 0 : 2;
-    };
+    const std::vector<uint64_t> starts = ctg.region_starts();
+    std::vector<uint64_t> at(num_reg + 1, 0);
+    auto kind = [&](size_t i) { return ctg.out_kind(i); };       // 0: draft text, 1: consensus, 2: nothing
     for (size_t i = 0; i < num_reg; ++i) {
         const int kd = kind(i);
         at[i + 1] = at[i] + (kd == 0 ? starts[i + 1] - starts[i] : kd == 1 ? ctg._pwindows[i]->consensus_ref().size() : 0);

@@ -37,6 +37,10 @@ struct MWMinimiserInfo {                       // include/Contig.hpp:46-52
     std::vector<uint32_t> support, coverage;   // 16-bit counters in the reference: read through & 0xffff
 };
 
+// A replacement unit (hypo --vcf): a maximal run of regions that operator<< does not write as draft text (valid windows, and
+// regions written as nothing); the draft span [beg, end) it covers and the text written in its place.
+struct EditUnit { uint32_t beg = 0, end = 0; std::string text; };
+
 class Contig {
 public:
     Contig(uint32_t id, const std::string& name, const std::string& seq);
@@ -82,6 +86,9 @@ public:
     uint64_t select(uint64_t i) const { return _solid_pos.select(i); }
     const std::string& get_name() const { return _name; }
     std::string draft_segment(uint32_t beg, uint32_t end) const { return _pseq.unpack(beg, end); }
+    char draft_base(uint64_t p) const { return _pseq.base_at(p); }
+    // the replacement units in draft order (exits with an error when a window's text does not lie inside its unit)
+    void collect_units(std::vector<EditUnit>& units) const;
     uint64_t get_len() const { return _len; }
     // region map for diagnostics / tests: (begin, end, type) of region i
     void region(uint32_t i, uint32_t& beg, uint32_t& end, RegionType& t) const { beg = (uint32_t)_reg_pos.select(i + 1); end = (uint32_t)_reg_pos.select(i + 2); t = _reg_type[i]; }
@@ -116,6 +123,13 @@ private:
     void initialise_minimserinfo(const std::string& draft_seq, uint32_t minfoind);
     void divide(uint32_t reg_index, uint32_t beg, uint32_t end, char pvs, char nxt);
     void force_divide(uint32_t beg, uint32_t end, char pvs, char nxt);
+    // what operator<< writes for region i — 0: its draft text, 1: the window's consensus, 2: nothing
+    int out_kind(size_t i) const {
+        if (_reg_type[i] == RegionType::SR || _reg_type[i] == RegionType::MSR) return 0;
+        if (_pwindows[i]) return 1;
+        return _no_long_reads ? 0 : 2;
+    }
+    std::vector<uint64_t> region_starts() const;
 };
 
 }  // namespace hypo

@@ -2,6 +2,7 @@
 #include "Hypo.hpp"
 #include "DeviceArms.hpp"
 #include "SolidBuild.hpp"
+#include "EditVcf.hpp"
 #include <ctime>
 #include <omp.h>
 #include <sys/resource.h>
@@ -17,7 +18,11 @@ namespace hypo {
 extern std::atomic<uint64_t> g_stage_counters[5];      // host/Contig.cpp
 namespace {
 std::string pending_tmp;                               // <output>.tmp while a run is writing it (Hypo::polish); removed by a run that fails
-void remove_pending_output() { if (!pending_tmp.empty()) std::remove(pending_tmp.c_str()); }
+std::string pending_vcf_tmp;                           // <vcf>.tmp likewise (--vcf)
+void remove_pending_output() {
+    if (!pending_tmp.empty()) std::remove(pending_tmp.c_str());
+    if (!pending_vcf_tmp.empty()) std::remove(pending_vcf_tmp.c_str());
+}
 }
 
 Hypo::Hypo(const InputFlags& flags) : _cFlags(flags) {
@@ -34,6 +39,13 @@ void Hypo::stop(const char* label) {
 }
 
 void Hypo::polish() {
+    // --vcf: the device library must provide the edit scripts (C-ABI 10); bound by name, and only here, so that libraries without
+    // the entry point still serve every run without --vcf
+    EditScriptsFn edit_fn = nullptr;
+    if (!_cFlags.vcf_filename.empty() && !(edit_fn = bind_edit_scripts())) {
+        std::fprintf(stderr, "[Hypo::Hypo] Error: --vcf needs hypo_gpu_edit_scripts (C-ABI 10), which the device library does not provide\n");
+        std::exit(1);
+    }
     std::ofstream stagefile(HYPO_STAGEFILE, std::ofstream::out | std::ofstream::app);
     if (_cFlags.intermed && !stagefile.is_open()) {
         std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: Stage File (%s) exists but could not be opened!\n", HYPO_STAGEFILE);
@@ -171,6 +183,17 @@ void Hypo::polish() {
     if (!ofile.is_open()) {
         std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: Output File (%s) could not be opened!\n", pending_tmp.c_str());
         std::exit(1);
+    }
+    std::ofstream vfile;
+    VcfStats vstats;
+    if (edit_fn) {                                         // (the VCF follows the FASTA: <vcf>.tmp until the run succeeds)
+        pending_vcf_tmp = _cFlags.vcf_filename + ".tmp";
+        vfile.open(pending_vcf_tmp);
+        if (!vfile.is_open()) {
+            std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: VCF File (%s) could not be opened!\n", pending_vcf_tmp.c_str());
+            std::exit(1);
+        }
+        vcf_header(vfile, _cFlags.draft_filename, _contigs);
     }
     std::thread writer;
     for (uint32_t batch_id = 0; batch_id < num_batches; ++batch_id) {
@@ -564,10 +587,28 @@ void Hypo::polish() {
                     else if (t != RegionType::SR && t != RegionType::MSR) dump << "\t0\t0\t0\t0\t0\t" << _contigs[i]->draft_segment(b, e);   // no arms: draft kept
                     dump << '\n';
                 }
+        // --vcf: the writer thread aligns the batch's replacement units against their drafts (one call on context 0, beside the
+        // next batch's stages on this thread) and formats each contig's records next to its FASTA record, before the contig's
+        // windows go
         if (writer.joinable()) writer.join();
-        writer = std::thread([this, &ofile, initial_cid, final_cid] {
+        writer = std::thread([this, &ofile, &vfile, &vstats, edit_fn, initial_cid, final_cid] {
             omp_set_num_threads(std::max(1, std::min((int)_cFlags.threads, 8)));
-            for (uint32_t c = initial_cid; c < final_cid; ++c) { ofile << *_contigs[c]; _contigs[c]->release_after_output(); }
+            std::unique_ptr<EditBatchResult> edits;
+            if (edit_fn) {
+                edits.reset(new EditBatchResult());
+                if (hypo_gpu_use_device(0) != HYPO_OK || edit_scripts_for(edit_fn, _contigs, initial_cid, final_cid, *edits) != HYPO_OK) {
+                    // (the main thread may be inside a device call: leave without running the static destructors under it)
+                    std::fprintf(stderr, "[Hypo::Hypo] Error: edit scripts: %s\n", hypo_gpu_last_error());
+                    std::fflush(nullptr);
+                    remove_pending_output();
+                    std::_Exit(1);
+                }
+            }
+            for (uint32_t c = initial_cid; c < final_cid; ++c) {
+                ofile << *_contigs[c];
+                if (edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, vstats);
+                _contigs[c]->release_after_output();
+            }
         });
     }
     _alignment_store.clear();
@@ -575,13 +616,28 @@ void Hypo::polish() {
 
     start();
     if (writer.joinable()) writer.join();
+    // both files are closed and checked before either takes its name; a VCF that cannot take its name takes the FASTA with it
     ofile.close();
     if (!ofile) { std::fprintf(stderr, "[Hypo::Hypo] Error: writing the output file (%s) failed!\n", pending_tmp.c_str()); std::exit(1); }
+    if (edit_fn) {
+        vfile.close();
+        if (!vfile) { std::fprintf(stderr, "[Hypo::Hypo] Error: writing the VCF file (%s) failed!\n", pending_vcf_tmp.c_str()); std::exit(1); }
+    }
     if (std::rename(pending_tmp.c_str(), _cFlags.output_filename.c_str()) != 0) {
         std::fprintf(stderr, "[Hypo::Hypo] Error: could not move %s to %s!\n", pending_tmp.c_str(), _cFlags.output_filename.c_str());
         std::exit(1);
     }
     pending_tmp.clear();
+    if (edit_fn) {
+        if (std::rename(pending_vcf_tmp.c_str(), _cFlags.vcf_filename.c_str()) != 0) {
+            std::fprintf(stderr, "[Hypo::Hypo] Error: could not move %s to %s!\n", pending_vcf_tmp.c_str(), _cFlags.vcf_filename.c_str());
+            std::remove(_cFlags.output_filename.c_str());
+            std::exit(1);
+        }
+        pending_vcf_tmp.clear();
+        std::fprintf(stdout, "[Hypo::Hypo] Info: VCF %s: %llu records, %llu substituted, %llu inserted, %llu deleted bases\n", _cFlags.vcf_filename.c_str(),
+                     (unsigned long long)vstats.records, (unsigned long long)vstats.sub, (unsigned long long)vstats.ins, (unsigned long long)vstats.del);
+    }
     stop("[Hypo:Hypo]: Writing results. ");
     _times.overall = std::chrono::duration<double>(std::chrono::steady_clock::now() - _tstart).count();
     std::fprintf(stdout, "RESOURCES ([Hypo:Hypo]: Overall. ): TIME= %g sec.\n", _times.overall);

@@ -24,6 +24,7 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     bool require_device = false;           // new, opt-in: --require-device (a stage the device should run must not quietly fall back to the host loops: error instead)
     bool host_arms = false;                // new, opt-in: --host-arms (cut the short reads into arms on the host, not on the device)
     bool ccs_windows = false;              // new, opt-in: --ccs-windows (the window sizes -k ccs was meant to select)
+    std::string vcf_filename;              // new, opt-in: --vcf <file> (every edit of the run as VCF records beside the FASTA)
 };
 
 enum class RegionType : uint8_t { SWS, SW, WS, MWM, MW, WM, SWM, MWS, OTHER, LONG, SR, MSR };   // globalDefs.hpp:95-108

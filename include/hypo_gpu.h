@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define HYPO_GPU_ABI_VERSION 9
+#define HYPO_GPU_ABI_VERSION 10
 #define HYPO_MAX_DEVICES 16      /* contexts one process can hold (an MI355X node has 8 GPUs) */
 
 /* error codes */
@@ -389,6 +389,22 @@ int hypo_gpu_kmer_count_add(const char* bytes, uint64_t n);
 int hypo_gpu_kmer_histogram(uint64_t* hist, uint32_t n_bins);
 int hypo_gpu_solid_set_build(uint32_t lower, uint32_t upper, int exclude_hp, uint64_t* bits, uint64_t* n_bits, uint64_t* n_canonical);
 int hypo_gpu_kmer_count_end(void);
+
+/* ABI 10: edit scripts of the replacement units (hypo --vcf; DESIGN.md "Edit scripts").  Pair p aligns a[a_off[p], a_off[p+1])
+ * (the draft span) against b[b_off[p], b_off[p+1]) (its polished text) with unit costs, bytes compared as bytes; the traceback
+ * from (n, m) takes the first move that holds of diagonal, up (a base of `a` deleted), left (a base inserted).
+ *  - dist[n_pairs]: the edit distances; run_off[n_pairs + 1]: where each pair's runs start in runs[] (run_off[0] = 0);
+ *    runs[] = (len << 2) | op, op 0 '=', 1 'X', 2 'D', 3 'I', in draft order; consecutive runs have different ops.
+ *  - runs_cap < run_off[n_pairs]: HYPO_E_WORKSPACE with dist and run_off filled; call again with runs of that size.  The
+ *    context keeps the results of that call: the next call on it that names the same batch (the same a, b pointers and the same
+ *    offsets; the bytes must not have changed in between) copies them out without computing again.
+ *  - every side below 2^30 bytes.  Runs on the calling thread's context; synchronous. */
+typedef struct HypoEditBatch {
+    uint32_t n_pairs, _pad;
+    const char* a; const uint64_t* a_off;
+    const char* b; const uint64_t* b_off;
+} HypoEditBatch;
+int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run_off, uint32_t* runs, uint64_t runs_cap);
 
 /* Kernel timing with HIP events on the stream the kernels run on ----------------------------------
  * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each records
