@@ -16,9 +16,13 @@ the per-window consensus lengths and bytes (what contig re-assembly needs, SURVE
 batch / max-over-ranks time; `--workload c3` runs the same job on one GPU, `--workload c2 --gpus N` the weak-scaling
 variant of round 1 (one C2 batch per rank).
 
-Prints ONE JSON line on rank 0.  `roofline` is measured live with HIP events recorded by the library on
-the stream its kernels run on; `cpu_baseline` times oracle/ (this repo's bit-exact CPU restatement of the
-reference's OpenMP/spoa path) on the same batch on this box's host cores (rank 0, N = 1 only).
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the steps, writes --dump-outputs and prints
+the headline with what the timed steps themselves yield: `roofline` is measured live with HIP events recorded by the
+library on the stream its kernels run on during those steps.  Everything that needs work of its own is behind
+`--full` (several minutes): the parity checks against oracle/ and the reference, `cpu_baseline` (oracle/, this repo's
+bit-exact CPU restatement of the reference's OpenMP/spoa path, on the same batch on the host's cores; rank 0, N = 1
+only), the other error rates, shapes and entry points, and the end-to-end legs; the --no-* / --e2e-1g / --t1-*
+options shape a --full run.
 """
 import argparse
 import json
@@ -501,6 +505,8 @@ def main():
     ap.add_argument("--workload", choices=["auto", "c2", "c3"], default="auto",
                     help="auto: C2 (BASELINE configs[1]) on one GPU, C3 strong scaling (configs[2]) on several")
     ap.add_argument("--windows", type=int, default=N_WINDOWS, help="windows per GPU of the C2 workload")
+    ap.add_argument("--full", action="store_true", help="after the headline, also run the parity checks, CPU baselines, other shapes and error rates, "
+                                                       "host-API rates and end-to-end legs (several minutes; the options below shape it)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--no-e2e", action="store_true")
@@ -638,7 +644,7 @@ def main():
 
     prof = gpu.profile_read()
     windows_timed = n_w * args.steps if db_alt is None else n_w * ((args.steps + 1) // 2) + db_alt.host.n_windows * (args.steps // 2)
-    if db_alt is not None and args.steps % 2 == 0:
+    if args.full and db_alt is not None and args.steps % 2 == 0:
         db.run()                                           # the checks below look at the FIRST batch: make it the most recent call
         torch.cuda.synchronize(dev)
     stats = db.stats()
@@ -647,7 +653,7 @@ def main():
 
     # ---- parity spot check (outside the timed region): the HIP results against the oracle -----------
     parity = None
-    if not args.no_check and rank == 0:
+    if args.full and not args.no_check and rank == 0:
         import oracle
         orc = oracle.Oracle()
         sub = sim.window_batch(4000, seed=77)
@@ -756,7 +762,7 @@ def main():
                                 "what": "POA kernels (all size classes) + solid-kmer scan(s) of one step: sum of algorithmic bytes / ms_per_step"}
 
     # ---- the same POA call on noisier reads and through the host-pointer entry point (N = 1 only, a few calls each) ----
-    if rank == 0 and world == 1 and not args.no_extras:
+    if args.full and rank == 0 and world == 1 and not args.no_extras:
         for key, sub in (("value_at_0p5pct", 0.005), ("value_at_1pct", 0.01)):
             # two batches of that error rate alternate, like the headline's
             ndbs = [gpu.device_batch(sim.window_batch(args.windows, seed=sd, read_sub=sub)) for sd in (1000, 5000)]
@@ -881,7 +887,7 @@ def main():
 
     # ---- CPU baseline: the bit-exact port of the reference's OpenMP/spoa path on this box -----------------
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         import oracle
         orc = oracle.Oracle()
         thr = orc.num_threads()
@@ -940,7 +946,7 @@ def main():
     e2e_k17 = None
     e2e_c5 = None
     e2e_real = None
-    if rank == 0 and world == 1 and not args.no_e2e and not strong:
+    if args.full and rank == 0 and world == 1 and not args.no_e2e and not strong:
         e2e = end_to_end_leg()
         if not args.no_e2e_c3:
             e2e_c3 = end_to_end_c3_leg()
@@ -966,9 +972,9 @@ def main():
                 e2e_t1["batchings_run"] = [50]
 
     # ---- N > 1: what the all-gather delivered, re-assembled in global window order, against the oracle on the WHOLE batch (opt-in:
-    # HYPO_BENCH_CHECK_GATHER=1; tests/test_gpu_distributed.py runs it with every rank on device 0) -----------------------------------
+    # --full and HYPO_BENCH_CHECK_GATHER=1; tests/test_gpu_distributed.py runs it with every rank on device 0) --------------------------
     parity_gathered = None
-    if strong and world > 1 and os.environ.get("HYPO_BENCH_CHECK_GATHER") == "1":
+    if args.full and strong and world > 1 and os.environ.get("HYPO_BENCH_CHECK_GATHER") == "1":
         gb, gl = exchange.gather(db.bases, db.len[:n_w])
         torch.cuda.synchronize(dev)
         if rank == 0:

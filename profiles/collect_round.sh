@@ -8,7 +8,7 @@ OUT=$R/gpurun_out/$TAG
 mkdir -p $OUT
 cd $R
 make -s -C hypo_amd/csrc prof >/dev/null 2>&1   # the diagnostic build must match the sources (it is not built by the default target)
-python bench.py > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full > $OUT/bench.json 2> $OUT/bench.err
 # kernel trace + counters of the bench's kernels (concurrent schedule = the product; sequential = every class alone)
 bash profiles/run_pmc.sh $TAG > /dev/null 2>&1
 python profiles/summarize_pmc.py gpurun_out/pmc_$TAG > $OUT/pmc_summary.csv

@@ -18,7 +18,7 @@ def test_bench_two_ranks_on_one_device_gathers_the_oracle_consensus():
                MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="16")
     port = 29600 + os.getpid() % 300
     p = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(port),
-                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--no-e2e", "--no-extras", "--no-cpu-baseline"],
+                        os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full", "--no-e2e", "--no-extras", "--no-cpu-baseline"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stdout[-1500:] + p.stderr[-1500:]
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]
