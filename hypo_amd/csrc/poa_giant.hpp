@@ -50,7 +50,7 @@ struct Giant {
     uint32_t* dst;
     int *e_src, *e_dst, *e_w, *e_nin, *e_nout, *e_lab_head, *e_lab_tail, *lab_seq, *lab_next;
     int* H;
-    uint32_t Ncap, Ecap, Pcap, Scap;
+    uint32_t Ncap, Ecap, Pcap, Scap, SQcap;
     uint64_t Hcap;
     uint64_t cells, aligns;
 #if defined(HYPO_PHASE_TIMERS) && !defined(HYPO_EMU)
@@ -97,7 +97,8 @@ struct Giant {
         e_lab_head = (int*)take(4ull * Ecap); e_lab_tail = (int*)take(4ull * Ecap);
         lab_seq = (int*)take(4ull * Pcap); lab_next = (int*)take(4ull * Pcap);
         seqbeg = (int*)take(4ull * nseq_max + 16);
-        sq = (uint8_t*)take((uint64_t)lmax + 64);
+        SQcap = lmax + 64;
+        sq = (uint8_t*)take((uint64_t)SQcap);
         if (off + 4096 > bytes) return false;
         H = (int*)(slice + off);
         Hcap = (bytes - off) / 4;
@@ -463,15 +464,16 @@ struct Giant {
 
     // ---- sequences --------------------------------------------------------------------------------------------------------------
     HD int draft_code(const HypoWindow& W, uint32_t i) const { const uint32_t c = (P->draft4[W.draft_off + (i >> 1)] >> (4 - 4 * (i & 1))) & 15u; return c < 4u ? (int)c : (int)C_N; }
-    // sq[] = [head marker] + the sequence + [tail marker]; which: -1 the draft, -2 the consensus of the round before (ctext2), else the arm
+    // sq[] = [head marker] + the sequence + [tail marker]; which: -1 the draft, -2 the consensus of the round before (ctext2), else the arm.
+    // Returns the staged length, or -1 (nothing written; the same on every lane) when sq[] cannot hold it: the window answers RES_OVERFLOW
     HD int stage(const HypoWindow& W, int which, bool head, bool tail, int prev_len) {
-        int len;
         const int o = head ? 1 : 0;
-        if (which == -1) { len = (int)W.draft_len; for (int i = g.lane; i < len; i += 64) sq[o + i] = (uint8_t)draft_code(W, (uint32_t)i); }
-        else if (which == -2) { len = prev_len; for (int i = g.lane; i < len; i += 64) sq[o + i] = ctext2[i]; }
+        const int len = which == -1 ? (int)W.draft_len : (which == -2 ? prev_len : (int)P->arm_len[(uint64_t)W.first_arm + (uint64_t)which]);
+        if ((uint64_t)(uint32_t)len + (uint64_t)o + (tail ? 1u : 0u) > (uint64_t)SQcap) return -1;
+        if (which == -1) { for (int i = g.lane; i < len; i += 64) sq[o + i] = (uint8_t)draft_code(W, (uint32_t)i); }
+        else if (which == -2) { for (int i = g.lane; i < len; i += 64) sq[o + i] = ctext2[i]; }
         else {
             const uint64_t a = (uint64_t)W.first_arm + (uint64_t)which;
-            len = (int)P->arm_len[a];
             const uint8_t* const src = P->arms2 + P->arm_off[a];
             for (int i = g.lane; i < len; i += 64) sq[o + i] = (uint8_t)((src[i >> 2] >> (6 - 2 * (i & 3))) & 3u);
         }
@@ -528,6 +530,14 @@ struct Giant {
             const uint64_t sum = ((uint64_t)(uint32_t)g.reduce_add((int)hi) << 24) + (uint64_t)(uint32_t)g.reduce_add((int)lo);
             total += sum; lmax = (uint32_t)lm_all > lmax ? (uint32_t)lm_all : lmax;
         }
+        if (is_long) {
+            // The second round aligns against the first round's curated consensus, not against the draft (src/Window.cpp:167-172), and nothing
+            // bounds that consensus by the draft or by an arm: it is a path of the first round's graph, so at most as long as that graph has
+            // nodes (<= total), and the second graph holds it next to the arms (<= total + total).  Tables, labels and sq[] are sized for
+            // that; the score matrix is checked per alignment (align) and sq[] per sequence (stage).
+            lmax = total > (uint64_t)LMAXG ? LMAXG : (uint32_t)total;
+            total += total;
+        }
         if (!layout(slice, slice_bytes, total, lmax, narm + 2, is_long)) return RES_OVERFLOW;
         const uint32_t ni = W.n_internal, np = W.n_prefix, ns = W.n_suffix;
         int rc;
@@ -536,17 +546,17 @@ struct Giant {
             if (g.lane == 0) g_reset(false);
             g.sync();
             bool added = false;
-            if (ni == 0) { const int L = stage(W, -1, true, true, 0); if ((rc = add(L, MODE_NW, m, n_, gp)) != RES_OK) return rc; }
+            if (ni == 0) { const int L = stage(W, -1, true, true, 0); if (L < 0) return RES_OVERFLOW; if ((rc = add(L, MODE_NW, m, n_, gp)) != RES_OK) return rc; }
             for (uint32_t i = 0; i < ni; ++i) if (P->arm_len[(uint64_t)W.first_arm + i] > 0) {
-                const int L = stage(W, (int)i, true, true, 0); added = true;
+                const int L = stage(W, (int)i, true, true, 0); if (L < 0) return RES_OVERFLOW; added = true;
                 if ((rc = add(L, MODE_NW, m, n_, gp)) != RES_OK) return rc;
             }
             for (uint32_t i = np; i-- > 0;) if (P->arm_len[(uint64_t)W.first_arm + ni + i] > 0) {      // last one first (:111)
-                const int L = stage(W, (int)(ni + i), true, false, 0); added = true;
+                const int L = stage(W, (int)(ni + i), true, false, 0); if (L < 0) return RES_OVERFLOW; added = true;
                 if ((rc = add(L, MODE_LOV, m, n_, gp)) != RES_OK) return rc;
             }
             for (uint32_t i = 0; i < ns; ++i) if (P->arm_len[(uint64_t)W.first_arm + ni + np + i] > 0) {
-                const int L = stage(W, (int)(ni + np + i), false, true, 0); added = true;
+                const int L = stage(W, (int)(ni + np + i), false, true, 0); if (L < 0) return RES_OVERFLOW; added = true;
                 if ((rc = add(L, MODE_ROV, m, n_, gp)) != RES_OK) return rc;
             }
             if (!added) { answer_draft(); return RES_OK; }
@@ -567,10 +577,10 @@ struct Giant {
             if (g.lane == 0) g_reset(true);
             g.sync();
             bool added = false;
-            if (round == 0) { const int L = stage(W, -1, false, false, 0); if ((rc = add(L, MODE_NW, m, n_, gp)) != RES_OK) return rc; }
-            else if (conslen > 0) { const int L = stage(W, -2, false, false, conslen); if ((rc = add(L, MODE_NW, m, n_, gp)) != RES_OK) return rc; }
+            if (round == 0) { const int L = stage(W, -1, false, false, 0); if (L < 0) return RES_OVERFLOW; if ((rc = add(L, MODE_NW, m, n_, gp)) != RES_OK) return rc; }
+            else if (conslen > 0) { const int L = stage(W, -2, false, false, conslen); if (L < 0) return RES_OVERFLOW; if ((rc = add(L, MODE_NW, m, n_, gp)) != RES_OK) return rc; }
             for (uint32_t a = 0; a < narm; ++a) if (P->arm_len[(uint64_t)W.first_arm + a] > 0) {
-                const int L = stage(W, (int)a, false, false, 0); added = true;
+                const int L = stage(W, (int)a, false, false, 0); if (L < 0) return RES_OVERFLOW; added = true;
                 if ((rc = add(L, MODE_NW, m, n_, gp)) != RES_OK) return rc;
             }
             if (!added) { answer_draft(); return RES_OK; }

@@ -51,6 +51,12 @@ SPACES = {            # name: (alphabet size, arms, max draft, max arm)
     "a4n3": (4, 3, 2, 2),      # (1.6 M)
     "a2n5": (2, 5, 3, 2),      # five arms (2.3 M)
 }
+# LONG windows (two rounds, every arm kNW, curate): arms of 0..La bases — the real reference cannot check these (its Window filters every
+# arm shorter than 19 bases away, include/Filter.hpp:64-102), the oracle does (tests/test_long_growth_cpu.py, tests/test_gpu_long_growth.py)
+LONG_SPACES = {
+    "l2n3": (2, 3, 4, 4),      # 30 drafts x 31^3 arm triples x 10 kind multisets = 8.9 M
+}
+LONG_SCORE_SETS = [(5, -4, -8, 3, -5, -4), (5, -4, -8, 2, -3, -2)]      # the default long-read scores (3, -5, -4) and one alternative
 SCORE_SETS = [(5, -4, -8, 3, -5, -4), (2, -1, -2, 3, -5, -4), (4, -3, -5, 3, -5, -4)]
 LETTERS = "ACGT"
 
@@ -61,15 +67,15 @@ def kind_multisets(n):
 
 
 def space_size(name):
-    s, n, ld, la = SPACES[name]
-    return sum(s ** l for l in range(1, ld + 1)) * sum(s ** l for l in range(1, la + 1)) ** n * len(kind_multisets(n))
+    s, n, ld, la = SPACES[name] if name in SPACES else LONG_SPACES[name]
+    return sum(s ** l for l in range(1, ld + 1)) * sum(s ** l for l in range(0 if name in LONG_SPACES else 1, la + 1)) ** n * len(kind_multisets(n))
 
 
 def configs(name):
     """Every (draft length, arm lengths, kinds) of a space with the number of windows it holds."""
-    s, n, ld, la = SPACES[name]
+    s, n, ld, la = SPACES[name] if name in SPACES else LONG_SPACES[name]
     for dl in range(1, ld + 1):
-        for lens in itertools.product(range(1, la + 1), repeat=n):
+        for lens in itertools.product(range(0 if name in LONG_SPACES else 1, la + 1), repeat=n):
             for kinds in kind_multisets(n):
                 yield s, dl, lens, kinds, s ** (dl + sum(lens))
 
@@ -84,9 +90,10 @@ def _digits(idx, s, count):
     return out
 
 
-def build_config(s, dl, lens, kinds, first, count):
-    """HostBatch of windows [first, first + count) of one configuration (all windows share every length: regular offsets)."""
-    idx = np.arange(first, first + count, dtype=np.int64)
+def build_config(s, dl, lens, kinds, first, count, type=abi.WIN_SHORT, step=1):
+    """HostBatch of windows [first, first + count) of one configuration (all windows share every length: regular offsets); step > 1: of
+    the `count` windows first, first + step, first + 2 * step, ... (a strided sample)."""
+    idx = first + step * np.arange(count, dtype=np.int64)
     dig = _digits(idx, s, dl + sum(lens))
     n = count
     na = len(lens)
@@ -107,7 +114,7 @@ def build_config(s, dl, lens, kinds, first, count):
         col += l
         o += ab[j]
     wd = np.zeros(n, dtype=abi.WINDOW_DTYPE)
-    wd["type"] = abi.WIN_SHORT
+    wd["type"] = type
     wd["draft_len"] = dl
     wd["draft_off"] = np.arange(n, dtype=np.uint64) * db
     wd["first_arm"] = np.arange(n, dtype=np.uint32) * na
@@ -144,18 +151,37 @@ def chunks(name, chunk, stride=1, offset=0):
     """HostBatches of about `chunk` windows covering the space (every `stride`-th block of a configuration when stride > 1)."""
     pend, have = [], 0
     blk = 0
+    wtype = abi.WIN_LONG if name in LONG_SPACES else abi.WIN_SHORT
     for s, dl, lens, kinds, size in configs(name):
         first = 0
         while first < size:
             take = min(size - first, max(chunk - have, 1))
             if stride == 1 or (blk % stride) == offset % stride:
-                pend.append(build_config(s, dl, lens, kinds, first, take))
+                pend.append(build_config(s, dl, lens, kinds, first, take, wtype))
                 have += take
             blk += 1
             first += take
             if have >= chunk:
                 yield concat(pend)
                 pend, have = [], 0
+    if pend:
+        yield concat(pend)
+
+
+def every_kth(name, k, chunk=4000):
+    """HostBatches of about `chunk` windows: every k-th window of the space in the order configs() enumerates it."""
+    wtype = abi.WIN_LONG if name in LONG_SPACES else abi.WIN_SHORT
+    pend, have, start = [], 0, 0
+    for s, dl, lens, kinds, size in configs(name):
+        first = (-start) % k
+        if first < size:
+            cnt = (size - first + k - 1) // k
+            pend.append(build_config(s, dl, lens, kinds, first, cnt, wtype, step=k))
+            have += cnt
+        start += size
+        if have >= chunk:
+            yield concat(pend)
+            pend, have = [], 0
     if pend:
         yield concat(pend)
 

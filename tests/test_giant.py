@@ -31,9 +31,11 @@ def _mutate(rng, s, err):
     return "".join(out) or "A"
 
 
-def giant_windows(rng, deep_arms=400):
+def giant_windows(rng, deep_arms=400, most_arms=False):
     """Windows beyond class 5's tables: (1) LONG, two arms carry the same 1 500-base insertion; (2) SHORT with a 1 300-base draft and
-    arms of that length; (3) SHORT with `deep_arms` short arms (the GPU test uses 20 000: more than class 5's 16 382 sequences)."""
+    arms of that length; (3) SHORT with `deep_arms` short arms (the GPU test uses 20 000: more than class 5's 16 382 sequences);
+    most_arms: and (4) LONG, the 1 500-base insertion in 7 of the 9 arms — it enters the consensus (2 000 bases from a 500-base draft),
+    and the second round aligns against that."""
     A = "ACGT"
     rnd = lambda n: "".join(A[i] for i in rng.integers(0, 4, size=n))
     t1 = rnd(500)
@@ -47,7 +49,15 @@ def giant_windows(rng, deep_arms=400):
     w2 = TextWindow(_mutate(rng, t2, 0.01), [_mutate(rng, t2, 0.01) for _ in range(5)], [t2[:700]], [t2[500:]], 0, False)
     t3 = rnd(50)
     w3 = TextWindow(_mutate(rng, t3, 0.02), [_mutate(rng, t3, 0.02) for _ in range(deep_arms)], [t3[:30], t3[:41]], [t3[20:], t3[33:]], 0, False)
-    return [w1, w2, w3]
+    if not most_arms:
+        return [w1, w2, w3]
+    t4 = rnd(500)
+    ins4 = rnd(1500)
+    arms4 = []
+    for k in range(9):
+        a = _mutate(rng, t4, 0.04)
+        arms4.append(a if k in (3, 7) else a[:250] + ins4 + a[250:])
+    return [w1, w2, w3, TextWindow(_mutate(rng, t4, 0.02), arms4, [], [], 0, True)]
 
 
 def test_giant_vs_oracle_on_simulator_batches(emu, oracle_lib):
@@ -78,11 +88,12 @@ def test_giant_vs_real_reference_on_exhaustive_slices(emu, name, stride):
 def test_windows_only_class_6_holds_vs_real_reference(emu, oracle_lib):
     import oracle
     rng = np.random.default_rng(606)
-    wins = giant_windows(rng)
+    wins = giant_windows(rng, most_arms=True)
     b = build_batch(wins)
     off = b.slot_layout()
     cons, st, res, cells, aligns = emu.poa_giant(b, off=off, slice_bytes=96 << 20)
     assert (res == emu_util.RES_OK).all() and (st == 0).all()
+    assert len(cons[3]) > 1900                                   # the insertion is in the consensus
     want, wst, wc, wa = oracle_lib.poa_batch(b, off=off)
     assert cons == want and cells == wc and aligns == wa
     if oracle.Ref.available():
@@ -91,7 +102,7 @@ def test_windows_only_class_6_holds_vs_real_reference(emu, oracle_lib):
         assert (rst == 0).all(), "the LONG window's arms must pass the reference's own filter (one shared minimizer per 50 bases)"
         assert cons == [rb[int(off[i]):int(off[i]) + int(rln[i])].tobytes().decode() for i in range(b.n_windows)]
     # the classes below cannot take them: class 5 answers "overflow" (the kernel then queues the window for class 6)
-    c5, st5, res5, _, _ = emu.poa_batch(build_batch(wins[:2]), 5)
+    c5, st5, res5, _, _ = emu.poa_batch(build_batch(wins[:2] + wins[3:]), 5)
     assert all(r in (emu_util.RES_OVERFLOW, emu_util.RES_UNSUPPORTED) for r in res5)
 
 
