@@ -5,7 +5,7 @@ Reference types mirrored: ScoreParams (include/globalDefs.hpp:58-66), hypo::Wind
 """
 import ctypes as C
 
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 HYPO_OK = 0
 HYPO_E_INVALID = -1

@@ -29,6 +29,7 @@ EXPORTS = [
     "hypo_gpu_solid_scan_keep", "hypo_gpu_solid_release", "hypo_gpu_support_kmers_kept", "hypo_gpu_host_alloc", "hypo_gpu_host_free", "hypo_gpu_host_register", "hypo_gpu_host_unregister",
     "hypo_gpu_kmer_count_begin", "hypo_gpu_kmer_count_add", "hypo_gpu_kmer_histogram", "hypo_gpu_solid_set_build",
     "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts",
+    "hypo_gpu_kset_begin", "hypo_gpu_kset_add", "hypo_gpu_kset_size", "hypo_gpu_kset_query", "hypo_gpu_kset_end",
 ]
 
 
@@ -249,6 +250,42 @@ class HypoGpu:
         ops = "=XDI"
         cigars = ["".join(f"{int(r) >> 2}{ops[int(r) & 3]}" for r in runs[int(run_off[i]):int(run_off[i + 1])]) for i in range(len(dist))]
         return dist, cigars
+
+    # ---- the exact k-mer set of the reads (ABI 11; hypo --qv) ---------------------------------------------------------------
+    def use_device(self, slot: int):
+        self._check(self.lib.hypo_gpu_use_device(C.c_int(slot)))
+
+    def kset_begin(self, k: int, expected_distinct: int = 0, max_bytes: int = 0):
+        self._check(self.lib.hypo_gpu_kset_begin(C.c_uint32(k), C.c_uint64(expected_distinct), C.c_uint64(max_bytes)))
+
+    def kset_add_rc(self, data) -> int:
+        """the return code of hypo_gpu_kset_add (HYPO_E_CAPACITY is an answer, not a failure of the binding)"""
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        return int(self.lib.hypo_gpu_kset_add(_p(a), C.c_uint64(a.size)))
+
+    def kset_add(self, data):
+        self._check(self.kset_add_rc(data))
+
+    def kset_size(self):
+        """(distinct k-mers in the set, bytes of its table)"""
+        n, b = C.c_uint64(0), C.c_uint64(0)
+        self._check(self.lib.hypo_gpu_kset_size(C.byref(n), C.byref(b)))
+        return int(n.value), int(b.value)
+
+    def kset_query(self, seqs):
+        """seqs: byte strings.  (total u64[n], missing u64[n]): the ACGT-only windows of every sequence and those not in the set"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        n = len(seqs)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+        data = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)
+        total = np.zeros(max(n, 1), dtype=np.uint64)
+        missing = np.zeros(max(n, 1), dtype=np.uint64)
+        self._check(self.lib.hypo_gpu_kset_query(_p(data), _p(off), C.c_uint32(n), _p(total), _p(missing)))
+        return total[:n], missing[:n]
+
+    def kset_end(self):
+        self._check(self.lib.hypo_gpu_kset_end())
 
     def _solid_build_files(self, paths, k, coverage):
         from .host import LIB_PATH as HOST_LIB

@@ -19,6 +19,7 @@
 #include "scan_kernel.hpp"
 #include "kmer_kernel.hpp"
 #include "edit_kernel.hpp"
+#include "kset_kernel.hpp"
 
 namespace {
 
@@ -154,6 +155,14 @@ struct Ctx {
     };
     struct EditBufs { DevBuf a, b, a_off, b_off, res, pool, lists, ctr, moves, moves_off, vals, vals_off; EditKept kept; };
     EditBufs ed;
+    // hypo_gpu_kset_begin .. _end: the hash table (exact size; replaced by a larger one when it grows), the number of keys in it, the
+    // bytes / offsets / results of the call in hand, the two counters of the kernels; what the growths cost (HYPO_KSET_STATS)
+    struct KSet {
+        uint64_t* table = nullptr; uint64_t slots = 0, max_slots = 0, count = 0; uint32_t k = 0; DevBuf in, off, res, ctr;
+        uint32_t growths = 0; double grow_s = 0; uint64_t peak_slots = 0;
+    };
+    KSet ks;
+    size_t mem_free_at_init = 0;                       // hipMemGetInfo when the context was created (default cap of the k-mer set)
     // hypo_gpu_solid_scan_keep: the marked positions (contig-local) and their k-mers stay on the device, one pair of exact-size
     // buffers per handle (the caller's contig number); hypo_gpu_support_kmers_kept votes against them
     struct KeptScan { void* kids = nullptr; uint32_t* spos = nullptr; uint64_t n = 0, n_bases = 0; uint32_t k = 0; bool used = false; };
@@ -383,6 +392,9 @@ static void release_ctx(Ctx& c) {
         c.kc.in.release(); c.kc.misc.release(); c.kc = Ctx::KmerCount();
         for (DevBuf* d : {&c.ed.a, &c.ed.b, &c.ed.a_off, &c.ed.b_off, &c.ed.res, &c.ed.pool, &c.ed.lists, &c.ed.ctr, &c.ed.moves, &c.ed.moves_off, &c.ed.vals, &c.ed.vals_off}) d->release();
         c.ed.kept = Ctx::EditKept();
+        if (c.ks.table) (void)hipFree(c.ks.table);
+        for (DevBuf* d : {&c.ks.in, &c.ks.off, &c.ks.res, &c.ks.ctr}) d->release();
+        c.ks = Ctx::KSet();
         c.bounce.release();
         for (auto& ks : c.kept) { if (ks.kids) (void)hipFree(ks.kids); if (ks.spos) (void)hipFree(ks.spos); }
         c.kept.clear();
@@ -417,6 +429,8 @@ int hypo_gpu_init(const int* device_ids, int n_devices) {
         HIP_TRY(hipStreamCreateWithFlags(&c.stream, hipStreamNonBlocking));
         c.slots[0].stream = c.stream;                      // (slot 1's stream is created when a second batch is first put in flight)
         c.device = device_ids[i]; c.num_cus = prop.multiProcessorCount; c.ready = true;
+        size_t mem_total = 0;
+        if (hipMemGetInfo(&c.mem_free_at_init, &mem_total) != hipSuccess) { (void)hipGetLastError(); c.mem_free_at_init = 0; }
         g_nctx = i + 1;
     }
     if (!getenv("HYPO_NO_WARMUP")) for (int i = 0; i < g_nctx; ++i) warm_up(&g_ctxs[i]);
@@ -1075,6 +1089,159 @@ int hypo_gpu_kmer_count_end(void) {
     if (kc.table) HIP_TRY(hipFree(kc.table));
     kc.in.release(); kc.misc.release();
     kc = Ctx::KmerCount();
+    return HYPO_OK;
+}
+
+}  // extern "C"
+// ---- the exact k-mer set of the reads (kset_kernel.hip; hypo --qv) -----------------------------------------------------------------
+namespace {
+double ks_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+uint64_t ks_slots_for(uint64_t keys) {                 // the smallest table that holds `keys` at KSET_MAX_LOAD
+    const uint64_t s = (uint64_t)((double)keys / hypo::KSET_MAX_LOAD) + 1;
+    return s < hypo::KSET_MIN_SLOTS ? hypo::KSET_MIN_SLOTS : s;
+}
+// A fresh table of `slots` slots takes the keys of the present one (if any) and its place.
+int ks_resize(Ctx::KSet& ks, uint64_t slots, hipStream_t st) {
+    const double t0 = ks_now();
+    uint64_t* fresh = nullptr;
+    hipError_t e = hipMalloc((void**)&fresh, slots * 8);
+    if (e != hipSuccess) { (void)hipGetLastError(); return fail(HYPO_E_HIP, "hipMalloc of a k-mer set table of %.3f GiB (%llu k-mers in the set): %s",
+                                                                 (double)slots * 8 / (1u << 30), (unsigned long long)ks.count, hipGetErrorString(e)); }
+    unsigned long long ctr[2] = {0, 0};
+    if ((e = hipMemsetAsync(fresh, 0xff, slots * 8, st)) == hipSuccess && (e = hipMemsetAsync(ks.ctr.p, 0, 16, st)) == hipSuccess && ks.table)
+        e = hypo::kset_rehash_run(ks.table, ks.slots, fresh, slots, (unsigned long long*)ks.ctr.p, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(ctr, ks.ctr.p, 16, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFree(fresh); return fail(HYPO_E_HIP, "k-mer set: resizing to %llu slots: %s", (unsigned long long)slots, hipGetErrorString(e)); }
+    if (ctr[1] || ctr[0] != ks.count) {
+        (void)hipFree(fresh);
+        return fail(HYPO_E_HIP, "k-mer set: internal error: %llu of %llu keys moved into %llu slots (overflow flag %llu)", ctr[0],
+                    (unsigned long long)ks.count, (unsigned long long)slots, ctr[1]);
+    }
+    if (ks.table) { (void)hipFree(ks.table); ++ks.growths; ks.grow_s += ks_now() - t0; }
+    ks.table = fresh; ks.slots = slots;
+    if (slots > ks.peak_slots) ks.peak_slots = slots;
+    return HYPO_OK;
+}
+}  // namespace
+
+extern "C" {
+
+int hypo_gpu_kset_begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    if (k < 12 || k > 31) return fail(HYPO_E_INVALID, "k=%u out of range 12..31 (the key is the 2k-bit canonical code in a 64-bit slot)", k);
+    if (!max_bytes) max_bytes = g_ctx.mem_free_at_init / 2;            // default cap: half of what the device had free at init
+    const uint64_t max_slots = max_bytes / 8;
+    if (max_slots < 2) return fail(HYPO_E_INVALID, "max_bytes = %llu holds no table", (unsigned long long)max_bytes);
+    Ctx::KSet& ks = g_ctx.ks;
+    if (ks.table) { (void)hipFree(ks.table); ks.table = nullptr; }
+    ks.k = 0; ks.slots = 0; ks.count = 0; ks.growths = 0; ks.grow_s = 0; ks.peak_slots = 0;
+    ks.max_slots = max_slots;
+    HIP_TRY(ks.ctr.alloc(16));
+    uint64_t slots = ks_slots_for(expected_distinct < ((uint64_t)1 << 62) ? expected_distinct : ((uint64_t)1 << 62));
+    if (slots > max_slots) slots = max_slots;
+    const int rc = ks_resize(ks, slots, g_ctx.stream);
+    if (rc != HYPO_OK) return rc;
+    ks.k = k;
+    return HYPO_OK;
+}
+
+int hypo_gpu_kset_add(const char* bytes, uint64_t n) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    Ctx::KSet& ks = g_ctx.ks;
+    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    if (n < ks.k) return HYPO_OK;                                       // holds no k-mer
+    if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
+    hipStream_t st = g_ctx.stream;
+    // Room for the call's worst case (every window a new k-mer) is made before the table is touched: a call that cannot get it
+    // leaves the set as it was, and no kernel ever meets a table more than half full.
+    const uint64_t worst = ks.count + (n - ks.k + 1);
+    const uint64_t need = ks_slots_for(worst);
+    if (need > ks.slots) {
+        if (need > ks.max_slots)
+            return fail(HYPO_E_CAPACITY, "the k-mer set holds %llu distinct %u-mers in a table of %.3f GiB; %llu more windows need %.3f GiB, the cap is %.3f GiB (--qv-mem)",
+                        (unsigned long long)ks.count, ks.k, (double)ks.slots * 8 / (1u << 30), (unsigned long long)(n - ks.k + 1),
+                        (double)need * 8 / (1u << 30), (double)ks.max_slots * 8 / (1u << 30));
+        uint64_t slots = need > 2 * ks.slots ? need : 2 * ks.slots;
+        if (slots > ks.max_slots) slots = ks.max_slots;
+        const int rc = ks_resize(ks, slots, st);
+        if (rc != HYPO_OK) return rc;
+    }
+    HIP_TRY(ks.in.alloc(n < kKmerPiece ? n : kKmerPiece));
+    // pieces as in hypo_gpu_kmer_count_add; a k-mer seen by two pieces is inserted twice, which changes nothing
+    for (uint64_t at = 0;;) {
+        const uint64_t m = n - at < kKmerPiece ? n - at : kKmerPiece;
+        unsigned long long ctr[2] = {0, 0};
+        HIP_TRY(h2d(ks.in.p, bytes + at, m, st));
+        HIP_TRY(hipMemsetAsync(ks.ctr.p, 0, 16, st));
+        HIP_TRY(hypo::kset_insert_run((const uint8_t*)ks.in.p, m, ks.k, ks.table, ks.slots, (unsigned long long*)ks.ctr.p, st));
+        HIP_TRY(hipMemcpyAsync(ctr, ks.ctr.p, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));                   // (the caller may refill `bytes` when this returns)
+        ks.count += ctr[0];
+        if (ctr[1]) return fail(HYPO_E_HIP, "k-mer set: internal error: a table of %llu slots with %llu keys had no room", (unsigned long long)ks.slots, (unsigned long long)ks.count);
+        if (at + m >= n) break;
+        at += m - (ks.k - 1);
+    }
+    return HYPO_OK;
+}
+
+int hypo_gpu_kset_size(uint64_t* n_distinct, uint64_t* table_bytes) {
+    HYPO_LOCKED();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    const Ctx::KSet& ks = g_ctx.ks;
+    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    if (n_distinct) *n_distinct = ks.count;
+    if (table_bytes) *table_bytes = ks.slots * 8;
+    return HYPO_OK;
+}
+
+int hypo_gpu_kset_query(const char* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t* total, uint64_t* missing) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    Ctx::KSet& ks = g_ctx.ks;
+    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    if (!n_seqs) return HYPO_OK;
+    if (!off || !total || !missing) return fail(HYPO_E_INVALID, "NULL buffer");
+    std::vector<uint64_t> rel((size_t)n_seqs + 1);
+    for (uint32_t i = 0; i <= n_seqs; ++i) {
+        if (off[i] < off[0] || (i && off[i] < off[i - 1])) return fail(HYPO_E_INVALID, "off[] must not decrease (entry %u)", i);
+        rel[i] = off[i] - off[0];
+    }
+    const uint64_t n = rel[n_seqs];
+    for (uint32_t i = 0; i < n_seqs; ++i) total[i] = missing[i] = 0;
+    if (!n) return HYPO_OK;
+    if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
+    hipStream_t st = g_ctx.stream;
+    HIP_TRY(ks.in.alloc(n));
+    HIP_TRY(ks.off.alloc(rel.size() * 8));
+    HIP_TRY(ks.res.alloc((size_t)n_seqs * 16));
+    unsigned long long* d_tot = (unsigned long long*)ks.res.p;
+    unsigned long long* d_mis = d_tot + n_seqs;
+    HIP_TRY(h2d(ks.in.p, bytes + off[0], n, st));
+    HIP_TRY(hipMemcpyAsync(ks.off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(ks.res.p, 0, (size_t)n_seqs * 16, st));
+    HIP_TRY(hypo::kset_query_run((const uint8_t*)ks.in.p, (const uint64_t*)ks.off.p, n_seqs, n, ks.k, ks.table, ks.slots, d_tot, d_mis, st));
+    HIP_TRY(hipMemcpyAsync(total, d_tot, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(missing, d_mis, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HYPO_OK;
+}
+
+int hypo_gpu_kset_end(void) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    Ctx::KSet& ks = g_ctx.ks;
+    if (ks.k && getenv("HYPO_KSET_STATS"))
+        fprintf(stderr, "[kset] k %u, %llu keys, %llu slots (peak %llu), %u growths in %.6f s\n", ks.k, (unsigned long long)ks.count,
+                (unsigned long long)ks.slots, (unsigned long long)ks.peak_slots, ks.growths, ks.grow_s);
+    if (ks.table) HIP_TRY(hipFree(ks.table));
+    for (DevBuf* d : {&ks.in, &ks.off, &ks.res, &ks.ctr}) d->release();
+    ks = Ctx::KSet();
     return HYPO_OK;
 }
 

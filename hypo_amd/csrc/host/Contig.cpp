@@ -570,6 +570,13 @@ void Contig::collect_units(std::vector<EditUnit>& units) const {
 // ---- operator<< (src/Contig.cpp:345-366): one-line FASTA record -------------------------------------------------------
 std::ostream& operator<<(std::ostream& os, const Contig& ctg) {
     os << ">" << ctg._name << std::endl;
+    os << ctg.polished_text();
+    os << std::endl;
+    return os;
+}
+
+std::string Contig::polished_text() const {
+    const Contig& ctg = *this;
     const size_t num_reg = ctg._reg_type.size() - 1;
     // the record is put together in one string: where every region's text goes is a prefix sum over the regions, the pieces are
     // copied on all threads (the reference streams them one by one; the bytes are the same)
@@ -589,9 +596,7 @@ std::ostream& operator<<(std::ostream& os, const Contig& ctg) {
         if (kd == 0) { for (uint64_t p = starts[i]; p < starts[i + 1]; ++p) *dst++ = ctg._pseq.base_at(p); }
         else if (kd == 1) { const std::string& c = ctg._pwindows[i]->consensus_ref(); std::memcpy(dst, c.data(), c.size()); }
     }
-    os << text;
-    os << std::endl;
-    return os;
+    return text;
 }
 
 }  // namespace hypo

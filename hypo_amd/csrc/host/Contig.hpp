@@ -69,6 +69,7 @@ public:
     // checks later alignments against them)
     void release_after_output();
     friend std::ostream& operator<<(std::ostream&, const Contig&);
+    std::string polished_text() const;                      // the sequence line operator<< writes (hypo --qv asks the k-mer set about it)
     friend class Alignment;
     friend class DeviceArms;
 

@@ -3,6 +3,7 @@
 #include "DeviceArms.hpp"
 #include "SolidBuild.hpp"
 #include "EditVcf.hpp"
+#include "QvReport.hpp"
 #include <ctime>
 #include <omp.h>
 #include <sys/resource.h>
@@ -19,9 +20,11 @@ extern std::atomic<uint64_t> g_stage_counters[5];      // host/Contig.cpp
 namespace {
 std::string pending_tmp;                               // <output>.tmp while a run is writing it (Hypo::polish); removed by a run that fails
 std::string pending_vcf_tmp;                           // <vcf>.tmp likewise (--vcf)
+std::string pending_qv_tmp;                            // <qv>.tmp while it is written (--qv)
 void remove_pending_output() {
     if (!pending_tmp.empty()) std::remove(pending_tmp.c_str());
     if (!pending_vcf_tmp.empty()) std::remove(pending_vcf_tmp.c_str());
+    if (!pending_qv_tmp.empty()) std::remove(pending_qv_tmp.c_str());
 }
 }
 
@@ -46,6 +49,30 @@ void Hypo::polish() {
         std::fprintf(stderr, "[Hypo::Hypo] Error: --vcf needs hypo_gpu_edit_scripts (C-ABI 10), which the device library does not provide\n");
         std::exit(1);
     }
+    // --qv: likewise the exact k-mer set (C-ABI 11).  It lives on context 0 from here until the last contig is written.
+    const bool qv_on = !_cFlags.qv_filename.empty();
+    QvReport qv;
+    if (qv_on && !qv.bind()) {
+        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv needs hypo_gpu_kset_begin / _add / _size / _query / _end (C-ABI 11), which the device library does not provide\n");
+        std::exit(1);
+    }
+    auto qv_fail = [&](const char* what) {
+        std::fprintf(stderr, "[Hypo::QV] Error: %s: %s\n", what, hypo_gpu_last_error());
+        qv.end();
+        std::exit(1);
+    };
+    ReadSink qv_sink;
+    if (qv_on) {
+        // (sized for one k-mer per genome position; what the read errors add makes it grow)
+        const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
+        if (qv.begin(_cFlags.qv_k, _cFlags.genome_size, cap, 0) != HYPO_OK) qv_fail("the k-mer set could not be created");
+        qv_sink = qv.sink();
+    }
+    auto qv_reads_done = [&](const SolidBuildStats& st, bool shared_pass) {
+        if (qv.read_size() != HYPO_OK) qv_fail("hypo_gpu_kset_size");
+        std::fprintf(stderr, "[Hypo::QV] Info: k-mer set of the reads (k = %u): %llu distinct k-mers, %.3f s in the insert calls of %.3f GB%s\n", qv.k(),
+                     (unsigned long long)qv.n_distinct(), st.sink_s, st.seq_bytes / 1e9, shared_pass ? " (the parse pass of the solid k-mers)" : " (reads parsed for the QV alone)");
+    };
     std::ofstream stagefile(HYPO_STAGEFILE, std::ofstream::out | std::ofstream::app);
     if (_cFlags.intermed && !stagefile.is_open()) {
         std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: Stage File (%s) exists but could not be opened!\n", HYPO_STAGEFILE);
@@ -57,7 +84,8 @@ void Hypo::polish() {
     if (_cFlags.done_stage < 1) {
         SolidBuildStats st;
         std::string err;
-        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err);
+        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err, qv_on ? &qv_sink : nullptr);
+        if (rc == SOLID_E_SINK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); qv.end(); std::exit(1); }
         if (rc == SOLID_E_UNDEFINED) {                   // the reference's own line for a failed initialise (src/Hypo.cpp:53)
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: %s\n", err.c_str());
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: KMC Output: Could not have successful run of SUK for computing Solid kmers!\n");
@@ -69,6 +97,7 @@ void Hypo::polish() {
         }
         std::fprintf(stderr, "[Hypo::SolidKmers] Info: device construction: %.3f s (parse %.3f s of %.3f GB, count %.3f s of %.3f GB sent, "
                              "histogram %.3f s, set %.3f s)\n", st.total_s, st.parse_s, st.file_bytes / 1e9, st.count_s, st.seq_bytes / 1e9, st.hist_s, st.fill_s);
+        if (qv_on) qv_reads_done(st, true);
         if (_cFlags.intermed) {
             if (!sk.store(HYPO_SKFILE)) {
                 std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Saving: Could not store the DS for Solid kmers!\n");
@@ -86,6 +115,13 @@ void Hypo::polish() {
         if (!sk.load(HYPO_SKFILE)) {
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Loading: Could not load the DS for Solid kmers (%s)!\n", HYPO_SKFILE);
             std::exit(1);
+        }
+        if (qv_on) {                                     // the stored set needs no reads; the QV does
+            SolidBuildStats st;
+            std::string err;
+            const int rc = stream_reads(_cFlags.sr_filenames, qv_sink, st, err);
+            if (rc != SOLID_OK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); qv.end(); std::exit(1); }
+            qv_reads_done(st, false);
         }
         stop("[Hypo:Hypo]: Loaded Solid kmers. ");
     }
@@ -591,7 +627,7 @@ void Hypo::polish() {
         // next batch's stages on this thread) and formats each contig's records next to its FASTA record, before the contig's
         // windows go
         if (writer.joinable()) writer.join();
-        writer = std::thread([this, &ofile, &vfile, &vstats, edit_fn, initial_cid, final_cid] {
+        writer = std::thread([this, &ofile, &vfile, &vstats, &qv, qv_on, edit_fn, initial_cid, final_cid] {
             omp_set_num_threads(std::max(1, std::min((int)_cFlags.threads, 8)));
             std::unique_ptr<EditBatchResult> edits;
             if (edit_fn) {
@@ -604,10 +640,25 @@ void Hypo::polish() {
                     std::_Exit(1);
                 }
             }
+            // --qv: the draft and the polished text of every contig of the batch go to the k-mer set in one query on context 0
+            int qrc = qv_on ? hypo_gpu_use_device(0) : HYPO_OK;
             for (uint32_t c = initial_cid; c < final_cid; ++c) {
-                ofile << *_contigs[c];
+                if (qv_on) {
+                    const std::string text = _contigs[c]->polished_text();
+                    ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;      // (operator<<'s bytes)
+                    if (qrc == HYPO_OK) qrc = qv.push(c, _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()), text);
+                } else {
+                    ofile << *_contigs[c];
+                }
                 if (edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, vstats);
                 _contigs[c]->release_after_output();
+            }
+            if (qv_on && qrc == HYPO_OK) qrc = qv.flush();
+            if (qrc != HYPO_OK) {
+                std::fprintf(stderr, "[Hypo::Hypo] Error: k-mer set query: %s\n", hypo_gpu_last_error());
+                std::fflush(nullptr);
+                remove_pending_output();
+                std::_Exit(1);
             }
         });
     }
@@ -623,6 +674,18 @@ void Hypo::polish() {
         vfile.close();
         if (!vfile) { std::fprintf(stderr, "[Hypo::Hypo] Error: writing the VCF file (%s) failed!\n", pending_vcf_tmp.c_str()); std::exit(1); }
     }
+    // --qv: the table is formatted once, closed and checked like the others; the set has answered its last query
+    if (qv_on) {
+        qv.end();
+        pending_qv_tmp = _cFlags.qv_filename + ".tmp";
+        std::ofstream qfile(pending_qv_tmp);
+        if (!qfile.is_open()) { std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: QV File (%s) could not be opened!\n", pending_qv_tmp.c_str()); std::exit(1); }
+        std::vector<std::string> names;
+        for (const auto& c : _contigs) names.push_back(c->get_name());
+        qv.write(qfile, names);
+        qfile.close();
+        if (!qfile) { std::fprintf(stderr, "[Hypo::Hypo] Error: writing the QV file (%s) failed!\n", pending_qv_tmp.c_str()); std::exit(1); }
+    }
     if (std::rename(pending_tmp.c_str(), _cFlags.output_filename.c_str()) != 0) {
         std::fprintf(stderr, "[Hypo::Hypo] Error: could not move %s to %s!\n", pending_tmp.c_str(), _cFlags.output_filename.c_str());
         std::exit(1);
@@ -637,6 +700,17 @@ void Hypo::polish() {
         pending_vcf_tmp.clear();
         std::fprintf(stdout, "[Hypo::Hypo] Info: VCF %s: %llu records, %llu substituted, %llu inserted, %llu deleted bases\n", _cFlags.vcf_filename.c_str(),
                      (unsigned long long)vstats.records, (unsigned long long)vstats.sub, (unsigned long long)vstats.ins, (unsigned long long)vstats.del);
+    }
+    if (qv_on) {
+        if (std::rename(pending_qv_tmp.c_str(), _cFlags.qv_filename.c_str()) != 0) {
+            std::fprintf(stderr, "[Hypo::Hypo] Error: could not move %s to %s!\n", pending_qv_tmp.c_str(), _cFlags.qv_filename.c_str());
+            std::remove(_cFlags.output_filename.c_str());
+            if (edit_fn) std::remove(_cFlags.vcf_filename.c_str());
+            std::exit(1);
+        }
+        pending_qv_tmp.clear();
+        std::fprintf(stdout, "[Hypo::Hypo] Info: QV %s (k = %u, %llu distinct read k-mers): draft %s, polished %s\n", _cFlags.qv_filename.c_str(), qv.k(),
+                     (unsigned long long)qv.n_distinct(), qv.draft_qv().c_str(), qv.polished_qv().c_str());
     }
     stop("[Hypo:Hypo]: Writing results. ");
     _times.overall = std::chrono::duration<double>(std::chrono::steady_clock::now() - _tstart).count();

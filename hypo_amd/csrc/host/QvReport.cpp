@@ -1,0 +1,91 @@
+// QvReport.cpp — see QvReport.hpp.
+#include "QvReport.hpp"
+#include <dlfcn.h>
+#include <cmath>
+#include <cstdio>
+
+namespace hypo {
+
+std::string qv_text(uint64_t missing, uint64_t total, uint32_t k) {
+    if (!total) return "NA";
+    if (!missing) return "inf";
+    const double err = 1.0 - std::pow(1.0 - (double)missing / (double)total, 1.0 / (double)k);
+    char b[64];
+    std::snprintf(b, sizeof b, "%.2f", -10.0 * std::log10(err) + 0.0);          // (+ 0.0: every k-mer missing prints 0.00, not -0.00)
+    return b;
+}
+
+bool QvReport::bind() {
+    _begin = (decltype(_begin))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_begin");
+    _add = (decltype(_add))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_add");
+    _size = (decltype(_size))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_size");
+    _query = (decltype(_query))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_query");
+    _end = (decltype(_end))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_end");
+    return _begin && _add && _size && _query && _end;
+}
+
+int QvReport::begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes, size_t n_contigs) {
+    const int rc = _begin(k, expected_distinct, max_bytes);
+    if (rc != HYPO_OK) return rc;
+    _open = true; _k = k;
+    _rows.assign(n_contigs, Row());
+    _off.assign(1, 0);
+    return HYPO_OK;
+}
+
+ReadSink QvReport::sink() {
+    ReadSink s;
+    s.k = _k;
+    s.add = [this](const char* p, uint64_t n) { return _add(p, n); };
+    return s;
+}
+
+int QvReport::read_size() { return _size(&_n_distinct, nullptr); }
+
+int QvReport::push(size_t contig, const std::string& draft, const std::string& polished) {
+    constexpr size_t kFlushAt = (size_t)512 << 20;           // text per query call (a batch of small contigs: one call)
+    if (_rows.size() <= contig) _rows.resize(contig + 1);
+    _text += draft; _off.push_back(_text.size());
+    _text += polished; _off.push_back(_text.size());
+    _who.push_back(contig);
+    return _text.size() >= kFlushAt ? flush() : HYPO_OK;
+}
+
+int QvReport::flush() {
+    if (_who.empty()) return HYPO_OK;
+    const uint32_t n = (uint32_t)(_off.size() - 1);
+    std::vector<uint64_t> total(n), missing(n);
+    const int rc = _query(_text.data(), _off.data(), n, total.data(), missing.data());
+    if (rc != HYPO_OK) return rc;
+    for (size_t i = 0; i < _who.size(); ++i) {
+        Row& r = _rows[_who[i]];
+        r.dt = total[2 * i]; r.dm = missing[2 * i]; r.pt = total[2 * i + 1]; r.pm = missing[2 * i + 1];
+    }
+    _text.clear(); _off.assign(1, 0); _who.clear();
+    return HYPO_OK;
+}
+
+void QvReport::end() {
+    if (_open) (void)_end();
+    _open = false;
+    std::string().swap(_text);
+}
+
+QvReport::Row QvReport::sums() const {
+    Row s;
+    for (const Row& r : _rows) { s.dm += r.dm; s.dt += r.dt; s.pm += r.pm; s.pt += r.pt; }
+    return s;
+}
+std::string QvReport::draft_qv() const { const Row s = sums(); return qv_text(s.dm, s.dt, _k); }
+std::string QvReport::polished_qv() const { const Row s = sums(); return qv_text(s.pm, s.pt, _k); }
+
+void QvReport::write(std::ostream& os, const std::vector<std::string>& names) const {
+    os << "#contig\tdraft_missing\tdraft_total\tdraft_qv\tpolished_missing\tpolished_total\tpolished_qv\n";
+    auto row = [&](const std::string& name, const Row& r) {
+        os << name << '\t' << r.dm << '\t' << r.dt << '\t' << qv_text(r.dm, r.dt, _k) << '\t' << r.pm << '\t' << r.pt << '\t' << qv_text(r.pm, r.pt, _k) << '\n';
+    };
+    for (size_t i = 0; i < names.size(); ++i) row(names[i], i < _rows.size() ? _rows[i] : Row());
+    row("*", sums());
+}
+
+}  // namespace hypo

@@ -1,0 +1,52 @@
+// QvReport.hpp — hypo --qv: the reference-free k-mer QV of every draft contig and of its polished text (DESIGN.md "k-mer QV").
+// The canonical k-mers of the short reads are kept as an exact set on device context 0 (hypo_gpu_kset_*, kset_kernel.hip), filled
+// by the parse pass of stage 0; the writer thread asks it, per contig batch, how many k-mers of the drafts and of the polished
+// texts it lacks.  QV = -10 log10(1 - (1 - missing / total)^(1 / k)) (Merqury's definition: a k-mer seen once is present).
+#pragma once
+#include <cstdint>
+#include <ostream>
+#include <string>
+#include <vector>
+#include "SolidBuild.hpp"
+
+namespace hypo {
+
+// "%.2f" of the QV; "inf" when nothing is missing, "NA" when there is no window
+std::string qv_text(uint64_t missing, uint64_t total, uint32_t k);
+
+class QvReport {
+public:
+    // binds hypo_gpu_kset_* by name: only runs with --qv need them (false: the device library does not provide them)
+    bool bind();
+    // the set on the calling thread's context; max_bytes 0 = the library's default cap
+    int begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes, size_t n_contigs);
+    ReadSink sink();
+    int read_size();                                         // after the reads: fetches the number of distinct k-mers
+    uint64_t n_distinct() const { return _n_distinct; }
+    uint32_t k() const { return _k; }
+    // one contig's two texts; they are queried (one call on the calling thread's context) when flush() is called or enough text has
+    // gathered.  HYPO_OK or the C-ABI's error.
+    int push(size_t contig, const std::string& draft, const std::string& polished);
+    int flush();
+    void end();                                              // frees the set (safe to call twice)
+    // the table: one row per contig in draft order, then the sums as contig "*"
+    void write(std::ostream& os, const std::vector<std::string>& names) const;
+    std::string draft_qv() const, polished_qv() const;       // of the sums
+private:
+    struct Row { uint64_t dm = 0, dt = 0, pm = 0, pt = 0; };
+    Row sums() const;
+    int (*_begin)(uint32_t, uint64_t, uint64_t) = nullptr;
+    int (*_add)(const char*, uint64_t) = nullptr;
+    int (*_size)(uint64_t*, uint64_t*) = nullptr;
+    int (*_query)(const char*, const uint64_t*, uint32_t, uint64_t*, uint64_t*) = nullptr;
+    int (*_end)(void) = nullptr;
+    bool _open = false;
+    uint32_t _k = 0;
+    uint64_t _n_distinct = 0;
+    std::vector<Row> _rows;
+    std::string _text;                                       // the texts waiting for a query, back to back
+    std::vector<uint64_t> _off;
+    std::vector<size_t> _who;                                // contig of every pair of texts in _text
+};
+
+}  // namespace hypo

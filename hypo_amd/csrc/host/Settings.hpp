@@ -25,6 +25,10 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     bool host_arms = false;                // new, opt-in: --host-arms (cut the short reads into arms on the host, not on the device)
     bool ccs_windows = false;              // new, opt-in: --ccs-windows (the window sizes -k ccs was meant to select)
     std::string vcf_filename;              // new, opt-in: --vcf <file> (every edit of the run as VCF records beside the FASTA)
+    std::string qv_filename;               // new, opt-in: --qv <file> (k-mer QV of every draft and polished contig against the reads' k-mers)
+    uint32_t qv_k = 21;                    // new, opt-in: --qv-k (12..31)
+    double qv_mem_gib = 0;                 // new, opt-in: --qv-mem (cap of the k-mer set; 0 = half of the device's free memory)
+    uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
 };
 
 enum class RegionType : uint8_t { SWS, SW, WS, MWM, MW, WM, SWM, MWS, OTHER, LONG, SR, MSR };   // globalDefs.hpp:95-108

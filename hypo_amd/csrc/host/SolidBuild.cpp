@@ -109,7 +109,9 @@ struct KmerApi {
 
 // Sequence bytes of the read files, cut into chunks for hypo_gpu_kmer_count_add: the bases of a record (its sequence lines
 // joined), one '\n' between records.  A chunk that fills up in the middle of a record is handed over as it is and the next chunk
-// starts with its last k - 1 bytes: every k-mer lies whole in exactly one chunk.
+// starts with its last k - 1 bytes: every k-mer lies whole in exactly one chunk.  (With a second consumer whose k-mers are longer,
+// k is the larger of the two and next() says how many bytes at the front of a chunk are such a repeat: the count table, which must
+// see every k-mer once, is given the chunk from its own k - 1 bytes before the end of that lead.)
 class ChunkPipe {
 public:
     ChunkPipe(size_t cap, uint32_t k) : _cap(cap), _carry(k - 1) {
@@ -133,12 +135,13 @@ public:
     void sep() { if (_buf[_fill].n && _buf[_fill].data[_buf[_fill].n - 1] != '\n') { const char c = '\n'; put(&c, 1); } }
     void finish() { if (_buf[_fill].n) hand_over(false); std::lock_guard<std::mutex> lk(_mu); _done = true; _cv.notify_all(); }
     // consumer side: the next full chunk (nullptr at the end); release() when it has been counted
-    const char* next(size_t& n) {
+    const char* next(size_t& n, size_t& lead) {
         std::unique_lock<std::mutex> lk(_mu);
         _cv.wait(lk, [this] { return _ready >= 0 || _done; });
         if (_ready < 0) return nullptr;
         _taking = _ready; _ready = -1;
         n = _buf[_taking].n;
+        lead = _buf[_taking].lead;
         return _buf[_taking].data;
     }
     void release() { std::lock_guard<std::mutex> lk(_mu); _buf[_taking].n = 0; _taking = -1; _cv.notify_all(); }
@@ -146,7 +149,7 @@ public:
     bool aborted() { std::lock_guard<std::mutex> lk(_mu); return _aborted; }
     uint64_t bytes_out = 0;
 private:
-    struct Buf { char* data = nullptr; size_t n = 0; bool pinned = false; std::vector<char> own; };
+    struct Buf { char* data = nullptr; size_t n = 0, lead = 0; bool pinned = false; std::vector<char> own; };
     void hand_over(bool carry) {
         std::unique_lock<std::mutex> lk(_mu);
         const int other = _fill ^ 1;
@@ -155,7 +158,8 @@ private:
         Buf& cur = _buf[_fill];
         Buf& nxt = _buf[other];
         bytes_out += cur.n;
-        if (carry && _carry) { std::memcpy(nxt.data, cur.data + cur.n - _carry, _carry); nxt.n = _carry; }
+        nxt.lead = 0;
+        if (carry && _carry) { std::memcpy(nxt.data, cur.data + cur.n - _carry, _carry); nxt.n = nxt.lead = _carry; }
         _ready = _fill; _fill = other;
         _cv.notify_all();
     }
@@ -204,10 +208,56 @@ bool parse_reads(const std::string& path, ChunkPipe& pipe, uint64_t& file_bytes,
 
 double secs(std::chrono::steady_clock::time_point a) { return std::chrono::duration<double>(std::chrono::steady_clock::now() - a).count(); }
 
+// The files through one parser thread and the pipe; consume(chunk, n, lead) on the calling thread, false (with `err` set) to stop.
+template <class Consume>
+int pump_reads(const std::vector<std::string>& files, uint32_t k, SolidBuildStats& stats, std::string& err, Consume consume) {
+    constexpr size_t kChunk = (size_t)256 << 20;
+    int rc = SOLID_OK;
+    ChunkPipe pipe(kChunk, k);
+    std::string perr;
+    bool parse_ok = true;
+    double parse_s = 0;
+    std::thread parser([&] {
+        const auto tp = std::chrono::steady_clock::now();
+        for (const auto& f : files) if (!(parse_ok = parse_reads(f, pipe, stats.file_bytes, perr)) || pipe.aborted()) break;
+        pipe.finish();
+        parse_s = secs(tp);
+    });
+    size_t n = 0, lead = 0;
+    while (const char* chunk = pipe.next(n, lead)) {
+        if (rc == SOLID_OK && (rc = consume(chunk, n, lead)) != SOLID_OK) pipe.abort();
+        pipe.release();
+    }
+    parser.join();
+    stats.parse_s = parse_s;
+    stats.seq_bytes = pipe.bytes_out;
+    if (rc == SOLID_OK && !parse_ok) { err = perr; rc = SOLID_E_INPUT; }
+    return rc;
+}
+
+// one chunk into the second consumer
+int sink_chunk(ReadSink& sink, const char* chunk, size_t n, SolidBuildStats& stats, std::string& err) {
+    const auto tc = std::chrono::steady_clock::now();
+    const int rc = sink.add(chunk, n);
+    stats.sink_s += secs(tc);
+    if (rc == HYPO_OK) return SOLID_OK;
+    err = hypo_gpu_last_error();
+    return SOLID_E_SINK;
+}
+
 }  // namespace
 
+int stream_reads(const std::vector<std::string>& files, ReadSink& sink, SolidBuildStats& stats, std::string& err) {
+    const auto t0 = std::chrono::steady_clock::now();
+    stats = SolidBuildStats();
+    if (files.empty()) { err = "no read files"; return SOLID_E_INPUT; }
+    const int rc = pump_reads(files, sink.k, stats, err, [&](const char* chunk, size_t n, size_t) { return sink_chunk(sink, chunk, n, stats, err); });
+    stats.total_s = secs(t0);
+    return rc;
+}
+
 int build_solid_kmers(const std::vector<std::string>& files, uint32_t k, uint32_t coverage, int threads, SolidKmers& sk,
-                      SolidBuildStats& stats, std::string& err) {
+                      SolidBuildStats& stats, std::string& err, ReadSink* sink) {
     (void)threads;                               // one parser thread and the thread that drives the device
     const auto t0 = std::chrono::steady_clock::now();
     stats = SolidBuildStats();
@@ -224,31 +274,15 @@ int build_solid_kmers(const std::vector<std::string>& files, uint32_t k, uint32_
     if (!api.bind()) { err = "the device library does not provide the k-mer counting entry points (hypo_gpu_kmer_*, ABI 9)"; return SOLID_E_DEVICE; }
     if (api.begin(k, coverage) != HYPO_OK) { err = hypo_gpu_last_error(); return SOLID_E_DEVICE; }
     struct End { KmerApi& a; ~End() { (void)a.end(); } } end_table{api};      // the table is freed on every way out
-    constexpr size_t kChunk = (size_t)256 << 20;
-    int rc = SOLID_OK;
-    {
-        ChunkPipe pipe(kChunk, k);
-        std::string perr;
-        bool parse_ok = true;
-        double parse_s = 0;
-        std::thread parser([&] {
-            const auto tp = std::chrono::steady_clock::now();
-            for (const auto& f : files) if (!(parse_ok = parse_reads(f, pipe, stats.file_bytes, perr)) || pipe.aborted()) break;
-            pipe.finish();
-            parse_s = secs(tp);
-        });
-        size_t n = 0;
-        while (const char* chunk = pipe.next(n)) {
-            const auto tc = std::chrono::steady_clock::now();
-            if (rc == SOLID_OK && api.add(chunk, n) != HYPO_OK) { err = hypo_gpu_last_error(); rc = SOLID_E_DEVICE; pipe.abort(); }
-            stats.count_s += secs(tc);
-            pipe.release();
-        }
-        parser.join();
-        stats.parse_s = parse_s;
-        stats.seq_bytes = pipe.bytes_out;
-        if (rc == SOLID_OK && !parse_ok) { err = perr; rc = SOLID_E_INPUT; }
-    }
+    // (the chunks overlap by the longer of the two k-mers less one; the count table gets each from its own k - 1 bytes before the new ones)
+    const int rc = pump_reads(files, sink ? std::max(k, sink->k) : k, stats, err, [&](const char* chunk, size_t n, size_t lead) {
+        const size_t skip = lead > k - 1 ? lead - (k - 1) : 0;
+        const auto tc = std::chrono::steady_clock::now();
+        const int arc = api.add(chunk + skip, n - skip);
+        stats.count_s += secs(tc);
+        if (arc != HYPO_OK) { err = hypo_gpu_last_error(); return (int)SOLID_E_DEVICE; }
+        return sink ? sink_chunk(*sink, chunk, n, stats, err) : (int)SOLID_OK;
+    });
     if (rc != SOLID_OK) return rc;
     auto th = std::chrono::steady_clock::now();
     stats.hist.assign((size_t)4 * coverage + 1, 0);

@@ -29,7 +29,8 @@ const struct option long_options[] = {
     {"device", required_argument, nullptr, 1000}, {"gpus", required_argument, nullptr, 1001},
     {"devices", required_argument, nullptr, 1002}, {"native-klov", no_argument, nullptr, 1003},
     {"ccs-windows", no_argument, nullptr, 1004}, {"host-arms", no_argument, nullptr, 1005}, {"require-device", no_argument, nullptr, 1006},
-    {"vcf", required_argument, nullptr, 1007}, {nullptr, 0, nullptr, 0}};
+    {"vcf", required_argument, nullptr, 1007}, {"qv", required_argument, nullptr, 1008}, {"qv-k", required_argument, nullptr, 1009},
+    {"qv-mem", required_argument, nullptr, 1010}, {nullptr, 0, nullptr, 0}};
 
 // Same layout as the reference's usage() (src/main.cpp:363-430): "Usage: hypo <args>", the mandatory block, the optional
 // block, every flag as "-x, --long <type>" followed by what it does and its default.  The wording is this build's own.
@@ -64,6 +65,9 @@ void usage() {
         {"    --host-arms", "[MI355X build] Cut the short reads into arms on the host (the reference's loops) instead of on the device.", "off"},
         {"    --require-device", "[MI355X build] Exit with an error, instead of an Info line and the host loops, when a stage the device should run (support votes, arm selection) cannot run there (also: HYPO_REQUIRE_DEVICE=1).", "off"},
         {"    --vcf <str>", "[MI355X build] Also write every change the polishing made to the draft as a VCF 4.2 file (REF = draft bases, ALT = polished bases; the alignment of each replaced stretch is computed on the device).", "no VCF"},
+        {"    --qv <str>", "[MI355X build] Also write the reference-free k-mer QV of every draft contig and of its polished text as a tab-separated file: the canonical k-mers of the short reads (-r) are kept as an exact set on the device, and a k-mer of a contig that is not among them counts as an error (Merqury's definition). The reads are parsed once for this and the solid k-mers; a run that starts from stage 1 (-i) parses them for the QV alone.", "no QV"},
+        {"    --qv-k <int>", "[MI355X build] k-mer length of --qv, 12 to 31.", "21"},
+        {"    --qv-mem <GiB>", "[MI355X build] Largest table the k-mer set of --qv may grow to; a read set that needs more ends the run before any contig is polished.", "half of the device's free memory"},
         {"-h, --help", "Print the usage.", nullptr}};
     std::printf("\n Usage: hypo <args>\n\n ** Mandatory args:\n");
     for (const auto& e : mandatory) std::printf("\t%s\n\t%s\n\n", e.flag, e.what);
@@ -78,7 +82,7 @@ void usage() {
 bool file_exists(const std::string& p) { struct stat st; return stat(p.c_str(), &st) == 0; }
 
 // src/main.cpp:490-528: smallest odd k with 4^k >= genome size
-unsigned get_kmer_len(const std::string& given) {
+unsigned get_kmer_len(const std::string& given, uint64_t* size_out = nullptr) {
     size_t ind = 0;
     const float val = std::stof(given, &ind);
     unsigned power = 0;
@@ -90,6 +94,7 @@ unsigned get_kmer_len(const std::string& given) {
             default: std::fprintf(stderr, "[Hypo::Utils] Error: Wrong format for genome-size: Allowed units for Genome-size are K (10^3),M (10^6),G (10^9),T (10^12)!\n"); std::exit(1);
         }
     }
+    if (size_out) *size_out = (uint64_t)std::min(std::ldexp((double)val, (int)power), 9e18);
     unsigned k = (unsigned)((double)power + std::ceil(std::log2(val)));
     k = (unsigned)std::ceil(k / 2);                 // integer division first, as in the reference
     if (k % 2 == 0) ++k;
@@ -142,7 +147,7 @@ int main(int argc, char** argv) {
                 is_sr = true; break;
             }
             case 'd': flags.draft_filename = optarg; need_file("Draft", flags.draft_filename); is_draft = true; break;
-            case 's': given_sz = optarg; flags.k = std::max(2u, get_kmer_len(given_sz)); is_size = true; break;
+            case 's': given_sz = optarg; flags.k = std::max(2u, get_kmer_len(given_sz, &flags.genome_size)); is_size = true; break;
             case 'c': flags.cov = (uint32_t)std::atoi(optarg); if (flags.cov == 0) { std::fprintf(stderr, "[Hypo::] Error: Arg Error: Coverage should be a positive integer %s!\n", optarg); std::exit(1); } is_cov = true; break;
             case 'b': flags.sr_bam_filename = optarg; need_file("Short reads BAM", flags.sr_bam_filename); is_bamsr = true; break;
             case 'B': flags.lr_bam_filename = optarg; need_file("Long reads BAM", flags.lr_bam_filename); break;
@@ -168,6 +173,14 @@ int main(int argc, char** argv) {
             case 1005: flags.host_arms = true; break;
             case 1006: flags.require_device = true; break;
             case 1007: flags.vcf_filename = optarg; break;
+            case 1008: flags.qv_filename = optarg; break;
+            case 1009: {
+                const int v = std::atoi(optarg);
+                if (v < 12 || v > 31) { std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-k must be between 12 and 31 (the k-mer set keeps 2k-bit codes in 64-bit slots) %s!\n", optarg); std::exit(1); }
+                flags.qv_k = (uint32_t)v; break;
+            }
+            case 1010: flags.qv_mem_gib = std::atof(optarg);
+                       if (!(flags.qv_mem_gib > 0)) { std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-mem must be a positive number of GiB %s!\n", optarg); std::exit(1); } break;
             case 1002: {
                 flags.devices.clear();
                 for (const char* c = optarg; *c;) { flags.devices.push_back(std::atoi(c)); while (*c && *c != ',') ++c; if (*c == ',') ++c; }

@@ -1,0 +1,27 @@
+// kset_kernel.hpp — host-visible interface of kset_kernel.hip (internal to libhypo_gpu.so): an exact set of canonical k-mers
+// (k = 12..31) as an open-addressing hash table in HBM, filled from read bytes and queried with contig text (hypo --qv;
+// DESIGN.md "k-mer QV").
+#pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+namespace hypo {
+
+constexpr uint64_t KSET_EMPTY = ~0ull;             // a key has 2k <= 62 bits: all-ones never is one
+// The host keeps count <= KSET_MAX_LOAD * slots between calls (linear probing: ~1.5 probes for a key that is there, ~2.5 for one
+// that is not, at one half).
+constexpr double KSET_MAX_LOAD = 0.5;
+constexpr uint64_t KSET_MIN_SLOTS = 1024;
+
+// Counters of a table (device memory): [0] keys in the table, [1] overflow flag (a lane found no room within `slots` probes).
+// table: `slots` 64-bit words, KSET_EMPTY where free (a fresh table is filled with 0xff bytes).  All pointers are device pointers.
+// every canonical k-mer of bytes[0, n) (the byte rules of kmer_count_run) into the table; ctr[0] += new keys
+hipError_t kset_insert_run(const uint8_t* bytes, uint64_t n, uint32_t k, uint64_t* table, uint64_t slots, unsigned long long* ctr, hipStream_t st);
+// every key of `old_table` into `table` (which must not hold any of them yet); ctr[0] += keys moved
+hipError_t kset_rehash_run(const uint64_t* old_table, uint64_t old_slots, uint64_t* table, uint64_t slots, unsigned long long* ctr, hipStream_t st);
+// n_seqs byte strings back to back in bytes[0, off[n_seqs]) (off[0] = 0): total[s] += length-k windows of sequence s made of
+// ACGTacgt only, missing[s] += those whose canonical k-mer is not in the table.  total / missing must be zeroed by the caller.
+hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table,
+                          uint64_t slots, unsigned long long* total, unsigned long long* missing, hipStream_t st);
+
+}  // namespace hypo

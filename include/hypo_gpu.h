@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define HYPO_GPU_ABI_VERSION 10
+#define HYPO_GPU_ABI_VERSION 11
 #define HYPO_MAX_DEVICES 16      /* contexts one process can hold (an MI355X node has 8 GPUs) */
 
 /* error codes */
@@ -42,7 +42,7 @@ extern "C" {
 #define HYPO_E_HIP          -3   /* a HIP call failed (message in hypo_gpu_last_error) */
 #define HYPO_E_WORKSPACE    -4   /* caller-provided workspace too small */
 #define HYPO_E_NOTINIT      -5
-#define HYPO_E_CAPACITY     -6   /* more than the 32-bit counters of the boundary hold: split the work */
+#define HYPO_E_CAPACITY     -6   /* more than the 32-bit counters of the boundary hold: split the work; the k-mer set reached its cap */
 #define HYPO_E_UNSUPPORTED  -7   /* this build of the library does not provide the entry point (test shims) */
 
 /* per-window status byte written by the POA entry points */
@@ -405,6 +405,27 @@ typedef struct HypoEditBatch {
     const char* b; const uint64_t* b_off;
 } HypoEditBatch;
 int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run_off, uint32_t* runs, uint64_t runs_cap);
+
+/* ABI 11: an exact set of the canonical k-mers of the reads, and how many k-mers of a sequence it lacks (hypo --qv; DESIGN.md
+ * "k-mer QV").  A hash table in device memory on the calling thread's context: presence only, no false positives.
+ *  - hypo_gpu_kset_begin(k, expected_distinct, max_bytes): k in 12..31.  The table is sized for expected_distinct keys at a load
+ *    of one half (at least 1024 slots of 8 bytes) and never grows beyond max_bytes (0: half of the memory the device had free at
+ *    hypo_gpu_init).
+ *  - hypo_gpu_kset_add(bytes, n): inserts min(fwd, rc) (A0 C1 G2 T3, MSB-first) of every k-mer of the bytes; the byte rules and the
+ *    guarantee about splitting the input into calls are those of hypo_gpu_kmer_count_add (overlap the calls by k - 1 bytes; a
+ *    larger overlap changes nothing here).  Synchronous.  Before it touches the table the call makes room for its worst case,
+ *    n - k + 1 new keys, by moving the keys into a larger table; when max_bytes does not allow that it returns HYPO_E_CAPACITY
+ *    (hypo_gpu_last_error names the size reached) and the set is what it was before the call.
+ *  - hypo_gpu_kset_size(n_distinct, table_bytes): keys in the set, bytes of the table (either pointer may be NULL).
+ *  - hypo_gpu_kset_query(bytes, off, n_seqs, total, missing): sequence s is bytes[off[s], off[s + 1]); total[s] = its length-k
+ *    windows made of ACGTacgt only, missing[s] = those, with multiplicity, whose canonical k-mer is not in the set.
+ *  - hypo_gpu_kset_end(): frees the table and the buffers.
+ * add / size / query without begin: HYPO_E_INVALID. */
+int hypo_gpu_kset_begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes);
+int hypo_gpu_kset_add(const char* bytes, uint64_t n);
+int hypo_gpu_kset_size(uint64_t* n_distinct, uint64_t* table_bytes);
+int hypo_gpu_kset_query(const char* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t* total, uint64_t* missing);
+int hypo_gpu_kset_end(void);
 
 /* Kernel timing with HIP events on the stream the kernels run on ----------------------------------
  * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each records
