@@ -30,7 +30,9 @@ EXPORTS = [
     "hypo_gpu_kmer_count_begin", "hypo_gpu_kmer_count_add", "hypo_gpu_kmer_histogram", "hypo_gpu_solid_set_build",
     "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts",
     "hypo_gpu_kset_begin", "hypo_gpu_kset_add", "hypo_gpu_kset_size", "hypo_gpu_kset_query", "hypo_gpu_kset_end",
+    "hypo_gpu_kset_query_spans",
 ]
+KSET_SPAN_PIECE = 2048        # windows per piece of a long span (kset_kernel.hpp)
 
 
 class HypoGpuError(RuntimeError):
@@ -283,6 +285,25 @@ class HypoGpu:
         missing = np.zeros(max(n, 1), dtype=np.uint64)
         self._check(self.lib.hypo_gpu_kset_query(_p(data), _p(off), C.c_uint32(n), _p(total), _p(missing)))
         return total[:n], missing[:n]
+
+    def kset_query_spans_rc(self, data, lo, hi):
+        """(return code, total u64[n], missing u64[n]) of hypo_gpu_kset_query_spans; nothing is checked here"""
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        lo = np.ascontiguousarray(lo, dtype=np.uint64)
+        hi = np.ascontiguousarray(hi, dtype=np.uint64)
+        assert lo.shape == hi.shape and lo.ndim == 1
+        n = lo.size
+        total = np.zeros(max(n, 1), dtype=np.uint64)
+        missing = np.zeros(max(n, 1), dtype=np.uint64)
+        pad = np.concatenate([a, np.zeros(1, np.uint8)])                # (an empty text still has an address)
+        rc = int(self.lib.hypo_gpu_kset_query_spans(_p(pad), C.c_uint64(a.size), _p(lo), _p(hi), C.c_uint32(n), _p(total), _p(missing)))
+        return rc, total[:n], missing[:n]
+
+    def kset_query_spans(self, data, lo, hi):
+        """span s = data[lo[s]:hi[s]].  (total u64[n], missing u64[n]) as kset_query gives them for the spans as sequences"""
+        rc, total, missing = self.kset_query_spans_rc(data, lo, hi)
+        self._check(rc)
+        return total, missing
 
     def kset_end(self):
         self._check(self.lib.hypo_gpu_kset_end())

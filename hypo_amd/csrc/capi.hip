@@ -1232,6 +1232,62 @@ int hypo_gpu_kset_query(const char* bytes, const uint64_t* off, uint32_t n_seqs,
     return HYPO_OK;
 }
 
+int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_t* lo, const uint64_t* hi, uint32_t n_spans, uint64_t* total, uint64_t* missing) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    Ctx::KSet& ks = g_ctx.ks;
+    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    if (!n_spans) return HYPO_OK;
+    if (!lo || !hi || !total || !missing) return fail(HYPO_E_INVALID, "NULL buffer");
+    // a span longer than KSET_SPAN_PIECE windows becomes several items (each carries the k - 1 bytes its last window needs)
+    const uint32_t k = ks.k;
+    uint64_t n_items = 0;
+    for (uint32_t s = 0; s < n_spans; ++s) {
+        if (lo[s] > hi[s] || hi[s] > n_bytes) return fail(HYPO_E_INVALID, "span %u = [%llu, %llu) of %llu bytes", s, (unsigned long long)lo[s], (unsigned long long)hi[s], (unsigned long long)n_bytes);
+        const uint64_t len = hi[s] - lo[s];
+        if (len >= k) n_items += (len - k + 1 + hypo::KSET_SPAN_PIECE - 1) / hypo::KSET_SPAN_PIECE;
+    }
+    for (uint32_t s = 0; s < n_spans; ++s) total[s] = missing[s] = 0;
+    if (!n_items) return HYPO_OK;
+    if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
+    if (n_items >= (1ull << 31)) return fail(HYPO_E_CAPACITY, "%llu pieces of spans in one call: split the call", (unsigned long long)n_items);
+    std::vector<uint64_t> item_lo((size_t)n_items);
+    std::vector<uint32_t> item_len((size_t)n_items);
+    size_t it = 0;
+    for (uint32_t s = 0; s < n_spans; ++s) {
+        const uint64_t len = hi[s] - lo[s];
+        if (len < k) continue;
+        const uint64_t n_win = len - k + 1;
+        for (uint64_t w = 0; w < n_win; w += hypo::KSET_SPAN_PIECE, ++it) {
+            item_lo[it] = lo[s] + w;
+            item_len[it] = (uint32_t)(n_win - w < hypo::KSET_SPAN_PIECE ? n_win - w : hypo::KSET_SPAN_PIECE) + k - 1;
+        }
+    }
+    int group = hypo::KSET_SPAN_GROUP;
+    if (const char* g = getenv("HYPO_KSET_SPAN_GROUP")) group = atoi(g) == 64 ? 64 : atoi(g) == 32 ? 32 : group;   // (profiles/guard_rate.py)
+    hipStream_t st = g_ctx.stream;
+    const size_t lo_bytes = ((size_t)n_items * 8 + 255) & ~(size_t)255;
+    HIP_TRY(ks.in.alloc(n_bytes));
+    HIP_TRY(ks.off.alloc(lo_bytes + (size_t)n_items * 4));
+    HIP_TRY(ks.res.alloc((size_t)n_items * 8));
+    HIP_TRY(h2d(ks.in.p, bytes, n_bytes, st));
+    HIP_TRY(h2d(ks.off.p, item_lo.data(), (size_t)n_items * 8, st));
+    HIP_TRY(h2d((char*)ks.off.p + lo_bytes, item_len.data(), (size_t)n_items * 4, st));
+    HIP_TRY(hypo::kset_spans_run((const uint8_t*)ks.in.p, (const uint64_t*)ks.off.p, (const uint32_t*)((const char*)ks.off.p + lo_bytes), (uint32_t)n_items, k,
+                                 ks.table, ks.slots, (uint2*)ks.res.p, group, st));
+    std::vector<uint2> res((size_t)n_items);
+    HIP_TRY(d2h(res.data(), ks.res.p, (size_t)n_items * 8, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    it = 0;
+    for (uint32_t s = 0; s < n_spans; ++s) {
+        const uint64_t len = hi[s] - lo[s];
+        if (len < k) continue;
+        for (uint64_t w = 0; w < len - k + 1; w += hypo::KSET_SPAN_PIECE, ++it) { total[s] += res[it].x; missing[s] += res[it].y; }
+    }
+    return HYPO_OK;
+}
+
 int hypo_gpu_kset_end(void) {
     HYPO_LOCKED();
     HYPO_ON_DEVICE();

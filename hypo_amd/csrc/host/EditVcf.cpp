@@ -52,22 +52,24 @@ int edit_scripts_for(EditScriptsFn fn, const std::vector<std::unique_ptr<Contig>
     return rc;
 }
 
-void vcf_header(std::ostream& os, const std::string& reference, const std::vector<std::unique_ptr<Contig>>& contigs) {
+void vcf_header(std::ostream& os, const std::string& reference, const std::vector<std::unique_ptr<Contig>>& contigs, bool kmer_filter) {
     os << "##fileformat=VCFv4.2\n##source=hypo\n##reference=" << reference << "\n";
     for (const auto& c : contigs) os << "##contig=<ID=" << c->get_name() << ",length=" << c->get_len() << ">\n";
     os << "##ALT=<ID=DEL,Description=\"Deletion\">\n"
           "##INFO=<ID=SVTYPE,Number=1,Type=String,Description=\"Type of structural variant\">\n"
-          "##INFO=<ID=END,Number=1,Type=Integer,Description=\"End position of the variant\">\n"
-          "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
+          "##INFO=<ID=END,Number=1,Type=Integer,Description=\"End position of the variant\">\n";
+    if (kmer_filter) os << "##FILTER=<ID=kmer,Description=\"rejected: adds k-mers that no read contains\">\n";
+    os << "#CHROM\tPOS\tID\tREF\tALT\tQUAL\tFILTER\tINFO\n";
 }
 
 // Column stream of the contig: draft text between units is '=' columns, each unit its script.  A record is a maximal run of
 // non-'=' columns; an empty REF or ALT takes the draft base before the run (after it, at position 0) on both sides; a record at 0
 // padded with the base after it and the next record padded with that same base become one record.
-void vcf_records(std::ostream& os, const Contig& ctg, const EditBatchResult& eb, size_t ci, VcfStats& st) {
+void vcf_make_records(const Contig& ctg, const EditBatchResult& eb, size_t ci, VcfStats& st, VcfContigRecords& out) {
     const std::vector<EditUnit>& units = eb.units[ci];
     const uint64_t len = ctg.get_len();
-    struct Rec { uint64_t rb = 0, re = 0; std::string alt; };
+    using Rec = VcfRec;
+    out.recs.clear(); out.whole_del = false;
     std::vector<Rec> raw;
     Rec cur; bool open = false;
     auto close = [&] { if (open) { raw.push_back(std::move(cur)); cur = Rec(); open = false; } };
@@ -94,13 +96,12 @@ void vcf_records(std::ostream& os, const Contig& ctg, const EditBatchResult& eb,
         }
     }
     close();
-    const std::string& name = ctg.get_name();
     if (len > 0 && out_len == 0) {
-        os << name << "\t1\t.\t" << ctg.draft_base(0) << "\t<DEL>\t.\tPASS\tSVTYPE=DEL;END=" << len << "\n";
+        out.whole_del = true;
         ++st.records;
         return;
     }
-    std::vector<Rec> recs;
+    std::vector<Rec>& recs = out.recs;
     for (Rec& r : raw) {
         if (r.rb == r.re || r.alt.empty()) {
             if (r.rb > 0) { --r.rb; r.alt.insert(r.alt.begin(), ctg.draft_base(r.rb)); }
@@ -114,15 +115,30 @@ void vcf_records(std::ostream& os, const Contig& ctg, const EditBatchResult& eb,
         }
         recs.push_back(std::move(r));
     }
+    st.records += recs.size();
+}
+
+void vcf_write_records(std::ostream& os, const Contig& ctg, const VcfContigRecords& rs, const std::vector<uint8_t>* rejected) {
+    const std::string& name = ctg.get_name();
+    if (rs.whole_del) {
+        os << name << "\t1\t.\t" << ctg.draft_base(0) << "\t<DEL>\t.\tPASS\tSVTYPE=DEL;END=" << ctg.get_len() << "\n";
+        return;
+    }
     std::string line;
-    for (const Rec& r : recs) {
+    for (size_t i = 0; i < rs.recs.size(); ++i) {
+        const VcfRec& r = rs.recs[i];
         line.clear();
         line += name; line += '\t'; line += std::to_string(r.rb + 1); line += "\t.\t";
         line += ctg.draft_segment((uint32_t)r.rb, (uint32_t)r.re);
-        line += '\t'; line += r.alt; line += "\t.\tPASS\t.\n";
+        line += '\t'; line += r.alt; line += rejected && (*rejected)[i] ? "\t.\tkmer\t.\n" : "\t.\tPASS\t.\n";
         os << line;
     }
-    st.records += recs.size();
+}
+
+void vcf_records(std::ostream& os, const Contig& ctg, const EditBatchResult& eb, size_t ci, VcfStats& st) {
+    VcfContigRecords rs;
+    vcf_make_records(ctg, eb, ci, st, rs);
+    vcf_write_records(os, ctg, rs, nullptr);
 }
 
 }  // namespace hypo

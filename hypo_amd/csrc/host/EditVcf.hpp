@@ -25,8 +25,16 @@ struct EditBatchResult {
 int edit_scripts_for(EditScriptsFn fn, const std::vector<std::unique_ptr<Contig>>& contigs, uint32_t c0, uint32_t c1, EditBatchResult& out);
 
 struct VcfStats { uint64_t records = 0, sub = 0, ins = 0, del = 0; };
-void vcf_header(std::ostream& os, const std::string& reference, const std::vector<std::unique_ptr<Contig>>& contigs);
+// kmer_filter: the header also declares FILTER kmer (hypo --kmer-guard)
+void vcf_header(std::ostream& os, const std::string& reference, const std::vector<std::unique_ptr<Contig>>& contigs, bool kmer_filter = false);
+// One record: REF = draft [rb, re), ALT = alt.  whole_del: the contig is written as nothing, its only record is the <DEL> one.
+struct VcfRec { uint64_t rb = 0, re = 0; std::string alt; };
+struct VcfContigRecords { std::vector<VcfRec> recs; bool whole_del = false; };
 // the records of one contig (before Contig::release_after_output); ci = the contig's index in the batch
+void vcf_make_records(const Contig& ctg, const EditBatchResult& eb, size_t ci, VcfStats& st, VcfContigRecords& out);
+// their lines; rejected (per record, may be NULL): FILTER kmer instead of PASS
+void vcf_write_records(std::ostream& os, const Contig& ctg, const VcfContigRecords& rs, const std::vector<uint8_t>* rejected);
+// both steps
 void vcf_records(std::ostream& os, const Contig& ctg, const EditBatchResult& eb, size_t ci, VcfStats& st);
 
 }  // namespace hypo

@@ -3,6 +3,7 @@
 #include "DeviceArms.hpp"
 #include "SolidBuild.hpp"
 #include "EditVcf.hpp"
+#include "KmerGuard.hpp"
 #include "QvReport.hpp"
 #include <ctime>
 #include <omp.h>
@@ -42,6 +43,21 @@ void Hypo::stop(const char* label) {
 }
 
 void Hypo::polish() {
+    // --kmer-guard: the k-mer set of --qv (with or without its table), the spans query against it, and the edit scripts whether
+    // or not a VCF is written.  Checked first, so that its error names everything the guard lacks.
+    const bool guard_on = _cFlags.kmer_guard;
+    KmerGuard guard;
+    EditScriptsFn guard_edit_fn = nullptr;
+    if (guard_on) {
+        guard.set_k(_cFlags.qv_k);
+        const bool have_spans = guard.bind(), have_set = QvReport().bind();
+        guard_edit_fn = bind_edit_scripts();
+        if (!have_spans || !have_set || !guard_edit_fn) {
+            std::fprintf(stderr, "[Hypo::Hypo] Error: --kmer-guard needs%s%s%s, which the device library does not provide\n", have_spans ? "" : " hypo_gpu_kset_query_spans",
+                         have_set ? "" : " hypo_gpu_kset_begin / _add / _size / _end", guard_edit_fn ? "" : " hypo_gpu_edit_scripts");
+            std::exit(1);
+        }
+    }
     // --vcf: the device library must provide the edit scripts (C-ABI 10); bound by name, and only here, so that libraries without
     // the entry point still serve every run without --vcf
     EditScriptsFn edit_fn = nullptr;
@@ -56,13 +72,15 @@ void Hypo::polish() {
         std::fprintf(stderr, "[Hypo::Hypo] Error: --qv needs hypo_gpu_kset_begin / _add / _size / _query / _end (C-ABI 11), which the device library does not provide\n");
         std::exit(1);
     }
+    const bool set_on = qv_on || guard_on;
+    if (guard_on && !qv_on) (void)qv.bind();             // (the guard's check above found the entry points)
     auto qv_fail = [&](const char* what) {
         std::fprintf(stderr, "[Hypo::QV] Error: %s: %s\n", what, hypo_gpu_last_error());
         qv.end();
         std::exit(1);
     };
     ReadSink qv_sink;
-    if (qv_on) {
+    if (set_on) {
         // (sized for one k-mer per genome position; what the read errors add makes it grow)
         const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
         if (qv.begin(_cFlags.qv_k, _cFlags.genome_size, cap, 0) != HYPO_OK) qv_fail("the k-mer set could not be created");
@@ -84,7 +102,7 @@ void Hypo::polish() {
     if (_cFlags.done_stage < 1) {
         SolidBuildStats st;
         std::string err;
-        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err, qv_on ? &qv_sink : nullptr);
+        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err, set_on ? &qv_sink : nullptr);
         if (rc == SOLID_E_SINK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); qv.end(); std::exit(1); }
         if (rc == SOLID_E_UNDEFINED) {                   // the reference's own line for a failed initialise (src/Hypo.cpp:53)
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: %s\n", err.c_str());
@@ -97,7 +115,7 @@ void Hypo::polish() {
         }
         std::fprintf(stderr, "[Hypo::SolidKmers] Info: device construction: %.3f s (parse %.3f s of %.3f GB, count %.3f s of %.3f GB sent, "
                              "histogram %.3f s, set %.3f s)\n", st.total_s, st.parse_s, st.file_bytes / 1e9, st.count_s, st.seq_bytes / 1e9, st.hist_s, st.fill_s);
-        if (qv_on) qv_reads_done(st, true);
+        if (set_on) qv_reads_done(st, true);
         if (_cFlags.intermed) {
             if (!sk.store(HYPO_SKFILE)) {
                 std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Saving: Could not store the DS for Solid kmers!\n");
@@ -116,7 +134,7 @@ void Hypo::polish() {
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Loading: Could not load the DS for Solid kmers (%s)!\n", HYPO_SKFILE);
             std::exit(1);
         }
-        if (qv_on) {                                     // the stored set needs no reads; the QV does
+        if (set_on) {                                    // the stored set needs no reads; the QV and the guard do
             SolidBuildStats st;
             std::string err;
             const int rc = stream_reads(_cFlags.sr_filenames, qv_sink, st, err);
@@ -229,7 +247,7 @@ void Hypo::polish() {
             std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: VCF File (%s) could not be opened!\n", pending_vcf_tmp.c_str());
             std::exit(1);
         }
-        vcf_header(vfile, _cFlags.draft_filename, _contigs);
+        vcf_header(vfile, _cFlags.draft_filename, _contigs, guard_on);
     }
     std::thread writer;
     for (uint32_t batch_id = 0; batch_id < num_batches; ++batch_id) {
@@ -627,12 +645,12 @@ void Hypo::polish() {
         // next batch's stages on this thread) and formats each contig's records next to its FASTA record, before the contig's
         // windows go
         if (writer.joinable()) writer.join();
-        writer = std::thread([this, &ofile, &vfile, &vstats, &qv, qv_on, edit_fn, initial_cid, final_cid] {
+        writer = std::thread([this, &ofile, &vfile, &vstats, &qv, &guard, qv_on, guard_on, edit_fn, guard_edit_fn, initial_cid, final_cid] {
             omp_set_num_threads(std::max(1, std::min((int)_cFlags.threads, 8)));
             std::unique_ptr<EditBatchResult> edits;
-            if (edit_fn) {
+            if (edit_fn || guard_on) {
                 edits.reset(new EditBatchResult());
-                if (hypo_gpu_use_device(0) != HYPO_OK || edit_scripts_for(edit_fn, _contigs, initial_cid, final_cid, *edits) != HYPO_OK) {
+                if (hypo_gpu_use_device(0) != HYPO_OK || edit_scripts_for(guard_on ? guard_edit_fn : edit_fn, _contigs, initial_cid, final_cid, *edits) != HYPO_OK) {
                     // (the main thread may be inside a device call: leave without running the static destructors under it)
                     std::fprintf(stderr, "[Hypo::Hypo] Error: edit scripts: %s\n", hypo_gpu_last_error());
                     std::fflush(nullptr);
@@ -642,6 +660,26 @@ void Hypo::polish() {
             }
             // --qv: the draft and the polished text of every contig of the batch go to the k-mer set in one query on context 0
             int qrc = qv_on ? hypo_gpu_use_device(0) : HYPO_OK;
+            // --kmer-guard: the batch's records are made first, their clusters judged by the set, and every contig is written as
+            // its draft with the accepted records applied
+            if (guard_on) {
+                VcfStats unused;
+                const int grc = guard.run_batch(_contigs, initial_cid, final_cid, *edits, edit_fn ? vstats : unused,
+                    [&](uint32_t c, const std::string& draft, const std::string& text, const VcfContigRecords& recs, const std::vector<uint8_t>& rejected) {
+                        ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;
+                        if (edit_fn) vcf_write_records(vfile, *_contigs[c], recs, &rejected);
+                        _contigs[c]->release_after_output();
+                        return qv_on ? qv.push(c, draft, text) : HYPO_OK;
+                    });
+                if (grc == HYPO_OK && qv_on) qrc = qv.flush();
+                if (grc != HYPO_OK || qrc != HYPO_OK) {
+                    std::fprintf(stderr, "[Hypo::Hypo] Error: k-mer %s: %s\n", grc != HYPO_OK ? "guard" : "set query", hypo_gpu_last_error());
+                    std::fflush(nullptr);
+                    remove_pending_output();
+                    std::_Exit(1);
+                }
+                return;
+            }
             for (uint32_t c = initial_cid; c < final_cid; ++c) {
                 if (qv_on) {
                     const std::string text = _contigs[c]->polished_text();
@@ -675,8 +713,8 @@ void Hypo::polish() {
         if (!vfile) { std::fprintf(stderr, "[Hypo::Hypo] Error: writing the VCF file (%s) failed!\n", pending_vcf_tmp.c_str()); std::exit(1); }
     }
     // --qv: the table is formatted once, closed and checked like the others; the set has answered its last query
+    if (set_on) qv.end();
     if (qv_on) {
-        qv.end();
         pending_qv_tmp = _cFlags.qv_filename + ".tmp";
         std::ofstream qfile(pending_qv_tmp);
         if (!qfile.is_open()) { std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: QV File (%s) could not be opened!\n", pending_qv_tmp.c_str()); std::exit(1); }
@@ -691,6 +729,10 @@ void Hypo::polish() {
         std::exit(1);
     }
     pending_tmp.clear();
+    if (guard_on)
+        std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer guard (k = %u): %llu clusters of %llu records, %llu clusters (%llu records) rejected\n", guard.k(),
+                     (unsigned long long)guard.stats().clusters, (unsigned long long)guard.stats().records, (unsigned long long)guard.stats().rejected_clusters,
+                     (unsigned long long)guard.stats().rejected_records);
     if (edit_fn) {
         if (std::rename(pending_vcf_tmp.c_str(), _cFlags.vcf_filename.c_str()) != 0) {
             std::fprintf(stderr, "[Hypo::Hypo] Error: could not move %s to %s!\n", pending_vcf_tmp.c_str(), _cFlags.vcf_filename.c_str());

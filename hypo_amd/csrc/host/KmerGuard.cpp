@@ -1,0 +1,98 @@
+// KmerGuard.cpp — see KmerGuard.hpp.
+#include "KmerGuard.hpp"
+#include <dlfcn.h>
+#include <algorithm>
+
+namespace hypo {
+
+bool KmerGuard::bind() {
+    _spans = (decltype(_spans))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_query_spans");
+    return _spans != nullptr;
+}
+
+void KmerGuard::clusters_of(const std::vector<VcfRec>& recs, uint32_t k, std::vector<Cluster>& out) {
+    out.clear();
+    int64_t shift = 0;                                       // polished position - draft position before the record in hand
+    for (size_t i = 0; i < recs.size(); ++i) {
+        const VcfRec& r = recs[i];
+        const int64_t delta = (int64_t)r.alt.size() - (int64_t)(r.re - r.rb);
+        if (out.empty() || r.rb - out.back().e >= (uint64_t)(k - 1)) {
+            Cluster c;
+            c.r0 = i; c.b = r.rb; c.qb = (uint64_t)((int64_t)r.rb + shift);
+            out.push_back(c);
+        }
+        shift += delta;
+        Cluster& c = out.back();
+        c.r1 = i + 1; c.e = r.re; c.qe = (uint64_t)((int64_t)r.re + shift);
+    }
+}
+
+std::string KmerGuard::apply(const std::string& draft, const std::vector<VcfRec>& recs, const std::vector<uint8_t>& rejected) {
+    std::string out;
+    out.reserve(draft.size() + draft.size() / 64);
+    uint64_t at = 0;
+    for (size_t i = 0; i < recs.size(); ++i) {
+        if (rejected[i]) continue;
+        out.append(draft, at, recs[i].rb - at);
+        out += recs[i].alt;
+        at = recs[i].re;
+    }
+    out.append(draft, at, std::string::npos);
+    return out;
+}
+
+int KmerGuard::run_batch(const std::vector<std::unique_ptr<Contig>>& contigs, uint32_t c0, uint32_t c1, const EditBatchResult& eb, VcfStats& vst, const Emit& emit) {
+    constexpr size_t kFlushAt = (size_t)512 << 20;
+    for (uint32_t c = c0; c < c1; ++c) {
+        const Contig& ctg = *contigs[c];
+        Pending p;
+        p.contig = c;
+        vcf_make_records(ctg, eb, c - c0, vst, p.recs);
+        clusters_of(p.recs.recs, _k, p.clusters);            // (none for a contig written as nothing: its <DEL> record is not guarded)
+        std::string d = ctg.draft_segment(0, (uint32_t)ctg.get_len()), q = ctg.polished_text();
+        if (!_pending.empty() && (_text.size() + d.size() + q.size() > kFlushAt || _lo.size() + 2 * p.clusters.size() >= (1ull << 32))) {
+            const int rc = flush(emit);
+            if (rc != HYPO_OK) return rc;
+        }
+        p.d_off = _text.size(); p.d_len = d.size(); _text += d;
+        p.p_off = _text.size(); p.p_len = q.size(); _text += q;
+        p.span0 = _lo.size();
+        const uint64_t flank = _k - 1;
+        for (const Cluster& cl : p.clusters) {
+            _lo.push_back(p.d_off + (cl.b > flank ? cl.b - flank : 0)); _hi.push_back(p.d_off + std::min<uint64_t>(p.d_len, cl.e + flank));
+            _lo.push_back(p.p_off + (cl.qb > flank ? cl.qb - flank : 0)); _hi.push_back(p.p_off + std::min<uint64_t>(p.p_len, cl.qe + flank));
+        }
+        _pending.push_back(std::move(p));
+    }
+    return flush(emit);
+}
+
+int KmerGuard::flush(const Emit& emit) {
+    if (_pending.empty()) return HYPO_OK;
+    std::vector<uint64_t> total(_lo.size() ? _lo.size() : 1), missing(total.size());
+    if (!_lo.empty()) {
+        const int rc = _spans(_text.data(), _text.size(), _lo.data(), _hi.data(), (uint32_t)_lo.size(), total.data(), missing.data());
+        if (rc != HYPO_OK) return rc;
+    }
+    std::vector<uint8_t> rejected;
+    for (const Pending& p : _pending) {
+        rejected.assign(p.recs.recs.size(), 0);
+        bool any = false;
+        for (size_t i = 0; i < p.clusters.size(); ++i) {
+            const Cluster& cl = p.clusters[i];
+            const uint64_t r_c = missing[p.span0 + 2 * i], a_c = missing[p.span0 + 2 * i + 1];
+            ++_stats.clusters; _stats.records += cl.r1 - cl.r0;
+            if (a_c <= r_c) continue;                            // (a tie: the polish is trusted)
+            ++_stats.rejected_clusters; _stats.rejected_records += cl.r1 - cl.r0;
+            std::fill(rejected.begin() + (ptrdiff_t)cl.r0, rejected.begin() + (ptrdiff_t)cl.r1, (uint8_t)1);
+            any = true;
+        }
+        const std::string draft = _text.substr(p.d_off, p.d_len);
+        const int rc = emit(p.contig, draft, any ? apply(draft, p.recs.recs, rejected) : _text.substr(p.p_off, p.p_len), p.recs, rejected);
+        if (rc != HYPO_OK) return rc;
+    }
+    _pending.clear(); _lo.clear(); _hi.clear(); _text.clear();
+    return HYPO_OK;
+}
+
+}  // namespace hypo

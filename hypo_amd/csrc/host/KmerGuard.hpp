@@ -1,0 +1,51 @@
+// KmerGuard.hpp — hypo --kmer-guard: only the edits the k-mers of the short reads support reach the output (DESIGN.md "k-mer
+// guard").  The VCF records of a contig (EditVcf) that lie closer than k - 1 unchanged draft bases form a cluster; no length-k window
+// touches the edits of two clusters, so each is judged alone: its draft text and its polished text, each with the k - 1 bases on
+// either side, are two spans of one hypo_gpu_kset_query_spans call on context 0 (kset_kernel.hip), and a cluster whose polished span
+// lacks more k-mers of the reads' set (QvReport holds it) than its draft span is rejected with all its records.  The FASTA record is
+// the draft with the accepted records applied.
+#pragma once
+#include <cstdint>
+#include <functional>
+#include <memory>
+#include <string>
+#include <vector>
+#include "Contig.hpp"
+#include "EditVcf.hpp"
+
+namespace hypo {
+
+class KmerGuard {
+public:
+    struct Stats { uint64_t clusters = 0, records = 0, rejected_clusters = 0, rejected_records = 0; };
+    // One contig's clusters: records [first[c], first[c + 1]) of the contig form cluster c; its draft span [b, e) and polished span
+    // [qb, qe) without the flanks.
+    struct Cluster { size_t r0 = 0, r1 = 0; uint64_t b = 0, e = 0, qb = 0, qe = 0; };
+    // what a contig's turn hands to the writer: the draft, the guarded text, the records and which of them were rejected
+    using Emit = std::function<int(uint32_t contig, const std::string& draft, const std::string& text, const VcfContigRecords& recs, const std::vector<uint8_t>& rejected)>;
+
+    // binds hypo_gpu_kset_query_spans by name (false: the device library does not provide it)
+    bool bind();
+    void set_k(uint32_t k) { _k = k; }
+    // the clusters of one contig's records (the rule above); polished spans follow from the records' length changes
+    static void clusters_of(const std::vector<VcfRec>& recs, uint32_t k, std::vector<Cluster>& out);
+    // the draft with the records that are not rejected applied
+    static std::string apply(const std::string& draft, const std::vector<VcfRec>& recs, const std::vector<uint8_t>& rejected);
+    // Contigs [c0, c1) of a batch whose edit scripts are in `eb`: records, clusters, the spans calls on the calling thread's context
+    // (at most 512 MiB of text a call, as QvReport; a larger contig gets a call of its own), decisions, and `emit` for every contig
+    // in order.  HYPO_OK, the C-ABI's error, or what emit answered.
+    int run_batch(const std::vector<std::unique_ptr<Contig>>& contigs, uint32_t c0, uint32_t c1, const EditBatchResult& eb, VcfStats& vst, const Emit& emit);
+    const Stats& stats() const { return _stats; }
+    uint32_t k() const { return _k; }
+private:
+    struct Pending { uint32_t contig = 0; uint64_t d_off = 0, d_len = 0, p_off = 0, p_len = 0; VcfContigRecords recs; std::vector<Cluster> clusters; size_t span0 = 0; };
+    int flush(const Emit& emit);
+    int (*_spans)(const char*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint64_t*, uint64_t*) = nullptr;
+    uint32_t _k = 21;
+    Stats _stats;
+    std::string _text;                                       // D and P of the pending contigs, back to back
+    std::vector<uint64_t> _lo, _hi;                          // two spans per cluster: draft, polished
+    std::vector<Pending> _pending;
+};
+
+}  // namespace hypo

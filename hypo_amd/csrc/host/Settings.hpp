@@ -28,6 +28,7 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     std::string qv_filename;               // new, opt-in: --qv <file> (k-mer QV of every draft and polished contig against the reads' k-mers)
     uint32_t qv_k = 21;                    // new, opt-in: --qv-k (12..31)
     double qv_mem_gib = 0;                 // new, opt-in: --qv-mem (cap of the k-mer set; 0 = half of the device's free memory)
+    bool kmer_guard = false;               // new, opt-in: --kmer-guard (edits whose k-mers the reads do not support are left out)
     uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
 };
 

@@ -30,7 +30,7 @@ const struct option long_options[] = {
     {"devices", required_argument, nullptr, 1002}, {"native-klov", no_argument, nullptr, 1003},
     {"ccs-windows", no_argument, nullptr, 1004}, {"host-arms", no_argument, nullptr, 1005}, {"require-device", no_argument, nullptr, 1006},
     {"vcf", required_argument, nullptr, 1007}, {"qv", required_argument, nullptr, 1008}, {"qv-k", required_argument, nullptr, 1009},
-    {"qv-mem", required_argument, nullptr, 1010}, {nullptr, 0, nullptr, 0}};
+    {"qv-mem", required_argument, nullptr, 1010}, {"kmer-guard", no_argument, nullptr, 1011}, {nullptr, 0, nullptr, 0}};
 
 // Same layout as the reference's usage() (src/main.cpp:363-430): "Usage: hypo <args>", the mandatory block, the optional
 // block, every flag as "-x, --long <type>" followed by what it does and its default.  The wording is this build's own.
@@ -68,6 +68,7 @@ void usage() {
         {"    --qv <str>", "[MI355X build] Also write the reference-free k-mer QV of every draft contig and of its polished text as a tab-separated file: the canonical k-mers of the short reads (-r) are kept as an exact set on the device, and a k-mer of a contig that is not among them counts as an error (Merqury's definition). The reads are parsed once for this and the solid k-mers; a run that starts from stage 1 (-i) parses them for the QV alone.", "no QV"},
         {"    --qv-k <int>", "[MI355X build] k-mer length of --qv, 12 to 31.", "21"},
         {"    --qv-mem <GiB>", "[MI355X build] Largest table the k-mer set of --qv may grow to; a read set that needs more ends the run before any contig is polished.", "half of the device's free memory"},
+        {"    --kmer-guard", "[MI355X build] Keep only the edits the k-mers of the short reads support: edits closer than k - 1 draft bases form a cluster, and a cluster that puts more k-mers no read contains into the contig than it removes is left out of the output (its VCF records get FILTER kmer instead of PASS; the polished columns of --qv describe the guarded text). Uses the k-mer set of --qv (--qv-k, --qv-mem) with or without --qv and --vcf.", "off"},
         {"-h, --help", "Print the usage.", nullptr}};
     std::printf("\n Usage: hypo <args>\n\n ** Mandatory args:\n");
     for (const auto& e : mandatory) std::printf("\t%s\n\t%s\n\n", e.flag, e.what);
@@ -181,6 +182,7 @@ int main(int argc, char** argv) {
             }
             case 1010: flags.qv_mem_gib = std::atof(optarg);
                        if (!(flags.qv_mem_gib > 0)) { std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-mem must be a positive number of GiB %s!\n", optarg); std::exit(1); } break;
+            case 1011: flags.kmer_guard = true; break;
             case 1002: {
                 flags.devices.clear();
                 for (const char* c = optarg; *c;) { flags.devices.push_back(std::atoi(c)); while (*c && *c != ',') ++c; if (*c == ',') ++c; }

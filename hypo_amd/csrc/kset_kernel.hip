@@ -168,6 +168,86 @@ __global__ void __launch_bounds__(KS_THREADS) kset_query_kernel(const uint8_t* _
     if (!same && tot) { atomicAdd(total + seq, tot); if (mis) atomicAdd(missing + seq, mis); }
 }
 
+// ---- many short spans (hypo --kmer-guard; DESIGN.md "k-mer guard") -------------------------------------------------------------------
+// A group of G lanes (a half-wave or a wave) owns one item, a piece of a span with at most KSET_SPAN_PIECE windows (the host cuts
+// longer spans, so one long span among short ones is spread over many groups).  The group walks its item in passes of G windows.
+// In a pass every lane loads ONE byte, the next G bytes of the item, and three ballots turn the group's bytes into bit masks: the
+// low bit of the base code, its high bit, and "not a base".  The masks of the pass before are carried (a window needs k - 1 <= G
+// bytes beyond its first), so every byte is loaded once.  Lane l's window is bits [l, l + k) of the two masks in hand: the forward
+// code is their bit-reversed interleave (MSB-first), the reverse complement the interleave of their complements.  No LDS, no
+// per-lane loop over bytes.  Hits and misses are counted with two more ballots, so the sums are wave-uniform and the group's first
+// lane stores them; no atomics, and the output is a pure function of the input.
+// Bounds: a lane reads bytes[lo + x] for x < len only (lo + len <= n is checked by the caller); items and out are indexed below
+// n_items; the probe is ks_contains (slot indices < slots, at most `slots` steps).
+__device__ __forceinline__ uint64_t ks_spread(uint64_t x) {     // bit j of the low 32 bits to bit 2j
+    x &= 0xffffffffull;
+    x = (x | (x << 16)) & 0x0000ffff0000ffffull;
+    x = (x | (x << 8)) & 0x00ff00ff00ff00ffull;
+    x = (x | (x << 4)) & 0x0f0f0f0f0f0f0f0full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+    return x;
+}
+
+template <int G> __device__ __forceinline__ uint64_t ks_group_part(uint64_t wave_mask, uint32_t half) {
+    return G == 64 ? wave_mask : (wave_mask >> (32 * half)) & 0xffffffffull;
+}
+// bits [l, l + 32) of the 2G bits (hi : lo)
+template <int G> __device__ __forceinline__ uint32_t ks_window_bits(uint64_t lo, uint64_t hi, uint32_t l) {
+    if (G == 32) return (uint32_t)(((hi << 32) | lo) >> l);
+    return (uint32_t)(l ? (lo >> l) | (hi << (64 - l)) : lo);
+}
+
+template <int G>
+__global__ void __launch_bounds__(KS_THREADS) kset_spans_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ item_lo,
+                                                                 const uint32_t* __restrict__ item_len, uint32_t n_items, uint32_t k,
+                                                                 const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out) {
+    static_assert(G == 32 || G == 64, "a half-wave or a wave");
+    const uint32_t lane = threadIdx.x & 63, l = lane & (G - 1), half = G == 64 ? 0 : lane >> 5;
+    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
+    const bool have = item < n_items;
+    const uint64_t lo = have ? item_lo[item] : 0;
+    const uint32_t len = have ? item_len[item] : 0;
+    const uint32_t n_win = len >= k ? len - k + 1 : 0;
+    const uint32_t kmask = (uint32_t)((1ull << k) - 1);
+    auto load_masks = [&](uint32_t at, uint64_t& b0, uint64_t& b1, uint64_t& bad) {   // bytes [at, at + G) of the item (wave-uniform call)
+        const uint32_t x = at + l;
+        const uint32_t c = x < len ? ks_base_code(bytes[lo + x]) : 4u;
+        b0 = ks_group_part<G>(__ballot(c & 1u), half);
+        b1 = ks_group_part<G>(__ballot(c & 2u), half);
+        bad = ks_group_part<G>(__ballot(c > 3u), half);
+    };
+    uint64_t c0, c1, cb, n0, n1, nb;                           // the masks of the pass's G bytes, and of the G bytes after them
+    load_masks(0, c0, c1, cb);
+    uint32_t tot = 0, mis = 0;
+    for (uint32_t base = 0; __any(base < n_win); base += G) {   // (both halves of a wave stay in the loop until the longer item is done)
+        load_masks(base + G, n0, n1, nb);
+        const bool in = base + l < n_win;
+        const bool ok = in && (ks_window_bits<G>(cb, nb, l) & kmask) == 0;
+        bool miss = false;
+        if (ok) {
+            const uint32_t h0 = ks_window_bits<G>(c0, n0, l) & kmask, h1 = ks_window_bits<G>(c1, n1, l) & kmask;
+            const uint64_t fwd = (ks_spread(__brev(h1) >> (32 - k)) << 1) | ks_spread(__brev(h0) >> (32 - k));
+            const uint64_t rc = (ks_spread(~h1 & kmask) << 1) | ks_spread(~h0 & kmask);
+            miss = !ks_contains(table, slots, fwd < rc ? fwd : rc);
+        }
+        tot += (uint32_t)__popcll(ks_group_part<G>(__ballot(ok), half));
+        mis += (uint32_t)__popcll(ks_group_part<G>(__ballot(miss), half));
+        c0 = n0; c1 = n1; cb = nb;
+    }
+    if (have && l == 0) out[item] = make_uint2(tot, mis);
+}
+
+hipError_t kset_spans_run(const uint8_t* bytes, const uint64_t* item_lo, const uint32_t* item_len, uint32_t n_items, uint32_t k,
+                          const uint64_t* table, uint64_t slots, uint2* out, int group, hipStream_t st) {
+    if (!n_items) return hipSuccess;
+    const uint32_t per_block = (uint32_t)KS_THREADS / (uint32_t)group;
+    const uint32_t blocks = (n_items + per_block - 1) / per_block;
+    if (group == 32) kset_spans_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out);
+    else kset_spans_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out);
+    return hipGetLastError();
+}
+
 hipError_t kset_insert_run(const uint8_t* bytes, uint64_t n, uint32_t k, uint64_t* table, uint64_t slots, unsigned long long* ctr, hipStream_t st) {
     if (!n) return hipSuccess;
     const uint64_t blocks = (n + KS_BLOCK_BYTES - 1) / KS_BLOCK_BYTES;

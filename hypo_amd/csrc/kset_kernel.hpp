@@ -23,5 +23,12 @@ hipError_t kset_rehash_run(const uint64_t* old_table, uint64_t old_slots, uint64
 // ACGTacgt only, missing[s] += those whose canonical k-mer is not in the table.  total / missing must be zeroed by the caller.
 hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table,
                           uint64_t slots, unsigned long long* total, unsigned long long* missing, hipStream_t st);
+// n_items pieces of spans: item i is bytes[item_lo[i], item_lo[i] + item_len[i]), no window crosses its ends; out[i] = (its windows
+// made of ACGTacgt only, those not in the table).  A group of `group` lanes (32 or 64) owns an item; the caller cuts a span into
+// items of at most KSET_SPAN_PIECE windows (consecutive items overlap by k - 1 bytes) and adds their results up.
+constexpr uint32_t KSET_SPAN_PIECE = 2048;
+constexpr int KSET_SPAN_GROUP = 32;                // the default geometry (DESIGN.md "k-mer guard": measured against 64)
+hipError_t kset_spans_run(const uint8_t* bytes, const uint64_t* item_lo, const uint32_t* item_len, uint32_t n_items, uint32_t k,
+                          const uint64_t* table, uint64_t slots, uint2* out, int group, hipStream_t st);
 
 }  // namespace hypo

@@ -426,6 +426,13 @@ int hypo_gpu_kset_add(const char* bytes, uint64_t n);
 int hypo_gpu_kset_size(uint64_t* n_distinct, uint64_t* table_bytes);
 int hypo_gpu_kset_query(const char* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t* total, uint64_t* missing);
 int hypo_gpu_kset_end(void);
+/* Many short spans of one text against the set (hypo --kmer-guard; DESIGN.md "k-mer guard").  Additive to ABI 11: callers bind it
+ * by name.  Span s is bytes[lo[s], hi[s]); total[s] = its length-k windows made of ACGTacgt only, missing[s] = those, with
+ * multiplicity, whose canonical k-mer is not in the set (the byte rules of hypo_gpu_kset_query).  No window crosses a span's ends.
+ * Spans may overlap, repeat, be empty or shorter than k, and come in any order; the answers depend on the input alone.  All
+ * n_bytes are sent to the device once, whatever the spans cover.  lo[s] > hi[s] or hi[s] > n_bytes: HYPO_E_INVALID.  Without a
+ * set: HYPO_E_INVALID, as hypo_gpu_kset_query.  Synchronous, on the calling thread's context. */
+int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_t* lo, const uint64_t* hi, uint32_t n_spans, uint64_t* total, uint64_t* missing);
 
 /* Kernel timing with HIP events on the stream the kernels run on ----------------------------------
  * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each records
