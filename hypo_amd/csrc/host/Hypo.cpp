@@ -1,6 +1,6 @@
 // Hypo.cpp — orchestration of one polishing run (reference: src/Hypo.cpp).
 #include "Hypo.hpp"
-#include "DeviceArms.hpp"
+#include "RunOutputs.hpp"
 #include "SolidBuild.hpp"
 #include "EditVcf.hpp"
 #include "KmerGuard.hpp"
@@ -8,24 +8,64 @@
 #include <ctime>
 #include <omp.h>
 #include <sys/resource.h>
-#include <thread>
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
-#include <fstream>
 #include <iostream>
-
 #include <atomic>
 namespace hypo {
 extern std::atomic<uint64_t> g_stage_counters[5];      // host/Contig.cpp
+
+// --vcf, --qv, --kmer-guard: the entry points Hypo::bind_extras bound and what the three keep from the reads to the last contig
+struct Extras {
+    EditScriptsFn edit_fn = nullptr, guard_edit_fn = nullptr;
+    QvReport qv;
+    KmerGuard guard;
+    bool qv_on = false, guard_on = false, set_on = false;
+    ReadSink qv_sink;                                      // (holds a pointer to qv: an Extras stays where it is)
+    VcfStats vstats;
+    Extras() = default; Extras(const Extras&) = delete;
+    [[noreturn]] void qv_fail(const char* what) {
+        std::fprintf(stderr, "[Hypo::QV] Error: %s: %s\n", what, hypo_gpu_last_error());
+        qv.end();
+        std::exit(1);
+    }
+    void qv_reads_done(const SolidBuildStats& st, bool shared_pass) {
+        if (qv.read_size() != HYPO_OK) qv_fail("hypo_gpu_kset_size");
+        std::fprintf(stderr, "[Hypo::QV] Info: k-mer set of the reads (k = %u): %llu distinct k-mers, %.3f s in the insert calls of %.3f GB%s\n", qv.k(),
+                     (unsigned long long)qv.n_distinct(), st.sink_s, st.seq_bytes / 1e9, shared_pass ? " (the parse pass of the solid k-mers)" : " (reads parsed for the QV alone)");
+    }
+};
+
+// one contig batch on its way through the phases of Hypo::polish
+struct Batch {
+    const uint32_t batch_id, initial_cid, final_cid;
+    const bool over_contigs;                               // at least one contig per thread
+    Batch(uint32_t id, uint32_t c0, uint32_t c1, bool over) : batch_id(id), initial_cid(c0), final_cid(c1), over_contigs(over) {}
+    std::vector<CtxWork> work;                             // per device context: its contigs, or its piece of one
+    std::vector<char> votes_dev;                           // per context: its reads are resident
+    std::vector<char> on_dev;                              // per contig of the batch: its short arms were cut on a device
+    std::vector<char> long_dev;                            // ... and its long arms (LONG windows resident on the device)
+    std::vector<char> materialized;                        // per contig of the batch: its Alignment objects exist (host loops)
+    int32_t opened_with_cid = -1;
+    bool require_device = false;
+    std::thread long_prefetch;
+    uint32_t n_contigs() const { return final_cid - initial_cid; }
+};
+
 namespace {
-std::string pending_tmp;                               // <output>.tmp while a run is writing it (Hypo::polish); removed by a run that fails
-std::string pending_vcf_tmp;                           // <vcf>.tmp likewise (--vcf)
-std::string pending_qv_tmp;                            // <qv>.tmp while it is written (--qv)
-void remove_pending_output() {
-    if (!pending_tmp.empty()) std::remove(pending_tmp.c_str());
-    if (!pending_vcf_tmp.empty()) std::remove(pending_vcf_tmp.c_str());
-    if (!pending_qv_tmp.empty()) std::remove(pending_qv_tmp.c_str());
+void host_fallback(const Batch& b, const char* what) {
+    if (!b.require_device) return;
+    std::fflush(stdout);
+    std::fprintf(stderr, "[Hypo::Hypo] Error: --require-device: %s would be computed on the host (last device message: %s)\n", what, hypo_gpu_last_error());
+    std::exit(1);
+}
+// (the main thread may be inside a device call: leave without running the static destructors under it)
+[[noreturn]] void writer_fatal(const char* what) {
+    std::fprintf(stderr, "[Hypo::Hypo] Error: %s: %s\n", what, hypo_gpu_last_error());
+    std::fflush(nullptr);
+    RunOutputs::discard();
+    std::_Exit(1);
 }
 }
 
@@ -43,67 +83,103 @@ void Hypo::stop(const char* label) {
 }
 
 void Hypo::polish() {
-    // --kmer-guard: the k-mer set of --qv (with or without its table), the spans query against it, and the edit scripts whether
-    // or not a VCF is written.  Checked first, so that its error names everything the guard lacks.
-    const bool guard_on = _cFlags.kmer_guard;
-    KmerGuard guard;
-    EditScriptsFn guard_edit_fn = nullptr;
-    if (guard_on) {
-        guard.set_k(_cFlags.qv_k);
-        const bool have_spans = guard.bind(), have_set = QvReport().bind();
-        guard_edit_fn = bind_edit_scripts();
-        if (!have_spans || !have_set || !guard_edit_fn) {
-            std::fprintf(stderr, "[Hypo::Hypo] Error: --kmer-guard needs%s%s%s, which the device library does not provide\n", have_spans ? "" : " hypo_gpu_kset_query_spans",
-                         have_set ? "" : " hypo_gpu_kset_begin / _add / _size / _end", guard_edit_fn ? "" : " hypo_gpu_edit_scripts");
-            std::exit(1);
-        }
-    }
-    // --vcf: the device library must provide the edit scripts (C-ABI 10); bound by name, and only here, so that libraries without
-    // the entry point still serve every run without --vcf
-    EditScriptsFn edit_fn = nullptr;
-    if (!_cFlags.vcf_filename.empty() && !(edit_fn = bind_edit_scripts())) {
-        std::fprintf(stderr, "[Hypo::Hypo] Error: --vcf needs hypo_gpu_edit_scripts (C-ABI 10), which the device library does not provide\n");
-        std::exit(1);
-    }
-    // --qv: likewise the exact k-mer set (C-ABI 11).  It lives on context 0 from here until the last contig is written.
-    const bool qv_on = !_cFlags.qv_filename.empty();
-    QvReport qv;
-    if (qv_on && !qv.bind()) {
-        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv needs hypo_gpu_kset_begin / _add / _size / _query / _end (C-ABI 11), which the device library does not provide\n");
-        std::exit(1);
-    }
-    const bool set_on = qv_on || guard_on;
-    if (guard_on && !qv_on) (void)qv.bind();             // (the guard's check above found the entry points)
-    auto qv_fail = [&](const char* what) {
-        std::fprintf(stderr, "[Hypo::QV] Error: %s: %s\n", what, hypo_gpu_last_error());
-        qv.end();
-        std::exit(1);
-    };
-    ReadSink qv_sink;
-    if (set_on) {
-        // (sized for one k-mer per genome position; what the read errors add makes it grow)
-        const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
-        if (qv.begin(_cFlags.qv_k, _cFlags.genome_size, cap, 0) != HYPO_OK) qv_fail("the k-mer set could not be created");
-        qv_sink = qv.sink();
-    }
-    auto qv_reads_done = [&](const SolidBuildStats& st, bool shared_pass) {
-        if (qv.read_size() != HYPO_OK) qv_fail("hypo_gpu_kset_size");
-        std::fprintf(stderr, "[Hypo::QV] Info: k-mer set of the reads (k = %u): %llu distinct k-mers, %.3f s in the insert calls of %.3f GB%s\n", qv.k(),
-                     (unsigned long long)qv.n_distinct(), st.sink_s, st.seq_bytes / 1e9, shared_pass ? " (the parse pass of the solid k-mers)" : " (reads parsed for the QV alone)");
-    };
+    Extras ex;
+    bind_extras(ex);
     std::ofstream stagefile(HYPO_STAGEFILE, std::ofstream::out | std::ofstream::app);
     if (_cFlags.intermed && !stagefile.is_open()) {
         std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: Stage File (%s) exists but could not be opened!\n", HYPO_STAGEFILE);
         std::exit(1);
     }
-    // ---- solid k-mers: built from the short reads on the device (stage 0), or loaded from aux/solid_kmers.bvsd ------------------
-    start();
     SolidKmers sk; sk.k = _cFlags.k;
+    solid_kmers(ex, stagefile, sk);
+    load_contigs();
+    start_readers();
+    scan_solid_positions(sk);
+    RunOutputs out;
+    open_outputs(ex, out);
+    for (uint32_t batch_id = 0; batch_id < _num_batches; ++batch_id) {
+        std::fprintf(stdout, "********** [Hypo::Hypo] Info: BATCH-ID: %u\n", batch_id);
+        const uint32_t initial_cid = batch_id * _contig_batch_size;
+        const uint32_t final_cid = std::min<uint32_t>((uint32_t)_contigs.size(), initial_cid + _contig_batch_size);
+        Batch b(batch_id, initial_cid, final_cid, (final_cid - initial_cid) >= _cFlags.threads);
+        load_reads(b);
+        plan_batch(b);
+        kmer_votes(b);
+        prepare_division(b);
+        minimizer_votes(b);
+        divide(b);
+        cut_short_arms(b);
+        if (!_cFlags.lr_bam_filename.empty()) cut_long_arms(b);
+        else Contig::set_no_long_reads();
+        run_poa(b);
+        if (_dump.is_open()) dump_regions(b);
+        // --vcf: the writer thread aligns the batch's replacement units against their drafts (one call on context 0, beside the
+        // next batch's stages on this thread) and formats each contig's records next to its FASTA record, before the contig's
+        // windows go
+        if (_writer.joinable()) _writer.join();
+        _writer = std::thread([this, job = WriterJob{initial_cid, final_cid}, &ex, &out] { write_batch(job, ex, out); });
+    }
+    _alignment_store.clear();
+    if (_long_release.joinable()) _long_release.join();
+    commit_outputs(ex, out);
+    _times.overall = std::chrono::duration<double>(std::chrono::steady_clock::now() - _tstart).count();
+    std::fprintf(stdout, "RESOURCES ([Hypo:Hypo]: Overall. ): TIME= %g sec.\n", _times.overall);
+    if (std::getenv("HYPO_STAGE_COUNTERS"))
+        std::fprintf(stdout, "[Hypo::Hypo] Info: stage counters: solid k-mers accepted with 40-80 %% support %llu, refused after another such k-mer %llu; force_divide calls %llu; "
+                             "minimizers dropped as recurring %llu, as poly-base %llu\n", (unsigned long long)g_stage_counters[0].load(), (unsigned long long)g_stage_counters[1].load(),
+                     (unsigned long long)g_stage_counters[2].load(), (unsigned long long)g_stage_counters[3].load(), (unsigned long long)g_stage_counters[4].load());
+    // (1.5 M windows with their arms and consensus strings: freed contig by contig on all threads, 0.37 s of the C3 run's wall otherwise)
+#pragma omp parallel for schedule(dynamic, 1)
+    for (int64_t i = 0; i < (int64_t)_contigs.size(); ++i) _contigs[(size_t)i].reset();
+    _contigs.clear();
+    _device_arms.clear();
+}
+
+// ---- once per run, before the batches ----------------------------------------------------------------------------------------
+void Hypo::bind_extras(Extras& ex) {
+    // --kmer-guard: the k-mer set of --qv (with or without its table), the spans query against it, and the edit scripts whether
+    // or not a VCF is written.  Checked first, so that its error names everything the guard lacks.
+    ex.guard_on = _cFlags.kmer_guard;
+    if (ex.guard_on) {
+        ex.guard.set_k(_cFlags.qv_k);
+        const bool have_spans = ex.guard.bind(), have_set = QvReport().bind();
+        ex.guard_edit_fn = bind_edit_scripts();
+        if (!have_spans || !have_set || !ex.guard_edit_fn) {
+            std::fprintf(stderr, "[Hypo::Hypo] Error: --kmer-guard needs%s%s%s, which the device library does not provide\n", have_spans ? "" : " hypo_gpu_kset_query_spans",
+                         have_set ? "" : " hypo_gpu_kset_begin / _add / _size / _end", ex.guard_edit_fn ? "" : " hypo_gpu_edit_scripts");
+            std::exit(1);
+        }
+    }
+    // --vcf: the device library must provide the edit scripts (C-ABI 10); bound by name, and only here, so that libraries without
+    // the entry point still serve every run without --vcf
+    if (!_cFlags.vcf_filename.empty() && !(ex.edit_fn = bind_edit_scripts())) {
+        std::fprintf(stderr, "[Hypo::Hypo] Error: --vcf needs hypo_gpu_edit_scripts (C-ABI 10), which the device library does not provide\n");
+        std::exit(1);
+    }
+    // --qv: likewise the exact k-mer set (C-ABI 11).  It lives on context 0 from here until the last contig is written.
+    ex.qv_on = !_cFlags.qv_filename.empty();
+    if (ex.qv_on && !ex.qv.bind()) {
+        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv needs hypo_gpu_kset_begin / _add / _size / _query / _end (C-ABI 11), which the device library does not provide\n");
+        std::exit(1);
+    }
+    ex.set_on = ex.qv_on || ex.guard_on;
+    if (ex.guard_on && !ex.qv_on) (void)ex.qv.bind();    // (the guard's check above found the entry points)
+    if (ex.set_on) {
+        // (sized for one k-mer per genome position; what the read errors add makes it grow)
+        const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
+        if (ex.qv.begin(_cFlags.qv_k, _cFlags.genome_size, cap, 0) != HYPO_OK) ex.qv_fail("the k-mer set could not be created");
+        ex.qv_sink = ex.qv.sink();
+    }
+}
+
+// ---- solid k-mers: built from the short reads on the device (stage 0), or loaded from aux/solid_kmers.bvsd ------------------
+void Hypo::solid_kmers(Extras& ex, std::ofstream& stagefile, SolidKmers& sk) {
+    start();
     if (_cFlags.done_stage < 1) {
         SolidBuildStats st;
         std::string err;
-        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err, set_on ? &qv_sink : nullptr);
-        if (rc == SOLID_E_SINK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); qv.end(); std::exit(1); }
+        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err, ex.set_on ? &ex.qv_sink : nullptr);
+        if (rc == SOLID_E_SINK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); ex.qv.end(); std::exit(1); }
         if (rc == SOLID_E_UNDEFINED) {                   // the reference's own line for a failed initialise (src/Hypo.cpp:53)
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: %s\n", err.c_str());
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: KMC Output: Could not have successful run of SUK for computing Solid kmers!\n");
@@ -115,7 +191,7 @@ void Hypo::polish() {
         }
         std::fprintf(stderr, "[Hypo::SolidKmers] Info: device construction: %.3f s (parse %.3f s of %.3f GB, count %.3f s of %.3f GB sent, "
                              "histogram %.3f s, set %.3f s)\n", st.total_s, st.parse_s, st.file_bytes / 1e9, st.count_s, st.seq_bytes / 1e9, st.hist_s, st.fill_s);
-        if (set_on) qv_reads_done(st, true);
+        if (ex.set_on) ex.qv_reads_done(st, true);
         if (_cFlags.intermed) {
             if (!sk.store(HYPO_SKFILE)) {
                 std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Saving: Could not store the DS for Solid kmers!\n");
@@ -134,18 +210,20 @@ void Hypo::polish() {
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Loading: Could not load the DS for Solid kmers (%s)!\n", HYPO_SKFILE);
             std::exit(1);
         }
-        if (set_on) {                                    // the stored set needs no reads; the QV and the guard do
+        if (ex.set_on) {                                 // the stored set needs no reads; the QV and the guard do
             SolidBuildStats st;
             std::string err;
-            const int rc = stream_reads(_cFlags.sr_filenames, qv_sink, st, err);
-            if (rc != SOLID_OK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); qv.end(); std::exit(1); }
-            qv_reads_done(st, false);
+            const int rc = stream_reads(_cFlags.sr_filenames, ex.qv_sink, st, err);
+            if (rc != SOLID_OK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); ex.qv.end(); std::exit(1); }
+            ex.qv_reads_done(st, false);
         }
         stop("[Hypo:Hypo]: Loaded Solid kmers. ");
     }
     std::fprintf(stdout, "[Hypo::Hypo] Info: Number of (canonical) solid kmers (nonhp) : %lu\n", (unsigned long)sk.num_solid);
+}
 
-    // ---- contigs ------------------------------------------------------------------------------------------------------
+// ---- contigs ------------------------------------------------------------------------------------------------------
+void Hypo::load_contigs() {
     start();
     {
         std::vector<FastaRecord> recs;
@@ -166,31 +244,34 @@ void Hypo::polish() {
     }
     stop("[Hypo:Hypo]: Loaded Contigs. ");
     _alignment_store.resize(_contigs.size());
+}
 
+// the batches, the short-read file, the teams beside the main thread, and the helper that parses the first batch's short reads
+void Hypo::start_readers() {
     _contig_batch_size = _cFlags.processing_batch_size == 0 ? (uint32_t)_contigs.size() : _cFlags.processing_batch_size;
-    uint32_t num_batches = _contig_batch_size ? (uint32_t)_contigs.size() / _contig_batch_size : 0;
-    if (_contig_batch_size && _contigs.size() % _contig_batch_size != 0) ++num_batches;
+    _num_batches = _contig_batch_size ? (uint32_t)_contigs.size() / _contig_batch_size : 0;
+    if (_contig_batch_size && _contigs.size() % _contig_batch_size != 0) ++_num_batches;
     _sf_short.reset(new SamReader(_cFlags.sr_bam_filename));
     if (!_sf_short->ok()) { std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: %s\n", _cFlags.sr_bam_filename.c_str()); std::exit(1); }
     // (a run of ONE batch has nothing beside the parser but the scans: it keeps whole teams)
-    const int side_team = num_batches > 1 ? std::max(1, (int)_cFlags.threads / 2) : std::max(1, (int)_cFlags.threads);
-    const int inflate_threads = std::getenv("HYPO_INFLATE_THREADS") ? std::max(1, std::atoi(std::getenv("HYPO_INFLATE_THREADS"))) : side_team;
-    _sf_short->set_inflate_threads(inflate_threads);
+    const int side_team = _num_batches > 1 ? std::max(1, (int)_cFlags.threads / 2) : std::max(1, (int)_cFlags.threads);
+    _inflate_threads = std::getenv("HYPO_INFLATE_THREADS") ? std::max(1, std::atoi(std::getenv("HYPO_INFLATE_THREADS"))) : side_team;
+    _sf_short->set_inflate_threads(_inflate_threads);
     // the short reads of the first batch are parsed while the contigs are scanned (the parser needs the contigs' names and lengths only)
-    std::thread prefetch, long_release;
-    ReadBatch staged;                                      // the next batch's short reads while the helper parses them
-    const bool prefetch_on = !(std::getenv("HYPO_PREFETCH") && std::atoi(std::getenv("HYPO_PREFETCH")) == 0);
+    _prefetch_on = !(std::getenv("HYPO_PREFETCH") && std::atoi(std::getenv("HYPO_PREFETCH")) == 0);
     // The parser's team and the team that inflates BGZF blocks for it are HALF of -t each: with all three teams (these two and the main
     // thread's phases) at -t the stages only got in each other's way — 500 Mbp at k = 17, -t 64 on the 128-core box: 4.4-4.8 s with
     // 64 / 64, 3.7-4.0 s with 32 / 32, 3.8 s with 16 / 16 or 24 / 24 (profiles/history/r04_thread_split.txt).
-    int helper_threads = side_team;
-    if (const char* e = std::getenv("HYPO_HELPER_THREADS")) helper_threads = std::max(1, std::atoi(e));        // (experiments)
-    if (prefetch_on && num_batches > 0) {
-        staged.reset(_contigs.size());
-        prefetch = std::thread([this, &staged, helper_threads] { omp_set_num_threads(helper_threads); create_alignments_flat(0, staged); });
+    _helper_threads = side_team;
+    if (const char* e = std::getenv("HYPO_HELPER_THREADS")) _helper_threads = std::max(1, std::atoi(e));        // (experiments)
+    if (_prefetch_on && _num_batches > 0) {
+        _staged.reset(_contigs.size());
+        _prefetch = std::thread([this] { omp_set_num_threads(_helper_threads); create_alignments_flat(0, _staged); });
     }
+}
 
-    // ---- solid positions: device scan (the C-ABI call is serialised on the context's stream) ------
+// ---- solid positions: device scan (the C-ABI call is serialised on the context's stream) ------
+void Hypo::scan_solid_positions(const SolidKmers& sk) {
     // the 4^k-bit set goes to the device once (2 GiB at the default k = 17), not once per contig
     start();
     if (hypo_gpu_solid_set_upload(sk.words.data(), sk.get_k()) != HYPO_OK) { std::fprintf(stderr, "[Hypo::Hypo] Error: %s\n", hypo_gpu_last_error()); std::exit(1); }
@@ -205,573 +286,459 @@ void Hypo::polish() {
         }
     }
     stop("[Hypo:Hypo]: Found Solid pos in contigs. ");
+}
 
-    std::fprintf(stdout, "[Hypo::Hypo] Info: Number.of contigs: %lu; Number of batches: %u\n", (unsigned long)_contigs.size(), num_batches);
+// the long-read file, the region dump, one DeviceArms per device context, and the result files
+void Hypo::open_outputs(Extras& ex, RunOutputs& out) {
+    std::fprintf(stdout, "[Hypo::Hypo] Info: Number.of contigs: %lu; Number of batches: %u\n", (unsigned long)_contigs.size(), _num_batches);
     if (!_cFlags.lr_bam_filename.empty()) {
         _sf_long.reset(new SamReader(_cFlags.lr_bam_filename));
         if (!_sf_long->ok()) { std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: %s\n", _cFlags.lr_bam_filename.c_str()); std::exit(1); }
-        _sf_long->set_inflate_threads(inflate_threads);
+        _sf_long->set_inflate_threads(_inflate_threads);
     }
     // which inflate path this run takes (libdeflate is bound by name at run time, zlib is the fall-back: the two differ by 1.5 x on a
     // 3 Gbp run, so a number quoted from this binary should say which one it was)
     if (_sf_short->bgzf() || (_sf_long && _sf_long->bgzf()))
-        std::fprintf(stdout, "[Hypo::Hypo] Info: BGZF blocks are inflated by %s on %d threads\n", BlockInflater::name(), inflate_threads);
-    std::ofstream dump;
-    if (!_region_dump.empty()) dump.open(_region_dump);
+        std::fprintf(stdout, "[Hypo::Hypo] Info: BGZF blocks are inflated by %s on %d threads\n", BlockInflater::name(), _inflate_threads);
+    if (!_region_dump.empty()) _dump.open(_region_dump);
 
     // one per device context (they outlive the batches: spent alignments are released behind the phases that follow)
-    const int n_ctx = std::max(1, hypo_gpu_num_devices());
-    std::vector<std::unique_ptr<DeviceArms>> device_arms;
-    for (int d = 0; d < n_ctx; ++d) device_arms.emplace_back(new DeviceArms(d));
+    _n_ctx = std::max(1, hypo_gpu_num_devices());
+    for (int d = 0; d < _n_ctx; ++d) _device_arms.emplace_back(new DeviceArms(d));
     _reads.reset(_contigs.size());
     // The polished contigs of a batch are filed by a writer thread while the next batch is processed (the reference writes
     // everything at the end, src/Hypo.cpp:256-268: the same bytes in the same order); what a written contig no longer needs is
     // released there.
-    // The records go to <output>.tmp, which takes the output's name only when every contig is in it and the file closed without an error:
-    // a run that fails half way (a device error, a bad record three batches in) leaves no truncated file under the name the caller asked
-    // for, and an earlier result under that name stays what it was.  A failing run removes its .tmp on the way out.
-    pending_tmp = _cFlags.output_filename + ".tmp";
-    static bool cleanup_registered = false;
-    if (!cleanup_registered) { cleanup_registered = true; std::atexit(remove_pending_output); }
-    std::ofstream ofile(pending_tmp);
-    if (!ofile.is_open()) {
-        std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: Output File (%s) could not be opened!\n", pending_tmp.c_str());
-        std::exit(1);
+    out.open_fasta(_cFlags.output_filename);
+    if (ex.edit_fn) vcf_header(out.open_vcf(_cFlags.vcf_filename), _cFlags.draft_filename, _contigs, ex.guard_on);
+}
+
+// ---- the phases of a batch ---------------------------------------------------------------------------------------------------
+void Hypo::load_reads(Batch& b) {
+    // The short-read records of the NEXT batch are parsed on a helper thread while this batch is with the device (support
+    // votes, arms and POA leave the host's cores idle most of the time); it fills a store of its own,
+    // the reader state belongs to create_alignments alone.  HYPO_PREFETCH=0: one batch after the other.
+    start();
+    // (records of contigs behind the previous batch that it had consumed — _reads holds them — come first, then what the helper
+    // or this thread parses now)
+    const size_t slices_before = _reads.n_slices();
+    if (_prefetch.joinable()) {
+        _prefetch.join();
+        _reads.append(_staged);
+    } else {
+        create_alignments_flat(b.batch_id, _reads);
     }
-    std::ofstream vfile;
-    VcfStats vstats;
-    if (edit_fn) {                                         // (the VCF follows the FASTA: <vcf>.tmp until the run succeeds)
-        pending_vcf_tmp = _cFlags.vcf_filename + ".tmp";
-        vfile.open(pending_vcf_tmp);
-        if (!vfile.is_open()) {
-            std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: VCF File (%s) could not be opened!\n", pending_vcf_tmp.c_str());
-            std::exit(1);
-        }
-        vcf_header(vfile, _cFlags.draft_filename, _contigs, guard_on);
+    // (read before the helper starts on the next batch: did this batch's load open with the record carried over, and of which contig)
+    b.opened_with_cid = _rs_short.opened_with_cid;
+    stop("[Hypo:Hypo]: Loaded alignments. ");
+    if (_prefetch_on && b.batch_id + 1 < _num_batches) {
+        _staged.reset(_contigs.size());
+        // (the helper's team: all of -t while the machine has threads to spare, half of it otherwise — the main thread's own
+        // parallel phases run next to it)
+        _prefetch = std::thread([this, batch_id = b.batch_id] { omp_set_num_threads(_helper_threads); create_alignments_flat(batch_id + 1, _staged); });
     }
-    std::thread writer;
-    for (uint32_t batch_id = 0; batch_id < num_batches; ++batch_id) {
-        std::fprintf(stdout, "********** [Hypo::Hypo] Info: BATCH-ID: %u\n", batch_id);
-        const uint32_t initial_cid = batch_id * _contig_batch_size;
-        const uint32_t final_cid = std::min<uint32_t>((uint32_t)_contigs.size(), initial_cid + _contig_batch_size);
-        const bool over_contigs = (final_cid - initial_cid) >= _cFlags.threads;
-        // The short-read records of the NEXT batch are parsed on a helper thread while this batch is with the device (support
-        // votes, arms and POA leave the host's cores idle most of the time); it fills a store of its own,
-        // the reader state belongs to create_alignments alone.  HYPO_PREFETCH=0: one batch after the other.
-        start();
-        // (records of contigs behind the previous batch that it had consumed — _reads holds them — come first, then what the helper
-        // or this thread parses now)
-        const size_t slices_before = _reads.n_slices();
-        if (prefetch.joinable()) {
-            prefetch.join();
-            _reads.append(staged);
-        } else {
-            create_alignments_flat(batch_id, _reads);
-        }
-        // (read before the helper starts on the next batch: did this batch's load open with the record carried over, and of which contig)
-        const int32_t opened_with_cid = _rs_short.opened_with_cid;
-        stop("[Hypo:Hypo]: Loaded alignments. ");
-        if (prefetch_on && batch_id + 1 < num_batches) {
-            staged.reset(_contigs.size());
-            // (the helper's team: all of -t while the machine has threads to spare, half of it otherwise — the main thread's own
-            // parallel phases run next to it)
-            prefetch = std::thread([this, batch_id, &staged, helper_threads] { omp_set_num_threads(helper_threads); create_alignments_flat(batch_id + 1, staged); });
-        }
-        // ... and THIS batch's long reads (-B) are read and parsed while its short-read phases run (the reference loads them behind the
-        // short arms, src/Hypo.cpp:225-229; what they are does not depend on anything those phases compute): 2.4 of the 8 s of the
-        // 250 Mbp set.  The record the long reader consumed for a later contig during the LAST batch is already in that contig's
-        // store entry (below), so the order of the two streams is the reference's.
-        std::thread long_prefetch;
-        if (prefetch_on && !_cFlags.lr_bam_filename.empty()) {
-            if (long_release.joinable()) long_release.join();
-            _reads_long.reset(_contigs.size());
-            long_prefetch = std::thread([this, batch_id, helper_threads] { omp_set_num_threads(helper_threads); create_alignments_flat(batch_id, _reads_long, false); });
-        }
-        std::vector<char> materialized(final_cid - initial_cid, 0);        // per contig of the batch: its Alignment objects exist (host loops)
-        _mat_base = initial_cid;
-        // The first long read of a contig may have been consumed while the previous batch's long reads were loaded; the reference
-        // files it in this contig's store entry, where the short-read phases of THIS batch find it in front of the short reads and
-        // treat it as one of them (src/Hypo.cpp:314-325, :126-199).  Same here: it moves to the front of the flat batch.
-        // ... in front of them but for ONE: when the short-read loader of the batch before had already consumed this contig's first short
-        // read, that record was filed first (store entry = [short carry, long carry, this batch's short reads ..]): the long read goes
-        // behind the batch's opening record then.  Arm order inside a window is record order, and POA depends on it.
-        // (the contig the batch opened with goes FIRST: `slices_before + 1` is an index into the slice list as it stands now, and every
-        // other contig's records are put in front of everything afterwards, which shifts indices but not the order inside a contig)
-        if (opened_with_cid >= (int32_t)initial_cid && opened_with_cid < (int32_t)final_cid && !_alignment_store[(size_t)opened_with_cid].empty()) {
-            _reads.prepend((uint32_t)opened_with_cid, _alignment_store[(size_t)opened_with_cid], slices_before + 1);
-            _alignment_store[(size_t)opened_with_cid].clear();
-        }
-        for (uint32_t c = initial_cid; c < final_cid; ++c)
-            if (!_alignment_store[c].empty()) { _reads.prepend(c, _alignment_store[c], 0); _alignment_store[c].clear(); }
+    // ... and THIS batch's long reads (-B) are read and parsed while its short-read phases run (the reference loads them behind the
+    // short arms, src/Hypo.cpp:225-229; what they are does not depend on anything those phases compute): 2.4 of the 8 s of the
+    // 250 Mbp set.  The record the long reader consumed for a later contig during the LAST batch is already in that contig's
+    // store entry (below), so the order of the two streams is the reference's.
+    if (_prefetch_on && !_cFlags.lr_bam_filename.empty()) {
+        if (_long_release.joinable()) _long_release.join();
+        _reads_long.reset(_contigs.size());
+        b.long_prefetch = std::thread([this, batch_id = b.batch_id] { omp_set_num_threads(_helper_threads); create_alignments_flat(batch_id, _reads_long, false); });
+    }
+    b.materialized.assign(b.n_contigs(), 0);
+    // The first long read of a contig may have been consumed while the previous batch's long reads were loaded; the reference
+    // files it in this contig's store entry, where the short-read phases of THIS batch find it in front of the short reads and
+    // treat it as one of them (src/Hypo.cpp:314-325, :126-199).  Same here: it moves to the front of the flat batch.
+    // ... in front of them but for ONE: when the short-read loader of the batch before had already consumed this contig's first short
+    // read, that record was filed first (store entry = [short carry, long carry, this batch's short reads ..]): the long read goes
+    // behind the batch's opening record then.  Arm order inside a window is record order, and POA depends on it.
+    // (the contig the batch opened with goes FIRST: `slices_before + 1` is an index into the slice list as it stands now, and every
+    // other contig's records are put in front of everything afterwards, which shifts indices but not the order inside a contig)
+    const int32_t opened_with_cid = b.opened_with_cid;
+    if (opened_with_cid >= (int32_t)b.initial_cid && opened_with_cid < (int32_t)b.final_cid && !_alignment_store[(size_t)opened_with_cid].empty()) {
+        _reads.prepend((uint32_t)opened_with_cid, _alignment_store[(size_t)opened_with_cid], slices_before + 1);
+        _alignment_store[(size_t)opened_with_cid].clear();
+    }
+    for (uint32_t c = b.initial_cid; c < b.final_cid; ++c)
+        if (!_alignment_store[c].empty()) { _reads.prepend(c, _alignment_store[c], 0); _alignment_store[c].clear(); }
+}
 
-        // With several devices the contigs of the batch are dealt out to the contexts in contiguous ranges of about equal
-        // numbers of alignments: every context keeps the reads of its contigs, counts their support votes, cuts their arms and
-        // polishes its own resident windows; no window travels.  A batch with FEWER contigs than contexts (BASELINE config C4 is one
-        // 250 Mbp contig) shares its contigs out instead (round 4): a contig's contexts each own a coordinate range of it and work
-        // on the reads around that range (DeviceArms::set_piece) — the reference's loop is over the windows of ONE contig too
-        // (src/Hypo.cpp:236-248).
-        struct CtxWork { uint32_t c0 = 0, c1 = 0; bool piece = false; uint32_t own0 = 0, own1 = 0; };
-        std::vector<CtxWork> work((size_t)n_ctx);
-        const uint32_t n_batch_contigs = final_cid - initial_cid;
-        work[0].c0 = initial_cid; work[0].c1 = final_cid;
-        if ((uint32_t)n_ctx > 1 && !_cFlags.host_arms && n_batch_contigs >= (uint32_t)n_ctx) {
-            std::vector<uint32_t> ctx_cut((size_t)n_ctx + 1, final_cid);
-            ctx_cut[0] = initial_cid;
-            uint64_t total = 0, acc = 0;
-            for (uint32_t c = initial_cid; c < final_cid; ++c) total += _reads.count(c) + 1;
-            int d = 1;
-            for (uint32_t c = initial_cid; c < final_cid && d < n_ctx; ++c) {
-                acc += _reads.count(c) + 1;
-                // the cut behind contig c belongs to context d when the first d shares are full (every context gets >= 1 contig)
-                while (d < n_ctx && acc * (uint64_t)n_ctx >= total * (uint64_t)d && final_cid - (c + 1) >= (uint32_t)(n_ctx - d)) ctx_cut[(size_t)d++] = c + 1;
-            }
-            for (; d < n_ctx; ++d) ctx_cut[(size_t)d] = std::max(ctx_cut[(size_t)d - 1] + 1, final_cid - (uint32_t)(n_ctx - d));
-            for (int x = 0; x < n_ctx; ++x) { work[(size_t)x].c0 = ctx_cut[(size_t)x]; work[(size_t)x].c1 = ctx_cut[(size_t)x + 1]; }
-        } else if ((uint32_t)n_ctx > 1 && !_cFlags.host_arms && !std::getenv("HYPO_NO_PIECES") && hypo_gpu_reads_upload(nullptr, nullptr, 0) != HYPO_E_UNSUPPORTED) {
-            // (the probe: a library without the resident-read entry points — the CPU test shim — answers HYPO_E_UNSUPPORTED, and the
-            // host loops, which know nothing of pieces, take the batch as before)
-            // contexts per contig: one each, the rest one at a time to the contig with most alignments per context it has
-            std::vector<uint32_t> share(n_batch_contigs, 1);
-            for (uint32_t extra = (uint32_t)n_ctx - n_batch_contigs; extra > 0; --extra) {
-                uint32_t best = 0; double best_load = -1;
-                for (uint32_t i = 0; i < n_batch_contigs; ++i) {
-                    const double load = (double)(_reads.count(initial_cid + i) + 1) / share[i];
-                    if (load > best_load) { best_load = load; best = i; }
-                }
-                ++share[best];
-            }
-            int d = 0;
-            for (uint32_t i = 0; i < n_batch_contigs; ++i) {
-                const uint32_t c = initial_cid + i, len = (uint32_t)_contigs[c]->get_len();
-                for (uint32_t j = 0; j < share[i]; ++j, ++d) {
-                    CtxWork& w = work[(size_t)d];
-                    w.c0 = c; w.c1 = c + 1; w.piece = share[i] > 1;
-                    w.own0 = (uint32_t)((uint64_t)len * j / share[i]); w.own1 = j + 1 == share[i] ? len : (uint32_t)((uint64_t)len * (j + 1) / share[i]);
-                }
-            }
-        }
-        for (int d = 0; d < n_ctx; ++d) {
-            const CtxWork& w = work[(size_t)d];
-            if (w.piece) {
-                // halo: the longest read of the contig + the longest window a read at the edge can still reach into
-                const uint32_t halo = _reads.max_span(w.c0) + 2048;
-                device_arms[(size_t)d]->set_piece(w.own0, w.own1, halo, (uint32_t)_contigs[w.c0]->get_len());
-                std::fprintf(stdout, "[Hypo::Hypo] Info: context %d owns [%u, %u) of contig %s (halo %u)\n", d, w.own0, w.own1, _contigs[w.c0]->get_name().c_str(), halo);
-            } else device_arms[(size_t)d]->clear_piece();
-        }
-        (void)hypo_gpu_last_error();
-        auto piece_failed = [&](int d, const char* what) {
-            std::fprintf(stderr, "[Hypo::Hypo] Error: %s failed on context %d, which shares contig %s with other contexts (%s); run on one device or with --host-arms\n",
-                         what, d, _contigs[work[(size_t)d].c0]->get_name().c_str(), hypo_gpu_last_error());
-            std::exit(1);
-        };
-        // N1: the reads go to the device once, now; the support votes are counted there (support_kernel.hip) and the arm kernels
-        // use the same copy later.  --host-arms, an unsorted file or a device error: the reference's host loops, per contig range.
-        start();
-        // --require-device / HYPO_REQUIRE_DEVICE=1: a stage that was meant for the device and is about to run in the host loops ends
-        // the run instead (the Info lines of DeviceArms say why it did not run there).  Not with --host-arms / HYPO_HOST_SUPPORT,
-        // which ask for the host loops.
-        const bool require_device = (_cFlags.require_device || (std::getenv("HYPO_REQUIRE_DEVICE") && std::atoi(std::getenv("HYPO_REQUIRE_DEVICE")) != 0)) &&
-                                    !_cFlags.host_arms && !std::getenv("HYPO_HOST_SUPPORT");
-        auto host_fallback = [&](const char* what) {
-            if (!require_device) return;
-            std::fflush(stdout);
-            std::fprintf(stderr, "[Hypo::Hypo] Error: --require-device: %s would be computed on the host (last device message: %s)\n", what, hypo_gpu_last_error());
-            std::exit(1);
-        };
-        std::vector<char> votes_dev((size_t)n_ctx, 0);         // per context: its reads are resident
-        if (!_cFlags.host_arms && !std::getenv("HYPO_HOST_SUPPORT"))
-            for (int d = 0; d < n_ctx; ++d) {
-                const uint32_t c0 = work[(size_t)d].c0, c1 = work[(size_t)d].c1;
-                if (c0 < c1) votes_dev[(size_t)d] = device_arms[(size_t)d]->upload_reads(_contigs, c0, c1, _reads) ? 1 : 0;
-                if (c0 < c1 && work[(size_t)d].piece && !votes_dev[(size_t)d]) piece_failed(d, "the upload of the reads");
-            }
-        for (int d = 0; d < n_ctx; ++d) {
-            const uint32_t c0 = work[(size_t)d].c0, c1 = work[(size_t)d].c1;
-            if (c0 >= c1) continue;
-            if (votes_dev[(size_t)d] && device_arms[(size_t)d]->support_kmers(_contigs, c0, c1, _cFlags.k)) continue;
-            if (work[(size_t)d].piece) piece_failed(d, "the k-mer support votes");
-            { uint64_t nr = 0; for (uint32_t c = c0; c < c1; ++c) nr += _reads.count(c); if (nr) host_fallback("the k-mer support votes"); }
-            materialize_alignments(c0, c1, materialized);
-            for (uint32_t cid = c0; cid < c1; ++cid) {
-                _contigs[cid]->ensure_kids();
-                auto& alns = _alignment_store[cid];
-#pragma omp parallel for
-                for (int64_t t = 0; t < (int64_t)alns.size(); ++t) alns[(size_t)t]->update_solidkmers_support(_cFlags.k, *_contigs[cid]);
-            }
-        }
-        hypo_gpu_use_device(0);
-        if (const char* vp = std::getenv("HYPO_DUMP_VOTES"))        // (tests: device votes against the host loops of the reference, counter by counter)
-            if (std::FILE* vf = std::fopen(vp, batch_id == 0 ? "wb" : "ab")) { for (uint32_t c = initial_cid; c < final_cid; ++c) _contigs[c]->dump_votes(vf, 0); std::fclose(vf); }
-        stop("[Hypo:Hypo]: Solid kmers support update. ");
+// the contigs of the batch are dealt out to the device contexts (CtxPlan.hpp), and every context is told its piece, if it has one
+void Hypo::plan_batch(Batch& b) {
+    std::vector<uint64_t> n_reads(b.n_contigs());
+    std::vector<uint32_t> contig_len(b.n_contigs());
+    for (uint32_t c = b.initial_cid; c < b.final_cid; ++c) { n_reads[c - b.initial_cid] = _reads.count(c); contig_len[c - b.initial_cid] = (uint32_t)_contigs[c]->get_len(); }
+    const bool split_batch = (uint32_t)_n_ctx > 1 && !_cFlags.host_arms;
+    // (the probe: a library without the resident-read entry points — the CPU test shim — answers HYPO_E_UNSUPPORTED, and the
+    // host loops, which know nothing of pieces, take the batch as before)
+    const bool allow_pieces = split_batch && b.n_contigs() < (uint32_t)_n_ctx && !std::getenv("HYPO_NO_PIECES") && hypo_gpu_reads_upload(nullptr, nullptr, 0) != HYPO_E_UNSUPPORTED;
+    b.work = plan_contexts(b.initial_cid, b.final_cid, _n_ctx, n_reads.data(), contig_len.data(), split_batch, allow_pieces);
+    for (int d = 0; d < _n_ctx; ++d) {
+        const CtxWork& w = b.work[(size_t)d];
+        if (w.piece) {
+            // halo: the longest read of the contig + the longest window a read at the edge can still reach into
+            const uint32_t halo = _reads.max_span(w.c0) + 2048;
+            _device_arms[(size_t)d]->set_piece(w.own0, w.own1, halo, (uint32_t)_contigs[w.c0]->get_len());
+            std::fprintf(stdout, "[Hypo::Hypo] Info: context %d owns [%u, %u) of contig %s (halo %u)\n", d, w.own0, w.own1, _contigs[w.c0]->get_name().c_str(), halo);
+        } else _device_arms[(size_t)d]->clear_piece();
+    }
+    (void)hypo_gpu_last_error();
+}
 
-        start();
-        {   // many contigs: one contig per thread as in the reference; fewer contigs than threads: the contigs side by side, each
-            // with its share of the threads for the minimizers of its mega-windows (a nested team; -p 10 on 64 threads took 45 ms per
-            // batch one contig after the other)
-            const int nc = (int)(final_cid - initial_cid), T = (int)_cFlags.threads;
-            const int outer = std::max(1, std::min(nc, T)), inner = over_contigs ? 1 : std::max(1, T / outer);
-            if (inner > 1) omp_set_max_active_levels(2);
-#pragma omp parallel for schedule(static, 1) num_threads(outer)
-            for (int64_t i = initial_cid; i < (int64_t)final_cid; ++i) {
-                omp_set_num_threads(inner);
-                _contigs[(size_t)i]->prepare_for_division(_cFlags.k);
-            }
-            omp_set_max_active_levels(1);
-        }
-        uint64_t num_sr = 0, len_sr = 0;
-        for (uint32_t i = initial_cid; i < final_cid; ++i) { num_sr += _contigs[i]->get_num_sr(); len_sr += _contigs[i]->get_len_sr(); }
-        std::fprintf(stdout, "[Hypo::Hypo] Info: Total number of SR: %lu; Total length of SR: %lu\n", (unsigned long)num_sr, (unsigned long)len_sr);
-        stop("[Hypo:Hypo]: Finding SR (and preparing for division). ");
+void Hypo::piece_failed(const Batch& b, int d, const char* what) {
+    std::fprintf(stderr, "[Hypo::Hypo] Error: %s failed on context %d, which shares contig %s with other contexts (%s); run on one device or with --host-arms\n",
+                 what, d, _contigs[b.work[(size_t)d].c0]->get_name().c_str(), hypo_gpu_last_error());
+    std::exit(1);
+}
 
-        start();
-        for (int d = 0; d < n_ctx; ++d) {
-            const uint32_t c0 = work[(size_t)d].c0, c1 = work[(size_t)d].c1;
-            if (c0 >= c1) continue;
-            if (votes_dev[(size_t)d] && device_arms[(size_t)d]->support_minimizers(_contigs, c0, c1)) continue;
-            if (work[(size_t)d].piece) piece_failed(d, "the minimizer support votes");
-            { uint64_t nr = 0; for (uint32_t c = c0; c < c1; ++c) nr += _reads.count(c); if (nr) host_fallback("the minimizer support votes"); }
-            materialize_alignments(c0, c1, materialized);
-            for (uint32_t cid = c0; cid < c1; ++cid) {
-                auto& alns = _alignment_store[cid];
-#pragma omp parallel for
-                for (int64_t t = 0; t < (int64_t)alns.size(); ++t) alns[(size_t)t]->update_minimisers_support(*_contigs[cid]);
-            }
-        }
-        hypo_gpu_use_device(0);
-        if (const char* vp = std::getenv("HYPO_DUMP_VOTES"))
-            if (std::FILE* vf = std::fopen(vp, "ab")) { for (uint32_t c = initial_cid; c < final_cid; ++c) _contigs[c]->dump_votes(vf, 1); std::fclose(vf); }
-        stop("[Hypo:Hypo]: Minimisers support update. ");
-
-        start();
-        {   // (as above: fewer contigs than threads share the team, each contig builds its Window objects with its share)
-            const int nc = (int)(final_cid - initial_cid), T = (int)_cFlags.threads;
-            const int outer = std::max(1, std::min(nc, T)), inner = over_contigs ? 1 : std::max(1, T / outer);
-            if (inner > 1) omp_set_max_active_levels(2);
-#pragma omp parallel for schedule(static, 1) num_threads(outer)
-            for (int64_t i = initial_cid; i < (int64_t)final_cid; ++i) {
-                omp_set_num_threads(inner);
-                _contigs[(size_t)i]->divide_into_regions();
-            }
-            omp_set_max_active_levels(1);
-        }
-        stop("[Hypo:Hypo]: Division into windows. ");
-
-        start();
-        // The device cuts the reads into arms, prunes the windows and keeps the window batch in its memory (DeviceArms.hpp);
-        // --host-arms, several devices or an unsorted alignment file take the host loops of the reference instead.
-        std::vector<char> on_dev(final_cid - initial_cid, 0);  // per contig of the batch: its short arms were cut on a device
-        std::vector<char> long_dev(final_cid - initial_cid, 0);  // ... and its long arms (LONG windows resident on the device)
-        if (!_cFlags.host_arms) {
-            for (int d = 0; d < n_ctx; ++d) {
-                const uint32_t c0 = work[(size_t)d].c0, c1 = work[(size_t)d].c1;
-                if (c0 >= c1) continue;
-                if (work[(size_t)d].piece) {
-                    // the halo was chosen before the division: a window longer than it (a weak region force_divide could not cut) would lose
-                    // the arms of the reads beyond it — the span grows to the longest window this context owns and its reads go over again
-                    const uint32_t longest = device_arms[(size_t)d]->longest_owned_window(*_contigs[c0], false);
-                    if (device_arms[(size_t)d]->widen_halo(longest + 64))
-                        std::fprintf(stdout, "[Hypo::Hypo] Info: context %d owns a window of %u bases: halo widened to %u, its reads are uploaded again\n", d, longest, device_arms[(size_t)d]->halo());
-                }
-                if (device_arms[(size_t)d]->build(_contigs, c0, c1, _reads, _cFlags.k))
-                    for (uint32_t c = c0; c < c1; ++c) on_dev[c - initial_cid] = 1;
-                else if (work[(size_t)d].piece) piece_failed(d, "short-arm selection");
-            }
-            for (int d = 0; d < n_ctx; ++d) if (work[(size_t)d].piece) DeviceArms::finish_short(_contigs, work[(size_t)d].c0, work[(size_t)d].c1);
-            hypo_gpu_use_device(0);
-        }
-        for (uint32_t cid = initial_cid; cid < final_cid; ++cid) {
-            if (on_dev[cid - initial_cid]) { _alignment_store[cid].clear(); continue; }       // (objects a host vote loop had asked for)
-            if (!_cFlags.host_arms && _reads.count(cid) > 0) host_fallback("short-arm selection");
-            materialize_alignments(cid, cid + 1, materialized);
+// One support-vote stage: every context counts the votes of its contigs on the device (on_device), or the reference's host loop
+// runs per_alignment over the contigs' Alignment objects.  kind: what Contig::dump_votes calls the counters, 0 = solid k-mers,
+// 1 = minimizers.
+template <class Dev, class Host> void Hypo::support_votes(Batch& b, const char* what, int kind, Dev on_device, Host per_alignment) {
+    for (int d = 0; d < _n_ctx; ++d) {
+        const uint32_t c0 = b.work[(size_t)d].c0, c1 = b.work[(size_t)d].c1;
+        if (c0 >= c1) continue;
+        if (b.votes_dev[(size_t)d] && on_device(*_device_arms[(size_t)d], c0, c1)) continue;
+        if (b.work[(size_t)d].piece) piece_failed(b, d, what);
+        { uint64_t nr = 0; for (uint32_t c = c0; c < c1; ++c) nr += _reads.count(c); if (nr) host_fallback(b, what); }
+        materialize_alignments(b, c0, c1);
+        for (uint32_t cid = c0; cid < c1; ++cid) {
+            if (kind == 0) _contigs[cid]->ensure_kids();
             auto& alns = _alignment_store[cid];
 #pragma omp parallel for
-            for (int64_t t = 0; t < (int64_t)alns.size(); ++t) alns[(size_t)t]->find_short_arms(_cFlags.k, *_contigs[cid]);
+            for (int64_t t = 0; t < (int64_t)alns.size(); ++t) per_alignment(*alns[(size_t)t], *_contigs[cid]);
         }
-        stop("[Hypo:Hypo]: Short arms computing. ");
-        start();
-        // few contigs: the parallelism is inside a contig (window ranges); many contigs: one contig per thread as in the reference
-#pragma omp parallel for schedule(static, 1) if (over_contigs)
-        for (int64_t i = initial_cid; i < (int64_t)final_cid; ++i) {
-            if (on_dev[(size_t)i - initial_cid]) continue;
-            _contigs[(size_t)i]->fill_short_windows(_alignment_store[(size_t)i]); _alignment_store[(size_t)i].clear();
-        }
-        {   // the batch's short reads are spent; what it consumed for contigs of later batches stays for them (src/Hypo.cpp:314-325)
-            ReadBatch later;
-            later.reset(_contigs.size());
-            _reads.carry_beyond(final_cid, later);
-            _reads.clear(&_block_pool, &_pool_mu);
-            _reads.reset(_contigs.size());
-            _reads.append(later);
-        }
-        stop("[Hypo:Hypo]: Short arms filling. ");
-
-        if (!_cFlags.lr_bam_filename.empty()) {
-            start();
-            // the long reads of the batch, flat like the short ones (ReadBatch.hpp; round 4: 1.2 M objects of 8 kb each took 2.5 s to
-            // build on the 250 Mbp set).  The reader stops behind the first kept record of a later contig; the reference files that
-            // record in ITS contig's store entry (src/Hypo.cpp:314-325), where that batch's short-read phases find it: it becomes
-            // an object there (see the top of the batch loop).
-            if (long_prefetch.joinable()) long_prefetch.join();
-            else { _reads_long.reset(_contigs.size()); create_alignments_flat(batch_id, _reads_long, false); }
-            if (_rs_long.carry_blk) {
-                ReadBatch one;
-                one.reset(_contigs.size());
-                one.add(_rs_long.carry_blk, _rs_long.carry_r0, _rs_long.carry_r1);
-                if (_rs_long.carry_cid >= 0) one.materialize((uint32_t)_rs_long.carry_cid, _alignment_store[(size_t)_rs_long.carry_cid]);
-                _rs_long.carry_blk.reset();
-            }
-            stop("[Hypo:Hypo]: Loaded alignments of Long reads. ");
-            start();
-            const auto tl0 = std::chrono::steady_clock::now();
-#pragma omp parallel for schedule(static, 1)
-            for (int64_t i = initial_cid; i < (int64_t)final_cid; ++i) _contigs[(size_t)i]->prepare_long_windows();
-            const auto tl1 = std::chrono::steady_clock::now();
-            // the long reads are cut into arms, filtered (Filter::is_good) and kept as a second resident batch by the context that
-            // holds the contig's short arms; --host-arms, an unsorted file or a device error take the reference's host loops
-            std::vector<char> long_on_dev(final_cid - initial_cid, 0);
-            if (!_cFlags.host_arms) {
-                for (int d = 0; d < n_ctx; ++d) {
-                    const uint32_t c0 = work[(size_t)d].c0, c1 = work[(size_t)d].c1;
-                    if (c0 >= c1) continue;
-                    if (work[(size_t)d].piece) {                     // (as for the short arms: the LONG pseudo-windows exist only now)
-                        const uint32_t longest = device_arms[(size_t)d]->longest_owned_window(*_contigs[c0], true);
-                        if (device_arms[(size_t)d]->widen_halo(longest + 64))
-                            std::fprintf(stdout, "[Hypo::Hypo] Info: context %d owns a LONG window of %u bases: halo widened to %u\n", d, longest, device_arms[(size_t)d]->halo());
-                    }
-                    if (device_arms[(size_t)d]->build_long(_contigs, c0, c1, _reads_long))
-                        for (uint32_t c = c0; c < c1; ++c) long_on_dev[c - initial_cid] |= 1;
-                    else {
-                        if (device_arms[(size_t)d]->long_failed()) host_fallback("long-arm selection");
-                        if (work[(size_t)d].piece) long_on_dev[c0 - initial_cid] |= 2;      // (a shared contig: all of its contexts or none)
-                    }
-                }
-                for (int d = 0; d < n_ctx; ++d) {
-                    if (!work[(size_t)d].piece) continue;
-                    const uint32_t c = work[(size_t)d].c0;
-                    if (long_on_dev[c - initial_cid] & 2) device_arms[(size_t)d]->drop_long();
-                }
-                for (uint32_t c = initial_cid; c < final_cid; ++c) {
-                    char& f = long_on_dev[c - initial_cid];
-                    const bool shared = f != 0 && n_batch_contigs < (uint32_t)n_ctx;
-                    if (f & 2) f = 0;
-                    else if (f == 1 && shared) DeviceArms::finish_long(_contigs, c, c + 1);
-                }
-                hypo_gpu_use_device(0);
-            }
-            for (uint32_t cid = initial_cid; cid < final_cid; ++cid) {
-                if (long_on_dev[cid - initial_cid]) continue;
-                auto& alns = _alignment_store[cid];                     // (the host loops of the reference read objects)
-                _reads_long.materialize(cid, alns);
-#pragma omp parallel for
-                for (int64_t t = 0; t < (int64_t)alns.size(); ++t) alns[(size_t)t]->find_long_arms(*_contigs[cid]);
-            }
-#pragma omp parallel for schedule(static, 1) if (over_contigs)
-            for (int64_t i = initial_cid; i < (int64_t)final_cid; ++i) {
-                if (long_on_dev[(size_t)i - initial_cid]) continue;
-                _contigs[(size_t)i]->fill_long_windows(_alignment_store[(size_t)i]); _alignment_store[(size_t)i].clear();
-            }
-            for (uint32_t c = initial_cid; c < final_cid; ++c) long_dev[c - initial_cid] = long_on_dev[c - initial_cid];
-            const auto tl2 = std::chrono::steady_clock::now();
-            // (7 GB of parsed long reads on the 250 Mbp set: handed back behind the POA, not in front of it)
-            if (long_release.joinable()) long_release.join();
-            long_release = std::thread([this, spent = std::make_shared<ReadBatch>(std::move(_reads_long))] { spent->clear(&_block_pool, &_pool_mu); });
-            _reads_long = ReadBatch();
-            if (std::getenv("HYPO_HOST_TIMING")) {
-                auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
-                std::fprintf(stderr, "[timing] long arms: prepare_long_windows %.3f s, arms %.3f s, long reads released %.3f s\n", sec(tl0, tl1), sec(tl1, tl2), sec(tl2, std::chrono::steady_clock::now()));
-            }
-            stop("[Hypo:Hypo]: Long arms filling. ");
-        } else {
-            Contig::set_no_long_reads();
-        }
-
-        // ---- POA: every valid window of the contig batch in one device call (reference: per-window OpenMP loop) ----
-        start();
-        Window::prepare_for_poa(_cFlags.score_params, _cFlags.threads);
-        std::vector<Window*> wins;
-        for (uint32_t i = initial_cid; i < final_cid; ++i)
-            for (uint64_t w = 0; w < _contigs[i]->get_num_regions(); ++w)
-                if (_contigs[i]->is_valid_window((uint32_t)w)) {
-                    const bool lw = _contigs[i]->window((uint32_t)w)->is_long();
-                    if (!(lw ? long_dev[i - initial_cid] : on_dev[i - initial_cid])) wins.push_back(_contigs[i]->window((uint32_t)w));
-                }
-        uint64_t n_resident = 0;
-        {   // the resident batches: every context polishes its own, side by side; what needs the host's retry path joins `wins`
-            std::vector<std::vector<Window*>> retry((size_t)n_ctx);
-            std::vector<int> prc((size_t)n_ctx, HYPO_OK);
-            std::vector<std::string> perr((size_t)n_ctx);
-            std::vector<std::thread> th;
-            for (int d = 0; d < n_ctx; ++d) {
-                DeviceArms& da = *device_arms[(size_t)d];
-                da.reset_polished();
-                if (!da.active() && !da.active_long()) continue;
-
-                auto job = [&, d] {
-                    DeviceArms& me = *device_arms[(size_t)d];
-                    prc[(size_t)d] = me.polish(_cFlags.score_params, dump.is_open(), &retry[(size_t)d]);
-                    if (prc[(size_t)d] == HYPO_OK) prc[(size_t)d] = me.polish_long(_cFlags.score_params, dump.is_open(), &retry[(size_t)d]);
-                    if (prc[(size_t)d] != HYPO_OK) perr[(size_t)d] = hypo_gpu_last_error();
-                };
-                if (n_ctx == 1) job(); else th.emplace_back(job);
-            }
-            for (auto& t : th) t.join();
-            for (int d = 0; d < n_ctx; ++d) n_resident += device_arms[(size_t)d]->polished_windows();      // (windows a context owns: its halo's are another's)
-            hypo_gpu_use_device(0);
-            for (int d = 0; d < n_ctx; ++d) {
-                if (prc[(size_t)d] != HYPO_OK) { std::fprintf(stderr, "[Hypo::Window] Error: %s\n", perr[(size_t)d].c_str()); std::exit(1); }
-                wins.insert(wins.end(), retry[(size_t)d].begin(), retry[(size_t)d].end());
-            }
-        }
-        if (Window::generate_consensus_batch(wins) != HYPO_OK) { std::fprintf(stderr, "[Hypo::Window] Error: %s\n", hypo_gpu_last_error()); std::exit(1); }
-        std::fprintf(stdout, "[Hypo::Hypo] Info: polished windows (Batch %u): %lu\n", batch_id, (unsigned long)(wins.size() + n_resident));
-        stop("[Hypo:Hypo]: POA of windows. ");
-
-        if (dump.is_open())
-            for (uint32_t i = initial_cid; i < final_cid; ++i)
-                for (uint64_t w = 0; w < _contigs[i]->get_num_regions(); ++w) {
-                    uint32_t b, e; RegionType t;
-                    _contigs[i]->region((uint32_t)w, b, e, t);
-                    const Window* win = _contigs[i]->window((uint32_t)w);
-                    if (!win && t != RegionType::SR && t != RegionType::MSR && !_cFlags.lr_bam_filename.empty()) continue;   // swallowed by a LONG window
-                    if (win) e = b + (uint32_t)win->get_window_len();           // a LONG window spans the arm-less regions that follow it
-                    dump << _contigs[i]->get_name() << '\t' << b << '\t' << e << '\t' << region_name(t);
-                    if (win) dump << '\t' << win->dump_counts() << '\t' << win->arms_crc32() << '\t' << win->get_consensus();
-                    if (win && std::getenv("HYPO_REGION_DUMP_ARMS")) dump << '\t' << (win->is_long() ? "L" : "S") << '\t' << win->dump_text();
-                    else if (t != RegionType::SR && t != RegionType::MSR) dump << "\t0\t0\t0\t0\t0\t" << _contigs[i]->draft_segment(b, e);   // no arms: draft kept
-                    dump << '\n';
-                }
-        // --vcf: the writer thread aligns the batch's replacement units against their drafts (one call on context 0, beside the
-        // next batch's stages on this thread) and formats each contig's records next to its FASTA record, before the contig's
-        // windows go
-        if (writer.joinable()) writer.join();
-        writer = std::thread([this, &ofile, &vfile, &vstats, &qv, &guard, qv_on, guard_on, edit_fn, guard_edit_fn, initial_cid, final_cid] {
-            omp_set_num_threads(std::max(1, std::min((int)_cFlags.threads, 8)));
-            std::unique_ptr<EditBatchResult> edits;
-            if (edit_fn || guard_on) {
-                edits.reset(new EditBatchResult());
-                if (hypo_gpu_use_device(0) != HYPO_OK || edit_scripts_for(guard_on ? guard_edit_fn : edit_fn, _contigs, initial_cid, final_cid, *edits) != HYPO_OK) {
-                    // (the main thread may be inside a device call: leave without running the static destructors under it)
-                    std::fprintf(stderr, "[Hypo::Hypo] Error: edit scripts: %s\n", hypo_gpu_last_error());
-                    std::fflush(nullptr);
-                    remove_pending_output();
-                    std::_Exit(1);
-                }
-            }
-            // --qv: the draft and the polished text of every contig of the batch go to the k-mer set in one query on context 0
-            int qrc = qv_on ? hypo_gpu_use_device(0) : HYPO_OK;
-            // --kmer-guard: the batch's records are made first, their clusters judged by the set, and every contig is written as
-            // its draft with the accepted records applied
-            if (guard_on) {
-                VcfStats unused;
-                const int grc = guard.run_batch(_contigs, initial_cid, final_cid, *edits, edit_fn ? vstats : unused,
-                    [&](uint32_t c, const std::string& draft, const std::string& text, const VcfContigRecords& recs, const std::vector<uint8_t>& rejected) {
-                        ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;
-                        if (edit_fn) vcf_write_records(vfile, *_contigs[c], recs, &rejected);
-                        _contigs[c]->release_after_output();
-                        return qv_on ? qv.push(c, draft, text) : HYPO_OK;
-                    });
-                if (grc == HYPO_OK && qv_on) qrc = qv.flush();
-                if (grc != HYPO_OK || qrc != HYPO_OK) {
-                    std::fprintf(stderr, "[Hypo::Hypo] Error: k-mer %s: %s\n", grc != HYPO_OK ? "guard" : "set query", hypo_gpu_last_error());
-                    std::fflush(nullptr);
-                    remove_pending_output();
-                    std::_Exit(1);
-                }
-                return;
-            }
-            for (uint32_t c = initial_cid; c < final_cid; ++c) {
-                if (qv_on) {
-                    const std::string text = _contigs[c]->polished_text();
-                    ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;      // (operator<<'s bytes)
-                    if (qrc == HYPO_OK) qrc = qv.push(c, _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()), text);
-                } else {
-                    ofile << *_contigs[c];
-                }
-                if (edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, vstats);
-                _contigs[c]->release_after_output();
-            }
-            if (qv_on && qrc == HYPO_OK) qrc = qv.flush();
-            if (qrc != HYPO_OK) {
-                std::fprintf(stderr, "[Hypo::Hypo] Error: k-mer set query: %s\n", hypo_gpu_last_error());
-                std::fflush(nullptr);
-                remove_pending_output();
-                std::_Exit(1);
-            }
-        });
     }
-    _alignment_store.clear();
-    if (long_release.joinable()) long_release.join();
+    hypo_gpu_use_device(0);
+    if (const char* vp = std::getenv("HYPO_DUMP_VOTES"))        // (tests: device votes against the host loops of the reference, counter by counter)
+        if (std::FILE* vf = std::fopen(vp, kind == 0 && b.batch_id == 0 ? "wb" : "ab")) { for (uint32_t c = b.initial_cid; c < b.final_cid; ++c) _contigs[c]->dump_votes(vf, kind); std::fclose(vf); }
+}
 
+void Hypo::kmer_votes(Batch& b) {
+    // N1: the reads go to the device once, now; the support votes are counted there (support_kernel.hip) and the arm kernels
+    // use the same copy later.  --host-arms, an unsorted file or a device error: the reference's host loops, per contig range.
     start();
-    if (writer.joinable()) writer.join();
-    // both files are closed and checked before either takes its name; a VCF that cannot take its name takes the FASTA with it
-    ofile.close();
-    if (!ofile) { std::fprintf(stderr, "[Hypo::Hypo] Error: writing the output file (%s) failed!\n", pending_tmp.c_str()); std::exit(1); }
-    if (edit_fn) {
-        vfile.close();
-        if (!vfile) { std::fprintf(stderr, "[Hypo::Hypo] Error: writing the VCF file (%s) failed!\n", pending_vcf_tmp.c_str()); std::exit(1); }
+    // --require-device / HYPO_REQUIRE_DEVICE=1: a stage that was meant for the device and is about to run in the host loops ends
+    // the run instead (the Info lines of DeviceArms say why it did not run there).  Not with --host-arms / HYPO_HOST_SUPPORT,
+    // which ask for the host loops.
+    b.require_device = (_cFlags.require_device || (std::getenv("HYPO_REQUIRE_DEVICE") && std::atoi(std::getenv("HYPO_REQUIRE_DEVICE")) != 0)) &&
+                       !_cFlags.host_arms && !std::getenv("HYPO_HOST_SUPPORT");
+    b.votes_dev.assign((size_t)_n_ctx, 0);
+    if (!_cFlags.host_arms && !std::getenv("HYPO_HOST_SUPPORT"))
+        for (int d = 0; d < _n_ctx; ++d) {
+            const uint32_t c0 = b.work[(size_t)d].c0, c1 = b.work[(size_t)d].c1;
+            if (c0 < c1) b.votes_dev[(size_t)d] = _device_arms[(size_t)d]->upload_reads(_contigs, c0, c1, _reads) ? 1 : 0;
+            if (c0 < c1 && b.work[(size_t)d].piece && !b.votes_dev[(size_t)d]) piece_failed(b, d, "the upload of the reads");
+        }
+    support_votes(b, "the k-mer support votes", 0, [this](DeviceArms& da, uint32_t c0, uint32_t c1) { return da.support_kmers(_contigs, c0, c1, _cFlags.k); },
+                  [this](Alignment& a, Contig& ctg) { a.update_solidkmers_support(_cFlags.k, ctg); });
+    stop("[Hypo:Hypo]: Solid kmers support update. ");
+}
+
+// many contigs: one contig per thread as in the reference; fewer contigs than threads: the contigs side by side, each
+// with its share of the threads for the minimizers of its mega-windows or for building its Window objects (a nested team; -p 10
+// on 64 threads took 45 ms per batch one contig after the other)
+template <class F> void Hypo::contigs_side_by_side(const Batch& b, F per_contig) {
+    const int nc = (int)b.n_contigs(), T = (int)_cFlags.threads;
+    const int outer = std::max(1, std::min(nc, T)), inner = b.over_contigs ? 1 : std::max(1, T / outer);
+    if (inner > 1) omp_set_max_active_levels(2);
+#pragma omp parallel for schedule(static, 1) num_threads(outer)
+    for (int64_t i = b.initial_cid; i < (int64_t)b.final_cid; ++i) {
+        omp_set_num_threads(inner);
+        per_contig(*_contigs[(size_t)i]);
     }
+    omp_set_max_active_levels(1);
+}
+
+void Hypo::prepare_division(Batch& b) {
+    start();
+    contigs_side_by_side(b, [this](Contig& ctg) { ctg.prepare_for_division(_cFlags.k); });
+    uint64_t num_sr = 0, len_sr = 0;
+    for (uint32_t i = b.initial_cid; i < b.final_cid; ++i) { num_sr += _contigs[i]->get_num_sr(); len_sr += _contigs[i]->get_len_sr(); }
+    std::fprintf(stdout, "[Hypo::Hypo] Info: Total number of SR: %lu; Total length of SR: %lu\n", (unsigned long)num_sr, (unsigned long)len_sr);
+    stop("[Hypo:Hypo]: Finding SR (and preparing for division). ");
+}
+
+void Hypo::minimizer_votes(Batch& b) {
+    start();
+    support_votes(b, "the minimizer support votes", 1, [this](DeviceArms& da, uint32_t c0, uint32_t c1) { return da.support_minimizers(_contigs, c0, c1); },
+                  [](Alignment& a, Contig& ctg) { a.update_minimisers_support(ctg); });
+    stop("[Hypo:Hypo]: Minimisers support update. ");
+}
+
+void Hypo::divide(Batch& b) {
+    start();
+    contigs_side_by_side(b, [](Contig& ctg) { ctg.divide_into_regions(); });
+    stop("[Hypo:Hypo]: Division into windows. ");
+}
+
+// The halo of a piece was chosen before the division: a window longer than it (a weak region force_divide could not cut) would lose
+// the arms of the reads beyond it — the span grows to the longest window this context owns and its reads go over again.  For the
+// long arms likewise, once the LONG pseudo-windows exist.
+void Hypo::widen_piece_halo(int d, const Contig& ctg, bool long_windows) {
+    DeviceArms& da = *_device_arms[(size_t)d];
+    const uint32_t longest = da.longest_owned_window(ctg, long_windows);
+    if (da.widen_halo(longest + 64))
+        std::fprintf(stdout, long_windows ? "[Hypo::Hypo] Info: context %d owns a LONG window of %u bases: halo widened to %u\n"
+                                          : "[Hypo::Hypo] Info: context %d owns a window of %u bases: halo widened to %u, its reads are uploaded again\n", d, longest, da.halo());
+}
+
+void Hypo::cut_short_arms(Batch& b) {
+    const uint32_t initial_cid = b.initial_cid, final_cid = b.final_cid;
+    start();
+    // The device cuts the reads into arms, prunes the windows and keeps the window batch in its memory (DeviceArms.hpp);
+    // --host-arms, several devices or an unsorted alignment file take the host loops of the reference instead.
+    b.on_dev.assign(b.n_contigs(), 0);
+    b.long_dev.assign(b.n_contigs(), 0);
+    if (!_cFlags.host_arms) {
+        for (int d = 0; d < _n_ctx; ++d) {
+            const uint32_t c0 = b.work[(size_t)d].c0, c1 = b.work[(size_t)d].c1;
+            if (c0 >= c1) continue;
+            if (b.work[(size_t)d].piece) widen_piece_halo(d, *_contigs[c0], false);
+            if (_device_arms[(size_t)d]->build(_contigs, c0, c1, _reads, _cFlags.k))
+                for (uint32_t c = c0; c < c1; ++c) b.on_dev[c - initial_cid] = 1;
+            else if (b.work[(size_t)d].piece) piece_failed(b, d, "short-arm selection");
+        }
+        for (int d = 0; d < _n_ctx; ++d) if (b.work[(size_t)d].piece) DeviceArms::finish_short(_contigs, b.work[(size_t)d].c0, b.work[(size_t)d].c1);
+        hypo_gpu_use_device(0);
+    }
+    for (uint32_t cid = initial_cid; cid < final_cid; ++cid) {
+        if (b.on_dev[cid - initial_cid]) { _alignment_store[cid].clear(); continue; }       // (objects a host vote loop had asked for)
+        if (!_cFlags.host_arms && _reads.count(cid) > 0) host_fallback(b, "short-arm selection");
+        materialize_alignments(b, cid, cid + 1);
+        auto& alns = _alignment_store[cid];
+#pragma omp parallel for
+        for (int64_t t = 0; t < (int64_t)alns.size(); ++t) alns[(size_t)t]->find_short_arms(_cFlags.k, *_contigs[cid]);
+    }
+    stop("[Hypo:Hypo]: Short arms computing. ");
+    start();
+    // few contigs: the parallelism is inside a contig (window ranges); many contigs: one contig per thread as in the reference
+#pragma omp parallel for schedule(static, 1) if (b.over_contigs)
+    for (int64_t i = initial_cid; i < (int64_t)final_cid; ++i) {
+        if (b.on_dev[(size_t)i - initial_cid]) continue;
+        _contigs[(size_t)i]->fill_short_windows(_alignment_store[(size_t)i]); _alignment_store[(size_t)i].clear();
+    }
+    {   // the batch's short reads are spent; what it consumed for contigs of later batches stays for them (src/Hypo.cpp:314-325)
+        ReadBatch later;
+        later.reset(_contigs.size());
+        _reads.carry_beyond(final_cid, later);
+        _reads.clear(&_block_pool, &_pool_mu);
+        _reads.reset(_contigs.size());
+        _reads.append(later);
+    }
+    stop("[Hypo:Hypo]: Short arms filling. ");
+}
+
+void Hypo::cut_long_arms(Batch& b) {
+    const uint32_t initial_cid = b.initial_cid, final_cid = b.final_cid;
+    start();
+    // the long reads of the batch, flat like the short ones (ReadBatch.hpp; round 4: 1.2 M objects of 8 kb each took 2.5 s to
+    // build on the 250 Mbp set).  The reader stops behind the first kept record of a later contig; the reference files that
+    // record in ITS contig's store entry (src/Hypo.cpp:314-325), where that batch's short-read phases find it: it becomes
+    // an object there (see Hypo::load_reads).
+    if (b.long_prefetch.joinable()) b.long_prefetch.join();
+    else { _reads_long.reset(_contigs.size()); create_alignments_flat(b.batch_id, _reads_long, false); }
+    if (_rs_long.carry_blk) {
+        ReadBatch one;
+        one.reset(_contigs.size());
+        one.add(_rs_long.carry_blk, _rs_long.carry_r0, _rs_long.carry_r1);
+        if (_rs_long.carry_cid >= 0) one.materialize((uint32_t)_rs_long.carry_cid, _alignment_store[(size_t)_rs_long.carry_cid]);
+        _rs_long.carry_blk.reset();
+    }
+    stop("[Hypo:Hypo]: Loaded alignments of Long reads. ");
+    start();
+    const auto tl0 = std::chrono::steady_clock::now();
+#pragma omp parallel for schedule(static, 1)
+    for (int64_t i = initial_cid; i < (int64_t)final_cid; ++i) _contigs[(size_t)i]->prepare_long_windows();
+    const auto tl1 = std::chrono::steady_clock::now();
+    // the long reads are cut into arms, filtered (Filter::is_good) and kept as a second resident batch by the context that
+    // holds the contig's short arms; --host-arms, an unsorted file or a device error take the reference's host loops
+    std::vector<char> long_on_dev(b.n_contigs(), 0);
+    if (!_cFlags.host_arms) {
+        for (int d = 0; d < _n_ctx; ++d) {
+            const uint32_t c0 = b.work[(size_t)d].c0, c1 = b.work[(size_t)d].c1;
+            if (c0 >= c1) continue;
+            if (b.work[(size_t)d].piece) widen_piece_halo(d, *_contigs[c0], true);
+            if (_device_arms[(size_t)d]->build_long(_contigs, c0, c1, _reads_long))
+                for (uint32_t c = c0; c < c1; ++c) long_on_dev[c - initial_cid] |= 1;
+            else {
+                if (_device_arms[(size_t)d]->long_failed()) host_fallback(b, "long-arm selection");
+                if (b.work[(size_t)d].piece) long_on_dev[c0 - initial_cid] |= 2;      // (a shared contig: all of its contexts or none)
+            }
+        }
+        for (int d = 0; d < _n_ctx; ++d) {
+            if (!b.work[(size_t)d].piece) continue;
+            const uint32_t c = b.work[(size_t)d].c0;
+            if (long_on_dev[c - initial_cid] & 2) _device_arms[(size_t)d]->drop_long();
+        }
+        for (uint32_t c = initial_cid; c < final_cid; ++c) {
+            char& f = long_on_dev[c - initial_cid];
+            const bool shared = f != 0 && b.n_contigs() < (uint32_t)_n_ctx;
+            if (f & 2) f = 0;
+            else if (f == 1 && shared) DeviceArms::finish_long(_contigs, c, c + 1);
+        }
+        hypo_gpu_use_device(0);
+    }
+    for (uint32_t cid = initial_cid; cid < final_cid; ++cid) {
+        if (long_on_dev[cid - initial_cid]) continue;
+        auto& alns = _alignment_store[cid];                     // (the host loops of the reference read objects)
+        _reads_long.materialize(cid, alns);
+#pragma omp parallel for
+        for (int64_t t = 0; t < (int64_t)alns.size(); ++t) alns[(size_t)t]->find_long_arms(*_contigs[cid]);
+    }
+#pragma omp parallel for schedule(static, 1) if (b.over_contigs)
+    for (int64_t i = initial_cid; i < (int64_t)final_cid; ++i) {
+        if (long_on_dev[(size_t)i - initial_cid]) continue;
+        _contigs[(size_t)i]->fill_long_windows(_alignment_store[(size_t)i]); _alignment_store[(size_t)i].clear();
+    }
+    for (uint32_t c = initial_cid; c < final_cid; ++c) b.long_dev[c - initial_cid] = long_on_dev[c - initial_cid];
+    const auto tl2 = std::chrono::steady_clock::now();
+    // (7 GB of parsed long reads on the 250 Mbp set: handed back behind the POA, not in front of it)
+    if (_long_release.joinable()) _long_release.join();
+    _long_release = std::thread([this, spent = std::make_shared<ReadBatch>(std::move(_reads_long))] { spent->clear(&_block_pool, &_pool_mu); });
+    _reads_long = ReadBatch();
+    if (std::getenv("HYPO_HOST_TIMING")) {
+        auto sec = [](std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double>(b - a).count(); };
+        std::fprintf(stderr, "[timing] long arms: prepare_long_windows %.3f s, arms %.3f s, long reads released %.3f s\n", sec(tl0, tl1), sec(tl1, tl2), sec(tl2, std::chrono::steady_clock::now()));
+    }
+    stop("[Hypo:Hypo]: Long arms filling. ");
+}
+
+// ---- POA: every valid window of the contig batch in one device call (reference: per-window OpenMP loop) ----
+void Hypo::run_poa(Batch& b) {
+    const uint32_t initial_cid = b.initial_cid, final_cid = b.final_cid;
+    start();
+    Window::prepare_for_poa(_cFlags.score_params, _cFlags.threads);
+    std::vector<Window*> wins;
+    for (uint32_t i = initial_cid; i < final_cid; ++i)
+        for (uint64_t w = 0; w < _contigs[i]->get_num_regions(); ++w)
+            if (_contigs[i]->is_valid_window((uint32_t)w)) {
+                const bool lw = _contigs[i]->window((uint32_t)w)->is_long();
+                if (!(lw ? b.long_dev[i - initial_cid] : b.on_dev[i - initial_cid])) wins.push_back(_contigs[i]->window((uint32_t)w));
+            }
+    uint64_t n_resident = 0;
+    {   // the resident batches: every context polishes its own, side by side; what needs the host's retry path joins `wins`
+        std::vector<std::vector<Window*>> retry((size_t)_n_ctx);
+        std::vector<int> prc((size_t)_n_ctx, HYPO_OK);
+        std::vector<std::string> perr((size_t)_n_ctx);
+        std::vector<std::thread> th;
+        for (int d = 0; d < _n_ctx; ++d) {
+            DeviceArms& da = *_device_arms[(size_t)d];
+            da.reset_polished();
+            if (!da.active() && !da.active_long()) continue;
+
+            auto job = [&, d] {
+                DeviceArms& me = *_device_arms[(size_t)d];
+                prc[(size_t)d] = me.polish(_cFlags.score_params, _dump.is_open(), &retry[(size_t)d]);
+                if (prc[(size_t)d] == HYPO_OK) prc[(size_t)d] = me.polish_long(_cFlags.score_params, _dump.is_open(), &retry[(size_t)d]);
+                if (prc[(size_t)d] != HYPO_OK) perr[(size_t)d] = hypo_gpu_last_error();
+            };
+            if (_n_ctx == 1) job(); else th.emplace_back(job);
+        }
+        for (auto& t : th) t.join();
+        for (int d = 0; d < _n_ctx; ++d) n_resident += _device_arms[(size_t)d]->polished_windows();      // (windows a context owns: its halo's are another's)
+        hypo_gpu_use_device(0);
+        for (int d = 0; d < _n_ctx; ++d) {
+            if (prc[(size_t)d] != HYPO_OK) { std::fprintf(stderr, "[Hypo::Window] Error: %s\n", perr[(size_t)d].c_str()); std::exit(1); }
+            wins.insert(wins.end(), retry[(size_t)d].begin(), retry[(size_t)d].end());
+        }
+    }
+    if (Window::generate_consensus_batch(wins) != HYPO_OK) { std::fprintf(stderr, "[Hypo::Window] Error: %s\n", hypo_gpu_last_error()); std::exit(1); }
+    std::fprintf(stdout, "[Hypo::Hypo] Info: polished windows (Batch %u): %lu\n", b.batch_id, (unsigned long)(wins.size() + n_resident));
+    stop("[Hypo:Hypo]: POA of windows. ");
+}
+
+void Hypo::dump_regions(const Batch& batch) {
+    for (uint32_t i = batch.initial_cid; i < batch.final_cid; ++i)
+        for (uint64_t w = 0; w < _contigs[i]->get_num_regions(); ++w) {
+            uint32_t b, e; RegionType t;
+            _contigs[i]->region((uint32_t)w, b, e, t);
+            const Window* win = _contigs[i]->window((uint32_t)w);
+            if (!win && t != RegionType::SR && t != RegionType::MSR && !_cFlags.lr_bam_filename.empty()) continue;   // swallowed by a LONG window
+            if (win) e = b + (uint32_t)win->get_window_len();           // a LONG window spans the arm-less regions that follow it
+            _dump << _contigs[i]->get_name() << '\t' << b << '\t' << e << '\t' << region_name(t);
+            if (win) _dump << '\t' << win->dump_counts() << '\t' << win->arms_crc32() << '\t' << win->get_consensus();
+            if (win && std::getenv("HYPO_REGION_DUMP_ARMS")) _dump << '\t' << (win->is_long() ? "L" : "S") << '\t' << win->dump_text();
+            else if (t != RegionType::SR && t != RegionType::MSR) _dump << "\t0\t0\t0\t0\t0\t" << _contigs[i]->draft_segment(b, e);   // no arms: draft kept
+            _dump << '\n';
+        }
+}
+
+// the writer thread: one batch's contigs go to the FASTA (and the VCF, and the k-mer set's query) while the next batch is processed
+void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
+    const uint32_t initial_cid = job.initial_cid, final_cid = job.final_cid;
+    std::ofstream& ofile = out.fasta();
+    std::ofstream& vfile = out.vcf();
+    omp_set_num_threads(std::max(1, std::min((int)_cFlags.threads, 8)));
+    std::unique_ptr<EditBatchResult> edits;
+    if (ex.edit_fn || ex.guard_on) {
+        edits.reset(new EditBatchResult());
+        if (hypo_gpu_use_device(0) != HYPO_OK || edit_scripts_for(ex.guard_on ? ex.guard_edit_fn : ex.edit_fn, _contigs, initial_cid, final_cid, *edits) != HYPO_OK)
+            writer_fatal("edit scripts");
+    }
+    // --qv: the draft and the polished text of every contig of the batch go to the k-mer set in one query on context 0
+    int qrc = ex.qv_on ? hypo_gpu_use_device(0) : HYPO_OK;
+    // --kmer-guard: the batch's records are made first, their clusters judged by the set, and every contig is written as
+    // its draft with the accepted records applied
+    if (ex.guard_on) {
+        VcfStats unused;
+        const int grc = ex.guard.run_batch(_contigs, initial_cid, final_cid, *edits, ex.edit_fn ? ex.vstats : unused,
+            [&](uint32_t c, const std::string& draft, const std::string& text, const VcfContigRecords& recs, const std::vector<uint8_t>& rejected) {
+                ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;
+                if (ex.edit_fn) vcf_write_records(vfile, *_contigs[c], recs, &rejected);
+                _contigs[c]->release_after_output();
+                return ex.qv_on ? ex.qv.push(c, draft, text) : HYPO_OK;
+            });
+        if (grc == HYPO_OK && ex.qv_on) qrc = ex.qv.flush();
+        if (grc != HYPO_OK || qrc != HYPO_OK) writer_fatal(grc != HYPO_OK ? "k-mer guard" : "k-mer set query");
+        return;
+    }
+    for (uint32_t c = initial_cid; c < final_cid; ++c) {
+        if (ex.qv_on) {
+            const std::string text = _contigs[c]->polished_text();
+            ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;      // (operator<<'s bytes)
+            if (qrc == HYPO_OK) qrc = ex.qv.push(c, _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()), text);
+        } else {
+            ofile << *_contigs[c];
+        }
+        if (edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, ex.vstats);
+        _contigs[c]->release_after_output();
+    }
+    if (ex.qv_on && qrc == HYPO_OK) qrc = ex.qv.flush();
+    if (qrc != HYPO_OK) writer_fatal("k-mer set query");
+}
+
+// ---- once per run, behind the batches ---------------------------------------------------------------------------------------
+void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
+    start();
+    if (_writer.joinable()) _writer.join();
     // --qv: the table is formatted once, closed and checked like the others; the set has answered its last query
-    if (set_on) qv.end();
-    if (qv_on) {
-        pending_qv_tmp = _cFlags.qv_filename + ".tmp";
-        std::ofstream qfile(pending_qv_tmp);
-        if (!qfile.is_open()) { std::fprintf(stderr, "[Hypo::Hypo] Error: File open error: QV File (%s) could not be opened!\n", pending_qv_tmp.c_str()); std::exit(1); }
+    if (ex.set_on) ex.qv.end();
+    if (ex.qv_on) {
         std::vector<std::string> names;
         for (const auto& c : _contigs) names.push_back(c->get_name());
-        qv.write(qfile, names);
-        qfile.close();
-        if (!qfile) { std::fprintf(stderr, "[Hypo::Hypo] Error: writing the QV file (%s) failed!\n", pending_qv_tmp.c_str()); std::exit(1); }
+        ex.qv.write(out.open_qv(_cFlags.qv_filename), names);
     }
-    if (std::rename(pending_tmp.c_str(), _cFlags.output_filename.c_str()) != 0) {
-        std::fprintf(stderr, "[Hypo::Hypo] Error: could not move %s to %s!\n", pending_tmp.c_str(), _cFlags.output_filename.c_str());
-        std::exit(1);
-    }
-    pending_tmp.clear();
-    if (guard_on)
-        std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer guard (k = %u): %llu clusters of %llu records, %llu clusters (%llu records) rejected\n", guard.k(),
-                     (unsigned long long)guard.stats().clusters, (unsigned long long)guard.stats().records, (unsigned long long)guard.stats().rejected_clusters,
-                     (unsigned long long)guard.stats().rejected_records);
-    if (edit_fn) {
-        if (std::rename(pending_vcf_tmp.c_str(), _cFlags.vcf_filename.c_str()) != 0) {
-            std::fprintf(stderr, "[Hypo::Hypo] Error: could not move %s to %s!\n", pending_vcf_tmp.c_str(), _cFlags.vcf_filename.c_str());
-            std::remove(_cFlags.output_filename.c_str());
-            std::exit(1);
-        }
-        pending_vcf_tmp.clear();
-        std::fprintf(stdout, "[Hypo::Hypo] Info: VCF %s: %llu records, %llu substituted, %llu inserted, %llu deleted bases\n", _cFlags.vcf_filename.c_str(),
-                     (unsigned long long)vstats.records, (unsigned long long)vstats.sub, (unsigned long long)vstats.ins, (unsigned long long)vstats.del);
-    }
-    if (qv_on) {
-        if (std::rename(pending_qv_tmp.c_str(), _cFlags.qv_filename.c_str()) != 0) {
-            std::fprintf(stderr, "[Hypo::Hypo] Error: could not move %s to %s!\n", pending_qv_tmp.c_str(), _cFlags.qv_filename.c_str());
-            std::remove(_cFlags.output_filename.c_str());
-            if (edit_fn) std::remove(_cFlags.vcf_filename.c_str());
-            std::exit(1);
-        }
-        pending_qv_tmp.clear();
-        std::fprintf(stdout, "[Hypo::Hypo] Info: QV %s (k = %u, %llu distinct read k-mers): draft %s, polished %s\n", _cFlags.qv_filename.c_str(), qv.k(),
-                     (unsigned long long)qv.n_distinct(), qv.draft_qv().c_str(), qv.polished_qv().c_str());
-    }
+    out.commit([&](RunOutputs::Which w) {
+        if (w == RunOutputs::FASTA && ex.guard_on)
+            std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer guard (k = %u): %llu clusters of %llu records, %llu clusters (%llu records) rejected\n", ex.guard.k(),
+                         (unsigned long long)ex.guard.stats().clusters, (unsigned long long)ex.guard.stats().records, (unsigned long long)ex.guard.stats().rejected_clusters,
+                         (unsigned long long)ex.guard.stats().rejected_records);
+        if (w == RunOutputs::VCF)
+            std::fprintf(stdout, "[Hypo::Hypo] Info: VCF %s: %llu records, %llu substituted, %llu inserted, %llu deleted bases\n", _cFlags.vcf_filename.c_str(),
+                         (unsigned long long)ex.vstats.records, (unsigned long long)ex.vstats.sub, (unsigned long long)ex.vstats.ins, (unsigned long long)ex.vstats.del);
+        if (w == RunOutputs::QV)
+            std::fprintf(stdout, "[Hypo::Hypo] Info: QV %s (k = %u, %llu distinct read k-mers): draft %s, polished %s\n", _cFlags.qv_filename.c_str(), ex.qv.k(),
+                         (unsigned long long)ex.qv.n_distinct(), ex.qv.draft_qv().c_str(), ex.qv.polished_qv().c_str());
+    });
     stop("[Hypo:Hypo]: Writing results. ");
-    _times.overall = std::chrono::duration<double>(std::chrono::steady_clock::now() - _tstart).count();
-    std::fprintf(stdout, "RESOURCES ([Hypo:Hypo]: Overall. ): TIME= %g sec.\n", _times.overall);
-    if (std::getenv("HYPO_STAGE_COUNTERS"))
-        std::fprintf(stdout, "[Hypo::Hypo] Info: stage counters: solid k-mers accepted with 40-80 %% support %llu, refused after another such k-mer %llu; force_divide calls %llu; "
-                             "minimizers dropped as recurring %llu, as poly-base %llu\n", (unsigned long long)g_stage_counters[0].load(), (unsigned long long)g_stage_counters[1].load(),
-                     (unsigned long long)g_stage_counters[2].load(), (unsigned long long)g_stage_counters[3].load(), (unsigned long long)g_stage_counters[4].load());
-    // (1.5 M windows with their arms and consensus strings: freed contig by contig on all threads, 0.37 s of the C3 run's wall otherwise)
-#pragma omp parallel for schedule(dynamic, 1)
-    for (int64_t i = 0; i < (int64_t)_contigs.size(); ++i) _contigs[(size_t)i].reset();
-    _contigs.clear();
 }
 
 // ---- the flat path of the short reads (ReadBatch.hpp) -------------------------------------------------------------------------
-void Hypo::materialize_alignments(uint32_t c0, uint32_t c1, std::vector<char>& done) {
-    // `done` belongs to the batch in hand: entry i = contig (_mat_base + i), _mat_base = the batch's first contig
+void Hypo::materialize_alignments(Batch& b, uint32_t c0, uint32_t c1) {
     for (uint32_t c = c0; c < c1; ++c) {
-        char& d = done[c - _mat_base];
+        char& d = b.materialized[c - b.initial_cid];
         if (d) continue;
         d = 1;
         _reads.materialize(c, _alignment_store[c]);
@@ -896,7 +863,7 @@ void Hypo::create_alignments_flat(uint32_t batch_id, ReadBatch& into, bool is_sr
                 // (this may be the helper thread, with the main thread inside a device call: leave without running the static
                 // destructors under it)
                 std::fflush(nullptr);
-                remove_pending_output();
+                RunOutputs::discard();
                 std::_Exit(1);
             }
             if (st == ParsedBlock::ST_KEPT) ++num_alns; else ++num_invalid;

@@ -1,10 +1,15 @@
 // Hypo.hpp — host mirror of hypo::Hypo (reference: include/Hypo.hpp:37-58, src/Hypo.cpp:37-329): phase sequencing of
-// one polishing run.  Same phases and log labels; the two hot-path phases call the MI355X through the C-ABI:
-// "Found Solid pos in contigs" (Contig::find_solid_pos -> hypo_gpu_solid_scan) and "POA of windows"
-// (all valid windows of a contig batch in ONE Window::generate_consensus_batch call).
+// one polishing run.  Same phases and log labels; polish() is the list of them.  Once per run: the solid k-mers (built from
+// the short reads on the device, or loaded), the contigs, their solid positions (Contig::find_solid_pos -> hypo_gpu_solid_scan),
+// the result files.  Per contig batch: the reads are loaded and dealt out to the device contexts (CtxPlan.hpp), the k-mer and
+// minimizer support votes are counted and the short and long arms cut on the device (DeviceArms) or by the reference's host
+// loops, every valid window is polished ("POA of windows": the resident batches per context, the rest in ONE
+// Window::generate_consensus_batch call), and a writer thread files the batch beside the next one.  Then the result files
+// take their names (RunOutputs.hpp).
 #pragma once
 #include <chrono>
 #include <condition_variable>
+#include <fstream>
 #include <memory>
 #include <mutex>
 #include <thread>
@@ -13,11 +18,18 @@
 #include <vector>
 #include "Alignment.hpp"
 #include "Contig.hpp"
+#include "CtxPlan.hpp"
+#include "DeviceArms.hpp"
 #include "ReadBatch.hpp"
 #include "SeqIO.hpp"
 #include "Settings.hpp"
 
 namespace hypo {
+
+class RunOutputs;
+struct Extras;           // run-wide optional outputs: --vcf, --qv, --kmer-guard (Hypo.cpp)
+struct Batch;            // the contig batch in hand (Hypo.cpp)
+struct WriterJob { uint32_t initial_cid = 0, final_cid = 0; };      // what the writer thread is given by value: the contigs to file
 
 struct PhaseTimes { std::vector<std::pair<std::string, double>> phases; double overall = 0; };
 
@@ -92,9 +104,44 @@ private:
     void create_alignments_flat(uint32_t batch_id, ReadBatch& into, bool is_sr = true);
     // long_reads: the normalised-edit-distance filter of the long-read constructor applies (src/Alignment.cpp:51-58)
     void parse_block(const SamReader& sf, const SamReader::RecordBlock& raw, ParsedBlock& blk, bool long_reads);
-    // Alignment objects of contigs [c0, c1) from _reads into _alignment_store (the host loops of the reference read those)
-    void materialize_alignments(uint32_t c0, uint32_t c1, std::vector<char>& done);
-    uint32_t _mat_base = 0;
+    // Alignment objects of contigs [c0, c1) of the batch from _reads into _alignment_store (the host loops of the reference read those)
+    void materialize_alignments(Batch& b, uint32_t c0, uint32_t c1);
+
+    // ---- polish(), phase by phase ----
+    // run-wide state: the teams beside the main thread, the helper threads and what they fill, one DeviceArms per device context
+    uint32_t _num_batches = 0;
+    int _inflate_threads = 1, _helper_threads = 1, _n_ctx = 1;
+    bool _prefetch_on = true;
+    std::thread _prefetch, _long_release, _writer;
+    ReadBatch _staged;                       // the next batch's short reads while the helper parses them
+    std::vector<std::unique_ptr<DeviceArms>> _device_arms;
+    std::ofstream _dump;
+    // once per run
+    void bind_extras(Extras& ex);
+    void solid_kmers(Extras& ex, std::ofstream& stagefile, SolidKmers& sk);
+    void load_contigs();
+    void start_readers();
+    void scan_solid_positions(const SolidKmers& sk);
+    void open_outputs(Extras& ex, RunOutputs& out);
+    // per batch
+    void load_reads(Batch& b);
+    void plan_batch(Batch& b);
+    void kmer_votes(Batch& b);
+    void prepare_division(Batch& b);
+    void minimizer_votes(Batch& b);
+    void divide(Batch& b);
+    void cut_short_arms(Batch& b);
+    void cut_long_arms(Batch& b);
+    void run_poa(Batch& b);
+    void dump_regions(const Batch& batch);
+    void write_batch(WriterJob job, Extras& ex, RunOutputs& out);          // (the writer thread)
+    // once more per run
+    void commit_outputs(Extras& ex, RunOutputs& out);
+    // what the phases share
+    [[noreturn]] void piece_failed(const Batch& b, int d, const char* what);
+    template <class F> void contigs_side_by_side(const Batch& b, F per_contig);
+    template <class Dev, class Host> void support_votes(Batch& b, const char* what, int kind, Dev on_device, Host per_alignment);
+    void widen_piece_halo(int d, const Contig& ctg, bool long_windows);
 };
 
 }  // namespace hypo

@@ -8,6 +8,7 @@
 #include "Contig.hpp"
 #include "Window.hpp"
 #include "SolidBuild.hpp"
+#include "CtxPlan.hpp"
 
 using namespace hypo;
 
@@ -131,6 +132,15 @@ int hypo_host_solid_build(const char* const* paths, int n, uint32_t k, uint32_t 
     counts[0] = st.n_bits; counts[1] = st.n_canonical; counts[2] = st.seq_bytes; counts[3] = st.file_bytes;
     times[0] = st.parse_s; times[1] = st.count_s; times[2] = st.hist_s; times[3] = st.fill_s; times[4] = st.total_s;
     return rc;
+}
+
+// plan_contexts (CtxPlan.hpp): which context works on which contigs of the batch [initial_cid, final_cid); n_reads and contig_len per
+// contig of the batch.  out: {c0, c1, piece, own0, own1} per context
+int hypo_host_plan_contexts(uint32_t initial_cid, uint32_t final_cid, int n_ctx, const uint64_t* n_reads, const uint32_t* contig_len,
+                            int split_batch, int allow_pieces, uint32_t* out) {
+    const std::vector<hypo::CtxWork> work = hypo::plan_contexts(initial_cid, final_cid, n_ctx, n_reads, contig_len, split_batch != 0, allow_pieces != 0);
+    for (const hypo::CtxWork& w : work) { *out++ = w.c0; *out++ = w.c1; *out++ = w.piece ? 1 : 0; *out++ = w.own0; *out++ = w.own1; }
+    return 0;
 }
 
 }  // extern "C"

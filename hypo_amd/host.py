@@ -77,3 +77,15 @@ class HostMirror:
             raise RuntimeError(f"hypo_host_contig_scan rc={rc}")
         n = int(ns.value)
         return n, kids[:n], ra[:rq.size], sa[:sq.size]
+
+    def plan_contexts(self, initial_cid, final_cid, n_ctx, n_reads, contig_len, split_batch, allow_pieces):
+        """[(c0, c1, piece, own0, own1)] per device context: how Hypo::polish deals the contigs [initial_cid, final_cid) of a batch out
+        (host/CtxPlan.hpp); n_reads and contig_len per contig of the batch"""
+        nr = np.asarray(n_reads, dtype=np.uint64)
+        cl = np.asarray(contig_len, dtype=np.uint32)
+        assert nr.size == cl.size == final_cid - initial_cid and n_ctx >= 1
+        out = np.zeros(5 * n_ctx, dtype=np.uint32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        self.lib.hypo_host_plan_contexts(C.c_uint32(initial_cid), C.c_uint32(final_cid), C.c_int(n_ctx), p(nr), p(cl),
+                                         C.c_int(1 if split_batch else 0), C.c_int(1 if allow_pieces else 0), p(out))
+        return [(int(r[0]), int(r[1]), bool(r[2]), int(r[3]), int(r[4])) for r in out.reshape(n_ctx, 5)]
