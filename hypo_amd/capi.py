@@ -30,9 +30,10 @@ EXPORTS = [
     "hypo_gpu_kmer_count_begin", "hypo_gpu_kmer_count_add", "hypo_gpu_kmer_histogram", "hypo_gpu_solid_set_build",
     "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts",
     "hypo_gpu_kset_begin", "hypo_gpu_kset_add", "hypo_gpu_kset_size", "hypo_gpu_kset_query", "hypo_gpu_kset_end",
-    "hypo_gpu_kset_query_spans",
+    "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants",
 ]
 KSET_SPAN_PIECE = 2048        # windows per piece of a long span (kset_kernel.hpp)
+KSET_MAX_EDITS = 12           # edits of a site of hypo_gpu_kset_query_variants (HYPO_KSET_MAX_EDITS)
 
 
 class HypoGpuError(RuntimeError):
@@ -304,6 +305,38 @@ class HypoGpu:
         rc, total, missing = self.kset_query_spans_rc(data, lo, hi)
         self._check(rc)
         return total, missing
+
+    def kset_query_variants_rc(self, data, alts, lo, hi, edit_off, eb, ee, ao, al, variants=True):
+        """(return code, best_mask u32[n], best_total u64[n], best_missing u64[n], var_total, var_missing) of
+        hypo_gpu_kset_query_variants; nothing is checked here.  var_*: u64[sum of 2^edits] as far as edit_off is sane, None
+        without `variants`."""
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        b = np.frombuffer(bytes(alts), dtype=np.uint8) if not isinstance(alts, np.ndarray) else np.ascontiguousarray(alts, dtype=np.uint8)
+        lo, hi = np.ascontiguousarray(lo, dtype=np.uint64), np.ascontiguousarray(hi, dtype=np.uint64)
+        edit_off = np.ascontiguousarray(edit_off, dtype=np.uint32)
+        eb, ee, ao = (np.ascontiguousarray(x, dtype=np.uint64) for x in (eb, ee, ao))
+        al = np.ascontiguousarray(al, dtype=np.uint32)
+        n = lo.size
+        assert hi.size == n and edit_off.size == n + 1
+        pad = lambda x, t: np.concatenate([x, np.zeros(1, t)])          # (an empty array still has an address)
+        n_edits = np.diff(edit_off.astype(np.int64))
+        n_vars = int(sum(1 << int(e) for e in n_edits if 0 <= e <= 16))
+        best_mask, best_total, best_missing = np.zeros(n + 1, np.uint32), np.zeros(n + 1, np.uint64), np.zeros(n + 1, np.uint64)
+        var_total = np.zeros(n_vars + 1, np.uint64) if variants else None
+        var_missing = np.zeros(n_vars + 1, np.uint64) if variants else None
+        rc = int(self.lib.hypo_gpu_kset_query_variants(
+            _p(pad(a, np.uint8)), C.c_uint64(a.size), _p(pad(b, np.uint8)), C.c_uint64(b.size), _p(pad(lo, np.uint64)), _p(pad(hi, np.uint64)), _p(edit_off),
+            C.c_uint32(n), _p(pad(eb, np.uint64)), _p(pad(ee, np.uint64)), _p(pad(ao, np.uint64)), _p(pad(al, np.uint32)), _p(best_mask), _p(best_total),
+            _p(best_missing), _p(var_total) if variants else None, _p(var_missing) if variants else None))
+        return rc, best_mask[:n], best_total[:n], best_missing[:n], (var_total[:n_vars] if variants else None), (var_missing[:n_vars] if variants else None)
+
+    def kset_query_variants(self, data, alts, lo, hi, edit_off, eb, ee, ao, al, variants=True):
+        """site s = data[lo[s]:hi[s]] with the edits edit_off[s] .. edit_off[s + 1] (edit e: data[eb[e]:ee[e]] -> alts[ao[e]:ao[e] + al[e]]).
+        (best_mask, best_total, best_missing, var_total, var_missing): per site the best subset of its edits (fewest missing, most
+        edits, greatest mask), and every subset's pair in site and mask order."""
+        out = self.kset_query_variants_rc(data, alts, lo, hi, edit_off, eb, ee, ao, al, variants)
+        self._check(out[0])
+        return out[1:]
 
     def kset_end(self):
         self._check(self.lib.hypo_gpu_kset_end())

@@ -1288,6 +1288,114 @@ int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_
     return HYPO_OK;
 }
 
+int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char* alts, uint64_t n_alt_bytes, const uint64_t* lo, const uint64_t* hi,
+                                 const uint32_t* edit_off, uint32_t n_sites, const uint64_t* eb, const uint64_t* ee, const uint64_t* ao, const uint32_t* al,
+                                 uint32_t* best_mask, uint64_t* best_total, uint64_t* best_missing, uint64_t* var_total, uint64_t* var_missing) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    Ctx::KSet& ks = g_ctx.ks;
+    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    if (!n_sites) return HYPO_OK;
+    if (!bytes || !lo || !hi || !edit_off || !best_mask || !best_total || !best_missing) return fail(HYPO_E_INVALID, "NULL buffer");
+    // everything is checked before a buffer is touched: the kernels trust what they are given
+    const uint32_t k = ks.k;
+    const uint32_t e_first = edit_off[0];
+    uint64_t n_vars = 0, n_items = 0;
+    for (uint32_t s = 0; s < n_sites; ++s) {
+        if (edit_off[s + 1] < edit_off[s]) return fail(HYPO_E_INVALID, "edit_off[] must not decrease (entry %u)", s + 1);
+        const uint32_t n = edit_off[s + 1] - edit_off[s];
+        if (n > hypo::KSET_MAX_EDITS) return fail(HYPO_E_INVALID, "site %u has %u edits, at most %u (HYPO_KSET_MAX_EDITS)", s, n, hypo::KSET_MAX_EDITS);
+        if (lo[s] > hi[s] || hi[s] > n_bytes) return fail(HYPO_E_INVALID, "site %u = [%llu, %llu) of %llu bytes", s, (unsigned long long)lo[s], (unsigned long long)hi[s], (unsigned long long)n_bytes);
+        if (n && (!eb || !ee || !ao || !al)) return fail(HYPO_E_INVALID, "NULL buffer");
+        uint64_t at = lo[s], longest = hi[s] - lo[s];
+        for (uint32_t e = edit_off[s]; e < edit_off[s + 1]; ++e) {
+            if (eb[e] < at || ee[e] < eb[e] || ee[e] > hi[s])
+                return fail(HYPO_E_INVALID, "edit %u of site %u = [%llu, %llu): the edits of a site ascend, do not overlap and stay inside [%llu, %llu)", e - edit_off[s], s,
+                            (unsigned long long)eb[e], (unsigned long long)ee[e], (unsigned long long)lo[s], (unsigned long long)hi[s]);
+            if (ao[e] > n_alt_bytes || al[e] > n_alt_bytes - ao[e] || (al[e] && !alts))
+                return fail(HYPO_E_INVALID, "edit %u of site %u: ALT [%llu, +%u) of %llu bytes", e - edit_off[s], s, (unsigned long long)ao[e], al[e], (unsigned long long)n_alt_bytes);
+            at = ee[e];
+            longest += al[e];
+        }
+        if (longest >= (1ull << 31)) return fail(HYPO_E_INVALID, "site %u: a variant of %llu bytes (at most 2^31 - 1)", s, (unsigned long long)longest);
+        n_vars += 1ull << n;
+        if (n_vars > 0xffffffffull) return fail(HYPO_E_INVALID, "more than 2^32 - 1 variants in one call (site %u): split the call", s);
+    }
+    // the items: every variant at least one, a variant with more than KSET_SPAN_PIECE windows several (each carries the k - 1 bytes
+    // its last window needs)
+    std::vector<uint4> items;
+    std::vector<uint32_t> site_item((size_t)n_sites + 1), var_off((size_t)n_sites + 1), rel_off((size_t)n_sites + 1);
+    items.reserve((size_t)(n_vars < (1u << 24) ? n_vars : (1u << 24)));
+    uint64_t vars_before = 0;
+    for (uint32_t s = 0; s < n_sites; ++s) {
+        const uint32_t e0 = edit_off[s], n = edit_off[s + 1] - e0;
+        site_item[s] = (uint32_t)items.size(); var_off[s] = (uint32_t)vars_before; rel_off[s] = e0 - e_first;
+        const int64_t base = (int64_t)(hi[s] - lo[s]);
+        for (uint32_t m = 0; m < (1u << n); ++m) {
+            int64_t len = base;
+            for (uint32_t j = 0; j < n; ++j) if ((m >> j) & 1u) len += (int64_t)al[e0 + j] - (int64_t)(ee[e0 + j] - eb[e0 + j]);
+            const uint32_t n_win = len >= (int64_t)k ? (uint32_t)len - k + 1 : 0;
+            if (!n_win) items.push_back(make_uint4(s, m, 0, 0));
+            for (uint32_t w = 0; w < n_win; w += hypo::KSET_SPAN_PIECE)
+                items.push_back(make_uint4(s, m, w, (n_win - w < hypo::KSET_SPAN_PIECE ? n_win - w : hypo::KSET_SPAN_PIECE) + k - 1));
+        }
+        vars_before += 1ull << n;
+        if (items.size() >= (1ull << 31)) return fail(HYPO_E_CAPACITY, "%llu pieces of variants in one call: split the call", (unsigned long long)items.size());
+    }
+    site_item[n_sites] = (uint32_t)items.size(); var_off[n_sites] = (uint32_t)n_vars; rel_off[n_sites] = edit_off[n_sites] - e_first;
+    n_items = items.size();
+    const uint32_t n_edits = edit_off[n_sites] - e_first;
+    const bool want_vars = var_total || var_missing;
+    int group = hypo::KSET_SPAN_GROUP;
+    if (const char* g = getenv("HYPO_KSET_SPAN_GROUP")) group = atoi(g) == 64 ? 64 : atoi(g) == 32 ? 32 : group;   // (profiles/guard_rate.py)
+    hipStream_t st = g_ctx.stream;
+    // ks.in: bytes | alts.  ks.off: site_lo | eb | ee | ao | items | edit_off | al | site_item | var_off.  ks.res: item pairs |
+    // best_total | best_missing | var_total | var_missing | best_mask.  Every section starts at a multiple of 256 bytes.
+    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t alt_at = up((size_t)n_bytes);
+    size_t o = 0;
+    auto take = [&](size_t bytes_) { const size_t at = o; o = up(o + bytes_); return at; };
+    const size_t o_lo = take((size_t)n_sites * 8), o_eb = take((size_t)n_edits * 8), o_ee = take((size_t)n_edits * 8), o_ao = take((size_t)n_edits * 8),
+                 o_items = take((size_t)n_items * 16), o_eoff = take(((size_t)n_sites + 1) * 4), o_al = take((size_t)n_edits * 4),
+                 o_sitem = take(((size_t)n_sites + 1) * 4), o_voff = take(((size_t)n_sites + 1) * 4);
+    const size_t off_bytes = o;
+    o = 0;
+    const size_t r_item = take((size_t)n_items * 8), r_bt = take((size_t)n_sites * 8), r_bm = take((size_t)n_sites * 8),
+                 r_vt = take(want_vars ? (size_t)n_vars * 8 : 0), r_vm = take(want_vars ? (size_t)n_vars * 8 : 0), r_mask = take((size_t)n_sites * 4);
+    const size_t res_bytes = o;
+    HIP_TRY(ks.in.alloc(alt_at + (size_t)n_alt_bytes));
+    HIP_TRY(ks.off.alloc(off_bytes));
+    HIP_TRY(ks.res.alloc(res_bytes));
+    char* d_in = (char*)ks.in.p; char* d_off = (char*)ks.off.p; char* d_res = (char*)ks.res.p;
+    if (n_bytes) HIP_TRY(h2d(d_in, bytes, n_bytes, st));
+    if (n_alt_bytes) HIP_TRY(h2d(d_in + alt_at, alts, n_alt_bytes, st));
+    HIP_TRY(h2d(d_off + o_lo, lo, (size_t)n_sites * 8, st));
+    if (n_edits) {
+        HIP_TRY(h2d(d_off + o_eb, eb + e_first, (size_t)n_edits * 8, st));
+        HIP_TRY(h2d(d_off + o_ee, ee + e_first, (size_t)n_edits * 8, st));
+        HIP_TRY(h2d(d_off + o_ao, ao + e_first, (size_t)n_edits * 8, st));
+        HIP_TRY(h2d(d_off + o_al, al + e_first, (size_t)n_edits * 4, st));
+    }
+    HIP_TRY(h2d(d_off + o_items, items.data(), (size_t)n_items * 16, st));
+    HIP_TRY(h2d(d_off + o_eoff, rel_off.data(), rel_off.size() * 4, st));
+    HIP_TRY(h2d(d_off + o_sitem, site_item.data(), site_item.size() * 4, st));
+    HIP_TRY(h2d(d_off + o_voff, var_off.data(), var_off.size() * 4, st));
+    HIP_TRY(hypo::kset_variants_run((const uint8_t*)d_in, (const uint8_t*)(d_in + alt_at), (const uint64_t*)(d_off + o_lo), (const uint32_t*)(d_off + o_eoff),
+                                    (const uint64_t*)(d_off + o_eb), (const uint64_t*)(d_off + o_ee), (const uint64_t*)(d_off + o_ao), (const uint32_t*)(d_off + o_al),
+                                    (const uint4*)(d_off + o_items), (uint32_t)n_items, (const uint32_t*)(d_off + o_sitem), (const uint32_t*)(d_off + o_voff), n_sites, k,
+                                    ks.table, ks.slots, (uint2*)(d_res + r_item), (uint32_t*)(d_res + r_mask), (unsigned long long*)(d_res + r_bt),
+                                    (unsigned long long*)(d_res + r_bm), want_vars ? (unsigned long long*)(d_res + r_vt) : nullptr,
+                                    want_vars ? (unsigned long long*)(d_res + r_vm) : nullptr, group, st));
+    HIP_TRY(d2h(best_mask, d_res + r_mask, (size_t)n_sites * 4, st));
+    HIP_TRY(d2h(best_total, d_res + r_bt, (size_t)n_sites * 8, st));
+    HIP_TRY(d2h(best_missing, d_res + r_bm, (size_t)n_sites * 8, st));
+    if (var_total) HIP_TRY(d2h(var_total, d_res + r_vt, (size_t)n_vars * 8, st));
+    if (var_missing) HIP_TRY(d2h(var_missing, d_res + r_vm, (size_t)n_vars * 8, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HYPO_OK;
+}
+
 int hypo_gpu_kset_end(void) {
     HYPO_LOCKED();
     HYPO_ON_DEVICE();

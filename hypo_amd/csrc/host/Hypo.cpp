@@ -142,6 +142,11 @@ void Hypo::bind_extras(Extras& ex) {
     ex.guard_on = _cFlags.kmer_guard;
     if (ex.guard_on) {
         ex.guard.set_k(_cFlags.qv_k);
+        // --guard-records: the variants query as well, bound by name and only under the flag
+        if (_cFlags.guard_records && !ex.guard.bind_variants(_cFlags.guard_records_max)) {
+            std::fprintf(stderr, "[Hypo::Hypo] Error: --guard-records needs hypo_gpu_kset_query_variants, which the device library does not provide\n");
+            std::exit(1);
+        }
         const bool have_spans = ex.guard.bind(), have_set = QvReport().bind();
         ex.guard_edit_fn = bind_edit_scripts();
         if (!have_spans || !have_set || !ex.guard_edit_fn) {
@@ -721,7 +726,17 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         ex.qv.write(out.open_qv(_cFlags.qv_filename), names);
     }
     out.commit([&](RunOutputs::Which w) {
-        if (w == RunOutputs::FASTA && ex.guard_on)
+        if (w == RunOutputs::FASTA && ex.guard_on && ex.guard.by_record()) {
+            const KmerGuard::Stats& gs = ex.guard.stats();
+            std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer guard (k = %u, by record in clusters of up to %u): %llu clusters of %llu records, %llu clusters rejected whole, %llu in part, %llu records rejected\n",
+                         ex.guard.k(), ex.guard.max_records(), (unsigned long long)gs.clusters, (unsigned long long)gs.records, (unsigned long long)gs.rejected_clusters,
+                         (unsigned long long)gs.partial_clusters, (unsigned long long)gs.rejected_records);
+            if (std::getenv("HYPO_STAGE_COUNTERS")) {
+                std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer guard: clusters by number of records:");
+                for (uint32_t n = 1; n <= ex.guard.max_records(); ++n) std::fprintf(stdout, " %u: %llu,", n, (unsigned long long)gs.by_size[n]);
+                std::fprintf(stdout, " > %u: %llu\n", ex.guard.max_records(), (unsigned long long)gs.by_size[0]);
+            }
+        } else if (w == RunOutputs::FASTA && ex.guard_on)
             std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer guard (k = %u): %llu clusters of %llu records, %llu clusters (%llu records) rejected\n", ex.guard.k(),
                          (unsigned long long)ex.guard.stats().clusters, (unsigned long long)ex.guard.stats().records, (unsigned long long)ex.guard.stats().rejected_clusters,
                          (unsigned long long)ex.guard.stats().rejected_records);

@@ -4,6 +4,10 @@
 // either side, are two spans of one hypo_gpu_kset_query_spans call on context 0 (kset_kernel.hip), and a cluster whose polished span
 // lacks more k-mers of the reads' set (QvReport holds it) than its draft span is rejected with all its records.  The FASTA record is
 // the draft with the accepted records applied.
+// hypo --guard-records (DESIGN.md "k-mer guard by record"): a cluster of 2 .. N records is one site of a
+// hypo_gpu_kset_query_variants call, its records the site's edits, and of all subsets of them the one the call names best is
+// kept; a larger cluster is a site with ONE edit, its draft span replaced by its polished span, which is the decision above.
+// Only the drafts and the ALT strings go to the device.
 #pragma once
 #include <cstdint>
 #include <functional>
@@ -17,7 +21,9 @@ namespace hypo {
 
 class KmerGuard {
 public:
-    struct Stats { uint64_t clusters = 0, records = 0, rejected_clusters = 0, rejected_records = 0; };
+    // rejected_clusters: rejected with all their records; partial_clusters: with some (by record only); by_size[n]: clusters of n
+    // records, n = 1 .. N, and [0] those of more (by record only)
+    struct Stats { uint64_t clusters = 0, records = 0, rejected_clusters = 0, rejected_records = 0, partial_clusters = 0; uint64_t by_size[13] = {}; };
     // One contig's clusters: records [first[c], first[c + 1]) of the contig form cluster c; its draft span [b, e) and polished span
     // [qb, qe) without the flanks.
     struct Cluster { size_t r0 = 0, r1 = 0; uint64_t b = 0, e = 0, qb = 0, qe = 0; };
@@ -26,6 +32,11 @@ public:
 
     // binds hypo_gpu_kset_query_spans by name (false: the device library does not provide it)
     bool bind();
+    // --guard-records: binds hypo_gpu_kset_query_variants by name (false: the device library does not provide it); clusters of up
+    // to max_records (2..12) records are decided record by record from here on
+    bool bind_variants(uint32_t max_records);
+    bool by_record() const { return _variants != nullptr; }
+    uint32_t max_records() const { return _max_records; }
     void set_k(uint32_t k) { _k = k; }
     // the clusters of one contig's records (the rule above); polished spans follow from the records' length changes
     static void clusters_of(const std::vector<VcfRec>& recs, uint32_t k, std::vector<Cluster>& out);
@@ -40,6 +51,17 @@ public:
 private:
     struct Pending { uint32_t contig = 0; uint64_t d_off = 0, d_len = 0, p_off = 0, p_len = 0; VcfContigRecords recs; std::vector<Cluster> clusters; size_t span0 = 0; };
     int flush(const Emit& emit);
+    int flush_by_record(const Emit& emit);
+    int (*_variants)(const char*, uint64_t, const char*, uint64_t, const uint64_t*, const uint64_t*, const uint32_t*, uint32_t, const uint64_t*, const uint64_t*,
+                     const uint64_t*, const uint32_t*, uint32_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*) = nullptr;
+    uint32_t _max_records = 8;
+    // by record: the ALT strings (and the polished spans of the clusters decided whole) back to back, one site per cluster
+    // ([_lo, _hi) as above, one entry a cluster), the sites' edits, and the polished texts (kept on the host for emit)
+    std::string _alts;
+    std::vector<uint32_t> _edit_off, _al;
+    std::vector<uint64_t> _eb, _ee, _ao;
+    std::vector<std::string> _polished;
+    uint64_t _n_variants = 0;
     int (*_spans)(const char*, uint64_t, const uint64_t*, const uint64_t*, uint32_t, uint64_t*, uint64_t*) = nullptr;
     uint32_t _k = 21;
     Stats _stats;

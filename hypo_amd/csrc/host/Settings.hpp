@@ -29,6 +29,8 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     uint32_t qv_k = 21;                    // new, opt-in: --qv-k (12..31)
     double qv_mem_gib = 0;                 // new, opt-in: --qv-mem (cap of the k-mer set; 0 = half of the device's free memory)
     bool kmer_guard = false;               // new, opt-in: --kmer-guard (edits whose k-mers the reads do not support are left out)
+    bool guard_records = false;            // new, opt-in: --guard-records (the guard decides clustered edits record by record; implies --kmer-guard)
+    uint32_t guard_records_max = 8;        // new, opt-in: --guard-records-max (2..12: clusters of more records are decided whole)
     uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
 };
 

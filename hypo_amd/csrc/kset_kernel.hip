@@ -12,6 +12,8 @@
 //     lookup is a read-only probe that ends at the key or at a free slot.  Windows and misses are summed per wave and added per
 //     sequence with one 64-bit add each (a lane whose stretch crosses into another sequence adds what it has first); the sums are
 //     integers, so their order does not matter.
+//   * kset_spans_kernel / kset_variants_kernel (below, with comments of their own): many short spans, and every subset of a few
+//     edits of many short sites, a group of 32 or 64 lanes per item; read-only probes, no LDS, no atomics.
 // Forward progress: every probe loop runs at most `slots` steps.  A lane of the insert or rehash kernel that finds neither its key
 // nor a free slot sets the overflow flag and leaves; lanes in a long probe look at the flag every 64 steps and leave too.  The host
 // keeps the table at most half full, so the flag says "internal error", but no input can make a kernel spin.
@@ -245,6 +247,130 @@ hipError_t kset_spans_run(const uint8_t* bytes, const uint64_t* item_lo, const u
     const uint32_t blocks = (n_items + per_block - 1) / per_block;
     if (group == 32) kset_spans_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out);
     else kset_spans_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out);
+    return hipGetLastError();
+}
+
+// ---- every subset of a site's edits (hypo --guard-records; DESIGN.md "k-mer guard by record") -------------------------------------------
+// An item is a piece of ONE variant of a site: x = site, y = mask, z = the piece's first byte in the variant's text, w = its length
+// (at most KSET_SPAN_PIECE windows, as the spans' pieces).  The variant's text exists nowhere: byte p of variant `mask` of a site
+// is found by walking the site's (at most KSET_MAX_EDITS) edits in order with two running positions, `sp` in bytes and `vp` in the
+// variant, and comes from `alts` inside an edit whose bit is set, from `bytes` otherwise.  A lane loads one such byte a pass; from
+// there on the kernel is kset_spans_kernel: three ballots, carried masks, the bit-reversed interleave, ks_contains, ballot counts.
+// No LDS, no atomics, no scratch; item i's pair goes to out[i] and kset_variants_reduce_kernel adds the pieces up.
+// Bounds: a lane asks for byte p of its item's variant only for p < z + w <= the variant's length (the caller computed both from the
+// same edits), so the walk ends inside the site: bytes is read at [lo, hi) of the site, alts at [ao[e], ao[e] + al[e]) of an edit
+// of the site, e in [edit_off[site], edit_off[site + 1]) — the caller checked lo <= eb_0 <= ee_0 <= ... <= hi <= n_bytes and
+// ao + al <= n_alt_bytes for all of them.  items / out are indexed below n_items, sites below n_sites (the caller's items name
+// sites it has), the probe is ks_contains.
+__device__ __forceinline__ uint32_t ks_variant_byte(const uint8_t* __restrict__ bytes, const uint8_t* __restrict__ alts, uint64_t lo,
+                                                     uint32_t e0, uint32_t e1, const uint64_t* __restrict__ eb, const uint64_t* __restrict__ ee,
+                                                     const uint64_t* __restrict__ ao, const uint32_t* __restrict__ al, uint32_t mask, uint32_t p) {
+    uint64_t sp = lo;                                           // bytes before sp are behind the walk
+    uint32_t vp = 0;                                            // and so are the variant's bytes before vp
+    for (uint32_t e = e0; e < e1; ++e) {
+        const uint64_t b = eb[e], en = ee[e];
+        const uint32_t keep = (uint32_t)(b - sp);               // the unchanged stretch in front of the edit
+        if (p - vp < keep) return bytes[sp + (p - vp)];
+        vp += keep;
+        if ((mask >> (e - e0)) & 1u) {
+            const uint32_t n = al[e];
+            if (p - vp < n) return alts[ao[e] + (p - vp)];
+            vp += n;
+        } else {
+            const uint32_t n = (uint32_t)(en - b);
+            if (p - vp < n) return bytes[b + (p - vp)];
+            vp += n;
+        }
+        sp = en;
+    }
+    return bytes[sp + (p - vp)];
+}
+
+template <int G>
+__global__ void __launch_bounds__(KS_THREADS) kset_variants_kernel(const uint8_t* __restrict__ bytes, const uint8_t* __restrict__ alts,
+                                                                    const uint64_t* __restrict__ site_lo, const uint32_t* __restrict__ edit_off,
+                                                                    const uint64_t* __restrict__ eb, const uint64_t* __restrict__ ee,
+                                                                    const uint64_t* __restrict__ ao, const uint32_t* __restrict__ al,
+                                                                    const uint4* __restrict__ items, uint32_t n_items, uint32_t k,
+                                                                    const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out) {
+    static_assert(G == 32 || G == 64, "a half-wave or a wave");
+    const uint32_t lane = threadIdx.x & 63, l = lane & (G - 1), half = G == 64 ? 0 : lane >> 5;
+    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
+    const bool have = item < n_items;
+    const uint4 it = have ? items[item] : make_uint4(0, 0, 0, 0);
+    const uint32_t len = it.w;
+    const uint64_t lo = have ? site_lo[it.x] : 0;
+    const uint32_t e0 = have ? edit_off[it.x] : 0, e1 = have ? edit_off[it.x + 1] : 0;
+    const uint32_t n_win = len >= k ? len - k + 1 : 0;
+    const uint32_t kmask = (uint32_t)((1ull << k) - 1);
+    auto load_masks = [&](uint32_t at, uint64_t& b0, uint64_t& b1, uint64_t& bad) {   // bytes [at, at + G) of the item (wave-uniform call)
+        const uint32_t x = at + l;
+        const uint32_t c = x < len ? ks_base_code(ks_variant_byte(bytes, alts, lo, e0, e1, eb, ee, ao, al, it.y, it.z + x)) : 4u;
+        b0 = ks_group_part<G>(__ballot(c & 1u), half);
+        b1 = ks_group_part<G>(__ballot(c & 2u), half);
+        bad = ks_group_part<G>(__ballot(c > 3u), half);
+    };
+    uint64_t c0, c1, cb, n0, n1, nb;
+    load_masks(0, c0, c1, cb);
+    uint32_t tot = 0, mis = 0;
+    for (uint32_t base = 0; __any(base < n_win); base += G) {   // (variant lengths differ per mask: both halves stay until the longer is done)
+        load_masks(base + G, n0, n1, nb);
+        const bool in = base + l < n_win;
+        const bool ok = in && (ks_window_bits<G>(cb, nb, l) & kmask) == 0;
+        bool miss = false;
+        if (ok) {
+            const uint32_t h0 = ks_window_bits<G>(c0, n0, l) & kmask, h1 = ks_window_bits<G>(c1, n1, l) & kmask;
+            const uint64_t fwd = (ks_spread(__brev(h1) >> (32 - k)) << 1) | ks_spread(__brev(h0) >> (32 - k));
+            const uint64_t rc = (ks_spread(~h1 & kmask) << 1) | ks_spread(~h0 & kmask);
+            miss = !ks_contains(table, slots, fwd < rc ? fwd : rc);
+        }
+        tot += (uint32_t)__popcll(ks_group_part<G>(__ballot(ok), half));
+        mis += (uint32_t)__popcll(ks_group_part<G>(__ballot(miss), half));
+        c0 = n0; c1 = n1; cb = nb;
+    }
+    if (have && l == 0) out[item] = make_uint2(tot, mis);
+}
+
+// One lane per site: the pieces of every variant are added up (the site's items are in mask order, a variant's pieces next to each
+// other) and the best variant is kept: fewest missing, then most edits taken, then the greatest mask — masks come in ascending
+// order, so among equals the later one wins when it takes at least as many edits.  var_total / var_missing (NULL or both): every
+// variant's sums at var_off[site] + mask.
+// Bounds: items / res below site_item[n_sites] = n_items, best_* below n_sites, var_* below var_off[site] + 2^(edits of the site).
+__global__ void __launch_bounds__(KS_THREADS) kset_variants_reduce_kernel(const uint4* __restrict__ items, const uint2* __restrict__ res,
+                                                                           const uint32_t* __restrict__ site_item, const uint32_t* __restrict__ var_off,
+                                                                           uint32_t n_sites, uint32_t* __restrict__ best_mask,
+                                                                           unsigned long long* __restrict__ best_total, unsigned long long* __restrict__ best_missing,
+                                                                           unsigned long long* __restrict__ var_total, unsigned long long* __restrict__ var_missing) {
+    const uint64_t s = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x;
+    if (s >= n_sites) return;
+    const uint32_t i0 = site_item[s], i1 = site_item[s + 1], v0 = var_off[s];
+    uint32_t bm = 0;
+    unsigned long long bt = 0, bmis = 0;
+    bool first = true;
+    for (uint32_t i = i0; i < i1;) {
+        const uint32_t m = items[i].y;
+        unsigned long long t = 0, mis = 0;
+        for (; i < i1 && items[i].y == m; ++i) { t += res[i].x; mis += res[i].y; }
+        if (var_total) { var_total[(uint64_t)v0 + m] = t; var_missing[(uint64_t)v0 + m] = mis; }
+        if (first || mis < bmis || (mis == bmis && __popc(m) >= __popc(bm))) { bm = m; bt = t; bmis = mis; first = false; }
+    }
+    best_mask[s] = bm; best_total[s] = bt; best_missing[s] = bmis;
+}
+
+hipError_t kset_variants_run(const uint8_t* bytes, const uint8_t* alts, const uint64_t* site_lo, const uint32_t* edit_off, const uint64_t* eb,
+                             const uint64_t* ee, const uint64_t* ao, const uint32_t* al, const uint4* items, uint32_t n_items,
+                             const uint32_t* site_item, const uint32_t* var_off, uint32_t n_sites, uint32_t k, const uint64_t* table, uint64_t slots,
+                             uint2* item_res, uint32_t* best_mask, unsigned long long* best_total, unsigned long long* best_missing,
+                             unsigned long long* var_total, unsigned long long* var_missing, int group, hipStream_t st) {
+    if (!n_sites || !n_items) return hipSuccess;
+    const uint32_t per_block = (uint32_t)KS_THREADS / (uint32_t)group;
+    const uint32_t blocks = (n_items + per_block - 1) / per_block;
+    if (group == 32) kset_variants_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res);
+    else kset_variants_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    kset_variants_reduce_kernel<<<dim3((n_sites + KS_THREADS - 1) / KS_THREADS), dim3(KS_THREADS), 0, st>>>(items, item_res, site_item, var_off, n_sites, best_mask, best_total,
+                                                                                                              best_missing, var_total, var_missing);
     return hipGetLastError();
 }
 

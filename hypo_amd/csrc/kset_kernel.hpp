@@ -31,4 +31,19 @@ constexpr int KSET_SPAN_GROUP = 32;                // the default geometry (DESI
 hipError_t kset_spans_run(const uint8_t* bytes, const uint64_t* item_lo, const uint32_t* item_len, uint32_t n_items, uint32_t k,
                           const uint64_t* table, uint64_t slots, uint2* out, int group, hipStream_t st);
 
+// Every subset of the edits of n_sites sites (hypo --guard-records): site s is bytes[site_lo[s], ..) with the edits
+// [edit_off[s], edit_off[s + 1]) (at most KSET_MAX_EDITS, ascending and disjoint; edit e replaces bytes[eb[e], ee[e]) by
+// alts[ao[e], ao[e] + al[e])); variant `mask` of a site takes the ALT of its edit j when bit j is set.  items: (site, mask, first
+// byte of the piece in the variant's text, bytes of the piece), in site order, within a site in mask order, within a variant in
+// text order, every variant with at least one item (w = 0: no window); site_item[s] = the first item of site s (n_sites + 1
+// entries), var_off[s] = the variants of the sites before s.  item_res: n_items pairs of work space.  best_*[s]: the variant with
+// the fewest missing windows, then the most edits taken, then the greatest mask; var_total / var_missing (both or neither): every
+// variant's pair at var_off[s] + mask.  The caller has checked every range (see the bounds comment of the kernels).
+constexpr uint32_t KSET_MAX_EDITS = 12;
+hipError_t kset_variants_run(const uint8_t* bytes, const uint8_t* alts, const uint64_t* site_lo, const uint32_t* edit_off, const uint64_t* eb,
+                             const uint64_t* ee, const uint64_t* ao, const uint32_t* al, const uint4* items, uint32_t n_items,
+                             const uint32_t* site_item, const uint32_t* var_off, uint32_t n_sites, uint32_t k, const uint64_t* table, uint64_t slots,
+                             uint2* item_res, uint32_t* best_mask, unsigned long long* best_total, unsigned long long* best_missing,
+                             unsigned long long* var_total, unsigned long long* var_missing, int group, hipStream_t st);
+
 }  // namespace hypo

@@ -433,6 +433,25 @@ int hypo_gpu_kset_end(void);
  * n_bytes are sent to the device once, whatever the spans cover.  lo[s] > hi[s] or hi[s] > n_bytes: HYPO_E_INVALID.  Without a
  * set: HYPO_E_INVALID, as hypo_gpu_kset_query.  Synchronous, on the calling thread's context. */
 int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_t* lo, const uint64_t* hi, uint32_t n_spans, uint64_t* total, uint64_t* missing);
+/* Every subset of a few edits of many short sites against the set (hypo --guard-records; DESIGN.md "k-mer guard by record").
+ * Additive to ABI 11: callers bind it by name.  Site s is bytes[lo[s], hi[s]); its edits are e in [edit_off[s], edit_off[s + 1]),
+ * at most HYPO_KSET_MAX_EDITS of them (none is allowed); edit e replaces bytes[eb[e], ee[e]) by alts[ao[e], ao[e] + al[e]).  Inside
+ * a site the edits ascend and do not overlap: lo <= eb_0 <= ee_0 <= eb_1 <= ... <= ee_{n-1} <= hi; abutting edits, empty REF
+ * spans and empty ALTs are allowed.  Variant m of a site (m < 2^n) is its text with the ALT of edit j where bit j of m is set and
+ * the REF bytes elsewhere; total / missing of a variant are those of hypo_gpu_kset_query for that text (no window crosses the
+ * site's ends).  The variants' texts are never built.  best_mask[s] is the variant with the fewest missing windows, among those
+ * the one with the most bits set, among those the greatest m; best_total[s] / best_missing[s] are its pair.  var_total /
+ * var_missing (each may be NULL) receive every variant's pair: in site order, within a site in mask order, sum of 2^n entries.
+ * Sites may overlap, repeat and come in any order; the answers depend on the input alone.  HYPO_E_INVALID: edits out of order or
+ * out of range, more than HYPO_KSET_MAX_EDITS of them in a site, a variant of 2^31 bytes or more, more than 2^32 - 1 variants in
+ * the call, a NULL required pointer with n_sites > 0, no set (as hypo_gpu_kset_query); a refused call changes nothing.
+ * Synchronous, on the calling thread's context. */
+#define HYPO_KSET_MAX_EDITS 12
+int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char* alts, uint64_t n_alt_bytes,
+    const uint64_t* lo, const uint64_t* hi, const uint32_t* edit_off /* n_sites + 1 */, uint32_t n_sites,
+    const uint64_t* eb, const uint64_t* ee, const uint64_t* ao, const uint32_t* al,
+    uint32_t* best_mask, uint64_t* best_total, uint64_t* best_missing,
+    uint64_t* var_total /* may be NULL */, uint64_t* var_missing /* may be NULL */);
 
 /* Kernel timing with HIP events on the stream the kernels run on ----------------------------------
  * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each records

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""hypo --kmer-guard on the MI355X: the rate of hypo_gpu_kset_query_spans on the spans of a real run's records, and what the guard
-adds to the wall time of `hypo` on BASELINE config C3 (DESIGN.md "k-mer guard").
+"""hypo --kmer-guard and --guard-records on the MI355X: the rates of hypo_gpu_kset_query_spans and hypo_gpu_kset_query_variants on the
+spans and the sites of a real run's records, and what the guard adds to the wall time of `hypo` on BASELINE config C3 (DESIGN.md "k-mer guard").
 
     python profiles/guard_rate.py --out DIR [--parent-bin PATH]      # everything below, in one call
       1. e2e_c3_100m_s31 (100 x 1 Mbp, -p 10) is generated in a scratch directory and polished once without a flag and once with
@@ -9,8 +9,12 @@ adds to the wall time of `hypo` on BASELINE config C3 (DESIGN.md "k-mer guard").
       2. a child builds the 21-mer set of the run's reads and makes the spans call with a half-wave and with a wave per span
          (HYPO_KSET_SPAN_GROUP): one warm-up call, then 5 timed calls each (spans/s of the entry, upload of the text included).
       3. `rocprofv3 --kernel-trace --stats` around the same child: the kernel's own time per call, per geometry.
+      2b. the same child makes the variants call of --guard-records (hypo_gpu_kset_query_variants: one site per cluster of up to 8
+         records, the records its edits, over the drafts alone) with both geometries, timed the same way; the cluster-size histogram
+         and the number of clusters the call accepts in part are recorded with it.
       4. `hypo` on C3, --wall-runs alternated runs each (default 10; process wall): no flag, no flag with the parent commit's binary
-         (--parent-bin: hypo of a build of the parent, beside its two libraries), --qv, --qv --kmer-guard.
+         (--parent-bin: hypo of a build of the parent, beside its two libraries), --qv, --qv --kmer-guard,
+         --kmer-guard, --guard-records.
     python profiles/guard_rate.py --spans-only spans_c3.npz --reads reads.fa      # (the child of steps 2 and 3)
 """
 import argparse
@@ -32,6 +36,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 K = 21
 PIECE = 256 << 20
 REPS = 5
+N_MAX = 8                     # --guard-records-max's default
 
 
 def spans_calls(path, reads):
@@ -63,6 +68,28 @@ def spans_calls(path, reads):
                                      "windows_per_s": round(windows / min(ts))}
     assert all(np.array_equal(a, b) for a, b in zip(*answers)), "the two geometries disagree"
     out["missing_windows"] = int(answers[0][1].sum())
+    if "v_lo" in z:                                          # the sites of --guard-records over the drafts alone
+        args = (z["v_text"], z["v_alts"], z["v_lo"], z["v_hi"], z["v_eoff"], z["v_eb"], z["v_ee"], z["v_ao"], z["v_al"])
+        n_edits = np.diff(z["v_eoff"].astype(np.int64))
+        v = {"sites": int(z["v_lo"].size), "edits": int(n_edits.sum()), "variants": int((1 << n_edits).sum()), "text_bytes": int(z["v_text"].size),
+             "alt_bytes": int(z["v_alts"].size), "cluster_sizes": json.loads(str(z["v_hist"])), "groups": {}}
+        masks = []
+        for group in (32, 64):
+            os.environ["HYPO_KSET_SPAN_GROUP"] = str(group)
+            gpu.kset_query_variants(*args, variants=False)
+            ts = []
+            for _ in range(REPS):
+                t0 = time.perf_counter()
+                best = gpu.kset_query_variants(*args, variants=False)
+                ts.append(time.perf_counter() - t0)
+            masks.append(best[0])
+            v["groups"][str(group)] = {"call_s": [round(t, 4) for t in ts], "best_s": round(min(ts), 4), "variants_per_s": round(v["variants"] / min(ts))}
+        assert np.array_equal(*masks), "the two geometries disagree"
+        full = (1 << n_edits) - 1
+        whole = z["v_whole"].astype(bool)                    # sites of clusters beyond the limit: one edit, decided whole
+        v["rejected_whole"] = int((masks[0] == 0).sum())
+        v["accepted_in_part"] = int(((masks[0] != 0) & (masks[0] != full) & ~whole).sum())
+        out["variants"] = v
     gpu.kset_end()
     return out
 
@@ -93,9 +120,25 @@ def prepare(outdir, threads):
             hi += [at + min(len(D), e + K - 1), at + len(D) + min(len(P), qe + K - 1)]
         parts += [D, P]
         at += len(D) + len(P)
+    # the sites of --guard-records: one per cluster, its records the edits (a cluster of more than N_MAX records: its polished span)
+    v_lo, v_hi, v_eoff, v_eb, v_ee, v_ao, v_al, v_whole, alts, hist, at = [], [], [0], [], [], [], [], [], bytearray(), {}, 0
+    for n, D in drafts:
+        P, rs = polished[n], recs.get(n, [])
+        for i0, i1, b, e, qb, qe in gc.clusters(rs, K):
+            size = i1 - i0
+            hist[str(size) if size <= N_MAX else "more"] = hist.get(str(size) if size <= N_MAX else "more", 0) + 1
+            v_lo.append(at + max(0, b - K + 1)); v_hi.append(at + min(len(D), e + K - 1)); v_whole.append(size > N_MAX)
+            edits = [(pos - 1, pos - 1 + len(ref), alt) for pos, ref, alt, _ in rs[i0:i1]] if size <= N_MAX else [(b, e, P[qb:qe])]
+            for eb_, ee_, alt in edits:
+                v_eb.append(at + eb_); v_ee.append(at + ee_); v_ao.append(len(alts)); v_al.append(len(alt)); alts += alt.encode()
+            v_eoff.append(len(v_eb))
+        at += len(D)
     path = os.path.join(outdir, "spans_c3.npz")
+    u64 = lambda x: np.array(x, np.uint64)
     np.savez(path, text=np.frombuffer("".join(parts).encode(), dtype=np.uint8), lo=np.array(lo, np.uint64), hi=np.array(hi, np.uint64),
-             genome=sum(len(D) for _, D in drafts))
+             genome=sum(len(D) for _, D in drafts), v_text=np.frombuffer("".join(D for _, D in drafts).encode(), dtype=np.uint8),
+             v_alts=np.frombuffer(bytes(alts), dtype=np.uint8), v_lo=u64(v_lo), v_hi=u64(v_hi), v_eoff=np.array(v_eoff, np.uint32), v_eb=u64(v_eb),
+             v_ee=u64(v_ee), v_ao=u64(v_ao), v_al=np.array(v_al, np.uint32), v_whole=np.array(v_whole, np.uint8), v_hist=json.dumps(hist))
     reads = argv[argv.index("-r") + 1]
     return path, d, argv, os.path.join(d, reads), {"first_run_s": round(dt, 2), "guarded_run_s": round(dt_g, 2), "guard_info": info[0] if info else None}
 
@@ -167,7 +210,8 @@ def main():
         shutil.rmtree(work, ignore_errors=True)
         raise SystemExit(1)
     # wall time on C3: alternated
-    kinds = {"no_flag": (argv, []), "qv": (argv, ["--qv", "t.tsv"]), "qv_guard": (argv, ["--qv", "t.tsv", "--kmer-guard"])}
+    kinds = {"no_flag": (argv, []), "qv": (argv, ["--qv", "t.tsv"]), "qv_guard": (argv, ["--qv", "t.tsv", "--kmer-guard"]),
+             "guard": (argv, ["--kmer-guard"]), "guard_records": (argv, ["--guard-records"])}
     if args.parent_bin:
         kinds["no_flag_parent"] = ([os.path.abspath(args.parent_bin)] + argv[1:], [])
     runs = {k: [] for k in kinds}
@@ -177,6 +221,7 @@ def main():
         print("wall", i, {k: round(v[-1], 3) for k, v in runs.items()}, flush=True)
     res["c3_wall"] = {k: spread(v) for k, v in runs.items()}
     res["c3_wall"]["guard_over_qv_median_pct"] = round(100 * (np.median(runs["qv_guard"]) / np.median(runs["qv"]) - 1), 2)
+    res["c3_wall"]["guard_records_over_guard_median_pct"] = round(100 * (np.median(runs["guard_records"]) / np.median(runs["guard"]) - 1), 2)
     if args.parent_bin:
         res["c3_wall"]["no_flag_vs_parent_median_pct"] = round(100 * (np.median(runs["no_flag"]) / np.median(runs["no_flag_parent"]) - 1), 2)
     print(json.dumps(res["c3_wall"]), flush=True)
