@@ -16,6 +16,9 @@ HYPO_E_NOTINIT = -5
 HYPO_E_CAPACITY = -6
 HYPO_E_UNSUPPORTED = -7
 
+# hypo_gpu_kset_query_track: what hypo_amd.capi puts into the interval arrays before a call (no position or count is that large)
+TRACK_UNTOUCHED = 0xFFFFFFFFFFFFFFFF
+
 ST_OK = 0
 ST_CONS_OVERFLOW = 1
 ST_CAPACITY = 2

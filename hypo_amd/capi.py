@@ -30,7 +30,7 @@ EXPORTS = [
     "hypo_gpu_kmer_count_begin", "hypo_gpu_kmer_count_add", "hypo_gpu_kmer_histogram", "hypo_gpu_solid_set_build",
     "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts",
     "hypo_gpu_kset_begin", "hypo_gpu_kset_add", "hypo_gpu_kset_size", "hypo_gpu_kset_query", "hypo_gpu_kset_end",
-    "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants",
+    "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants", "hypo_gpu_kset_query_track",
 ]
 KSET_SPAN_PIECE = 2048        # windows per piece of a long span (kset_kernel.hpp)
 KSET_MAX_EDITS = 12           # edits of a site of hypo_gpu_kset_query_variants (HYPO_KSET_MAX_EDITS)
@@ -335,6 +335,41 @@ class HypoGpu:
         (best_mask, best_total, best_missing, var_total, var_missing): per site the best subset of its edits (fewest missing, most
         edits, greatest mask), and every subset's pair in site and mask order."""
         out = self.kset_query_variants_rc(data, alts, lo, hi, edit_off, eb, ee, ao, al, variants)
+        self._check(out[0])
+        return out[1:]
+
+    def kset_query_track_rc(self, seqs_or_text, off=None, want=None, iv_cap=0):
+        """(return code, total u64[n], missing u64[n], iv_off u64[n + 1], iv_start, iv_end, iv_missing: u64[iv_cap]) of one call of
+        hypo_gpu_kset_query_track; nothing is checked here.  A list of byte strings, or one text with its n + 1 offsets.  The three
+        interval arrays are filled with abi.TRACK_UNTOUCHED before the call (iv_cap = 0: the counting call, NULL pointers)."""
+        if off is None:
+            seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs_or_text]
+            off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+            text = b"".join(seqs)
+        else:
+            text = seqs_or_text.encode() if isinstance(seqs_or_text, str) else bytes(seqs_or_text)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = off.size - 1
+        data = np.frombuffer(text + b"\0", dtype=np.uint8)               # (an empty text still has an address)
+        if want is not None:
+            want = np.ascontiguousarray(want, dtype=np.uint8)
+            assert want.size == n
+        total, missing = np.zeros(max(n, 1), dtype=np.uint64), np.zeros(max(n, 1), dtype=np.uint64)
+        iv_off = np.zeros(n + 1, dtype=np.uint64)
+        iv = [np.full(iv_cap, abi.TRACK_UNTOUCHED, dtype=np.uint64) for _ in range(3)]
+        rc = int(self.lib.hypo_gpu_kset_query_track(_p(data), _p(off), C.c_uint32(n), _p(want) if want is not None and n else None, _p(total), _p(missing),
+                                                    _p(iv_off), *[_p(a) if iv_cap else None for a in iv], C.c_uint64(iv_cap)))
+        return (rc, total[:n], missing[:n], iv_off) + tuple(iv)
+
+    def kset_query_track(self, seqs_or_text, off=None, want=None):
+        """kset_query, and where the missing windows are: (total u64[n], missing u64[n], iv_off u64[n + 1], iv_start, iv_end,
+        iv_missing).  The intervals of sequence s are [iv_off[s], iv_off[s + 1]) of the three arrays: maximal runs [start, end) of
+        bases under a missing window, relative to the sequence, ascending, with the missing windows inside.  want[s] == 0: no
+        intervals for s.  Two calls: one that counts, one with room."""
+        out = self.kset_query_track_rc(seqs_or_text, off, want, 0)
+        if out[0] == abi.HYPO_E_WORKSPACE:
+            out = self.kset_query_track_rc(seqs_or_text, off, want, int(out[3][-1]))
         self._check(out[0])
         return out[1:]
 

@@ -1232,6 +1232,77 @@ int hypo_gpu_kset_query(const char* bytes, const uint64_t* off, uint32_t n_seqs,
     return HYPO_OK;
 }
 
+int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n_seqs, const uint8_t* want, uint64_t* total, uint64_t* missing,
+                              uint64_t* iv_off, uint64_t* iv_start, uint64_t* iv_end, uint64_t* iv_missing, uint64_t iv_cap) {
+    HYPO_LOCKED();
+    HYPO_ON_DEVICE();
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    Ctx::KSet& ks = g_ctx.ks;
+    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    if (iv_cap && (!iv_start || !iv_end || !iv_missing)) return fail(HYPO_E_INVALID, "NULL buffer");
+    if (!n_seqs) { if (iv_off) iv_off[0] = 0; return HYPO_OK; }
+    if (!off || !total || !missing || !iv_off) return fail(HYPO_E_INVALID, "NULL buffer");
+    std::vector<uint64_t> rel((size_t)n_seqs + 1);
+    for (uint32_t i = 0; i <= n_seqs; ++i) {
+        if (off[i] < off[0] || (i && off[i] < off[i - 1])) return fail(HYPO_E_INVALID, "off[] must not decrease (entry %u)", i);
+        rel[i] = off[i] - off[0];
+    }
+    const uint64_t n = rel[n_seqs];
+    if (n && !bytes) return fail(HYPO_E_INVALID, "NULL buffer");
+    for (uint32_t i = 0; i < n_seqs; ++i) total[i] = missing[i] = 0;
+    for (uint32_t i = 0; i <= n_seqs; ++i) iv_off[i] = 0;
+    if (!n) return HYPO_OK;
+    hipStream_t st = g_ctx.stream;
+    // `in`: the bytes.  `off`: the offsets, the want bytes, then what indexes the bytes: the two flag words per 32 positions, the
+    // per-workgroup sums and their prefixes.  `res`: total / missing first; once those and the number of intervals are on the
+    // host, iv_off and the intervals (a grown arena loses nothing that is still needed).
+    const uint32_t blocks = hypo::kset_track_blocks(n);
+    const size_t n_words = (size_t)blocks * 256;
+    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+    const size_t at_want = pad(rel.size() * 8), at_miss = at_want + pad(n_seqs), at_begin = at_miss + pad(n_words * 4),
+                 at_sums = at_begin + pad(n_words * 4), at_pre = at_sums + pad((size_t)blocks * 8), off_bytes = at_pre + pad(((size_t)blocks + 1) * 24);
+    HIP_TRY(ks.in.alloc(n));
+    HIP_TRY(ks.off.alloc(off_bytes));
+    HIP_TRY(ks.res.alloc((size_t)n_seqs * 16));
+    char* const d_off = (char*)ks.off.p;
+    unsigned long long* d_tot = (unsigned long long*)ks.res.p;
+    unsigned long long* d_mis = d_tot + n_seqs;
+    const uint64_t* d_pre = (const uint64_t*)(d_off + at_pre);
+    HIP_TRY(h2d(ks.in.p, bytes + off[0], n, st));
+    HIP_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+    if (want) HIP_TRY(hipMemcpyAsync(d_off + at_want, want, n_seqs, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(ks.res.p, 0, (size_t)n_seqs * 16, st));
+    HIP_TRY(hypo::kset_track_count_run((const uint8_t*)ks.in.p, (const uint64_t*)d_off, n_seqs, n, ks.k, ks.table, ks.slots, d_tot, d_mis,
+                                       want ? (const uint8_t*)(d_off + at_want) : nullptr, (uint32_t*)(d_off + at_miss), (uint32_t*)(d_off + at_begin),
+                                       (uint64_t*)(d_off + at_sums), (uint64_t*)(d_off + at_pre), st));
+    uint64_t sums[3] = {0, 0, 0};                               // starts, ends, missing windows of the wanted sequences
+    HIP_TRY(hipMemcpyAsync(total, d_tot, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(missing, d_mis, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(sums, d_pre + 3 * (size_t)blocks, 24, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (sums[0] != sums[1]) return fail(HYPO_E_HIP, "k-mer track: internal error: %llu interval starts, %llu ends", (unsigned long long)sums[0], (unsigned long long)sums[1]);
+    const uint64_t n_iv = sums[0];
+    const size_t at_iv = pad(rel.size() * 8), iv_bytes = pad((size_t)n_iv * 8);
+    HIP_TRY(ks.res.alloc(at_iv + 4 * iv_bytes));
+    char* const d_res = (char*)ks.res.p;
+    uint64_t* const d_start = (uint64_t*)(d_res + at_iv);
+    uint64_t* const d_end = (uint64_t*)(d_res + at_iv + iv_bytes);
+    uint64_t* const d_lo = (uint64_t*)(d_res + at_iv + 2 * iv_bytes);
+    uint64_t* const d_hi = (uint64_t*)(d_res + at_iv + 3 * iv_bytes);
+    HIP_TRY(hypo::kset_track_emit_run((const uint64_t*)d_off, n_seqs, n, ks.k, (const uint32_t*)(d_off + at_miss), (const uint32_t*)(d_off + at_begin), d_pre, n_iv,
+                                      (uint64_t*)d_res, d_start, d_end, d_lo, d_hi, st));
+    HIP_TRY(hipMemcpyAsync(iv_off, d_res, rel.size() * 8, hipMemcpyDeviceToHost, st));
+    const bool fits = n_iv <= iv_cap;
+    if (fits && n_iv) {
+        HIP_TRY(d2h(iv_start, d_start, (size_t)n_iv * 8, st));
+        HIP_TRY(d2h(iv_end, d_end, (size_t)n_iv * 8, st));
+        HIP_TRY(d2h(iv_missing, d_hi, (size_t)n_iv * 8, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    if (!fits) return fail(HYPO_E_WORKSPACE, "%llu intervals, room for %llu: call again with arrays of that size", (unsigned long long)n_iv, (unsigned long long)iv_cap);
+    return HYPO_OK;
+}
+
 int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_t* lo, const uint64_t* hi, uint32_t n_spans, uint64_t* total, uint64_t* missing) {
     HYPO_LOCKED();
     HYPO_ON_DEVICE();

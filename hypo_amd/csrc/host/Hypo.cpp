@@ -16,12 +16,14 @@
 namespace hypo {
 extern std::atomic<uint64_t> g_stage_counters[5];      // host/Contig.cpp
 
-// --vcf, --qv, --kmer-guard: the entry points Hypo::bind_extras bound and what the three keep from the reads to the last contig
+// --vcf, --qv, --qv-bed, --kmer-guard: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
 struct Extras {
     EditScriptsFn edit_fn = nullptr, guard_edit_fn = nullptr;
     QvReport qv;
     KmerGuard guard;
-    bool qv_on = false, guard_on = false, set_on = false;
+    bool qv_on = false, bed_on = false, guard_on = false;
+    bool ask_on = false;                                   // --qv or --qv-bed: every contig's texts are put to the set
+    bool set_on = false;                                   // ... or --kmer-guard: the set is built
     ReadSink qv_sink;                                      // (holds a pointer to qv: an Extras stays where it is)
     VcfStats vstats;
     Extras() = default; Extras(const Extras&) = delete;
@@ -137,6 +139,12 @@ void Hypo::polish() {
 
 // ---- once per run, before the batches ----------------------------------------------------------------------------------------
 void Hypo::bind_extras(Extras& ex) {
+    // --qv-bed: the track query, bound by name and only under the flag, and the set it asks.  Checked first: its error names it.
+    ex.bed_on = !_cFlags.qv_bed_filename.empty();
+    if (ex.bed_on && !(ex.qv.bind_track() && ex.qv.bind())) {
+        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv-bed needs hypo_gpu_kset_query_track and hypo_gpu_kset_begin / _add / _size / _end, which the device library does not provide\n");
+        std::exit(1);
+    }
     // --kmer-guard: the k-mer set of --qv (with or without its table), the spans query against it, and the edit scripts whether
     // or not a VCF is written.  Checked first, so that its error names everything the guard lacks.
     ex.guard_on = _cFlags.kmer_guard;
@@ -167,8 +175,9 @@ void Hypo::bind_extras(Extras& ex) {
         std::fprintf(stderr, "[Hypo::Hypo] Error: --qv needs hypo_gpu_kset_begin / _add / _size / _query / _end (C-ABI 11), which the device library does not provide\n");
         std::exit(1);
     }
-    ex.set_on = ex.qv_on || ex.guard_on;
-    if (ex.guard_on && !ex.qv_on) (void)ex.qv.bind();    // (the guard's check above found the entry points)
+    ex.ask_on = ex.qv_on || ex.bed_on;
+    ex.set_on = ex.ask_on || ex.guard_on;
+    if (ex.guard_on && !ex.ask_on) (void)ex.qv.bind();   // (the guard's check above found the entry points)
     if (ex.set_on) {
         // (sized for one k-mer per genome position; what the read errors add makes it grow)
         const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
@@ -683,7 +692,7 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
             writer_fatal("edit scripts");
     }
     // --qv: the draft and the polished text of every contig of the batch go to the k-mer set in one query on context 0
-    int qrc = ex.qv_on ? hypo_gpu_use_device(0) : HYPO_OK;
+    int qrc = ex.ask_on ? hypo_gpu_use_device(0) : HYPO_OK;
     // --kmer-guard: the batch's records are made first, their clusters judged by the set, and every contig is written as
     // its draft with the accepted records applied
     if (ex.guard_on) {
@@ -693,14 +702,14 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
                 ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;
                 if (ex.edit_fn) vcf_write_records(vfile, *_contigs[c], recs, &rejected);
                 _contigs[c]->release_after_output();
-                return ex.qv_on ? ex.qv.push(c, draft, text) : HYPO_OK;
+                return ex.ask_on ? ex.qv.push(c, draft, text) : HYPO_OK;
             });
-        if (grc == HYPO_OK && ex.qv_on) qrc = ex.qv.flush();
+        if (grc == HYPO_OK && ex.ask_on) qrc = ex.qv.flush();
         if (grc != HYPO_OK || qrc != HYPO_OK) writer_fatal(grc != HYPO_OK ? "k-mer guard" : "k-mer set query");
         return;
     }
     for (uint32_t c = initial_cid; c < final_cid; ++c) {
-        if (ex.qv_on) {
+        if (ex.ask_on) {
             const std::string text = _contigs[c]->polished_text();
             ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;      // (operator<<'s bytes)
             if (qrc == HYPO_OK) qrc = ex.qv.push(c, _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()), text);
@@ -710,7 +719,7 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
         if (edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, ex.vstats);
         _contigs[c]->release_after_output();
     }
-    if (ex.qv_on && qrc == HYPO_OK) qrc = ex.qv.flush();
+    if (ex.ask_on && qrc == HYPO_OK) qrc = ex.qv.flush();
     if (qrc != HYPO_OK) writer_fatal("k-mer set query");
 }
 
@@ -724,6 +733,11 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         std::vector<std::string> names;
         for (const auto& c : _contigs) names.push_back(c->get_name());
         ex.qv.write(out.open_qv(_cFlags.qv_filename), names);
+    }
+    if (ex.bed_on) {
+        std::vector<std::string> names;
+        for (const auto& c : _contigs) names.push_back(c->get_name());
+        ex.qv.write_track(out.open_bed(_cFlags.qv_bed_filename), names);
     }
     out.commit([&](RunOutputs::Which w) {
         if (w == RunOutputs::FASTA && ex.guard_on && ex.guard.by_record()) {
@@ -746,6 +760,11 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         if (w == RunOutputs::QV)
             std::fprintf(stdout, "[Hypo::Hypo] Info: QV %s (k = %u, %llu distinct read k-mers): draft %s, polished %s\n", _cFlags.qv_filename.c_str(), ex.qv.k(),
                          (unsigned long long)ex.qv.n_distinct(), ex.qv.draft_qv().c_str(), ex.qv.polished_qv().c_str());
+        if (w == RunOutputs::BED) {
+            const QvReport::TrackSums ts = ex.qv.track_sums();
+            std::fprintf(stdout, "[Hypo::Hypo] Info: QV track %s (k = %u): %llu intervals covering %llu bases, %llu missing k-mers\n", _cFlags.qv_bed_filename.c_str(), ex.qv.k(),
+                         (unsigned long long)ts.intervals, (unsigned long long)ts.bases, (unsigned long long)ts.missing);
+        }
     });
     stop("[Hypo:Hypo]: Writing results. ");
 }

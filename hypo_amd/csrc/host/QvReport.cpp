@@ -24,6 +24,11 @@ bool QvReport::bind() {
     return _begin && _add && _size && _query && _end;
 }
 
+bool QvReport::bind_track() {
+    _track = (decltype(_track))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_query_track");
+    return _track != nullptr;
+}
+
 int QvReport::begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes, size_t n_contigs) {
     const int rc = _begin(k, expected_distinct, max_bytes);
     if (rc != HYPO_OK) return rc;
@@ -55,8 +60,29 @@ int QvReport::flush() {
     if (_who.empty()) return HYPO_OK;
     const uint32_t n = (uint32_t)(_off.size() - 1);
     std::vector<uint64_t> total(n), missing(n);
-    const int rc = _query(_text.data(), _off.data(), n, total.data(), missing.data());
-    if (rc != HYPO_OK) return rc;
+    int rc;
+    if (_track) {
+        // intervals of the polished texts only (the odd sequences); a call that finds more than there is room for says how many
+        std::vector<uint8_t> want(n);
+        for (uint32_t s = 0; s < n; ++s) want[s] = s & 1;
+        const size_t room = 1024 + _text.size() / 1024;         // (a retry asks the set everything again: rare at one interval per kbp)
+        std::vector<uint64_t> iv_off(n + 1), start(room), end(room), count(room);
+        rc = _track(_text.data(), _off.data(), n, want.data(), total.data(), missing.data(), iv_off.data(), start.data(), end.data(), count.data(), start.size());
+        if (rc == HYPO_E_WORKSPACE) {
+            start.resize(iv_off[n]); end.resize(iv_off[n]); count.resize(iv_off[n]);
+            rc = _track(_text.data(), _off.data(), n, want.data(), total.data(), missing.data(), iv_off.data(), start.data(), end.data(), count.data(), start.size());
+        }
+        if (rc != HYPO_OK) return rc;
+        if (_intervals.size() < _rows.size()) _intervals.resize(_rows.size());
+        for (size_t i = 0; i < _who.size(); ++i) {
+            std::vector<Interval>& iv = _intervals[_who[i]];
+            iv.clear();
+            for (uint64_t j = iv_off[2 * i + 1]; j < iv_off[2 * i + 2]; ++j) iv.push_back(Interval{start[j], end[j], count[j]});
+        }
+    } else {
+        rc = _query(_text.data(), _off.data(), n, total.data(), missing.data());
+        if (rc != HYPO_OK) return rc;
+    }
     for (size_t i = 0; i < _who.size(); ++i) {
         Row& r = _rows[_who[i]];
         r.dt = total[2 * i]; r.dm = missing[2 * i]; r.pt = total[2 * i + 1]; r.pm = missing[2 * i + 1];
@@ -86,6 +112,19 @@ void QvReport::write(std::ostream& os, const std::vector<std::string>& names) co
     };
     for (size_t i = 0; i < names.size(); ++i) row(names[i], i < _rows.size() ? _rows[i] : Row());
     row("*", sums());
+}
+
+void QvReport::write_track(std::ostream& os, const std::vector<std::string>& names) const {
+    os << "#contig\tstart\tend\tmissing_kmers\n";
+    for (size_t i = 0; i < names.size() && i < _intervals.size(); ++i)
+        for (const Interval& iv : _intervals[i]) os << names[i] << '\t' << iv.start << '\t' << iv.end << '\t' << iv.missing << '\n';
+}
+
+QvReport::TrackSums QvReport::track_sums() const {
+    TrackSums s;
+    for (const auto& ivs : _intervals)
+        for (const Interval& iv : ivs) { ++s.intervals; s.bases += iv.end - iv.start; s.missing += iv.missing; }
+    return s;
 }
 
 }  // namespace hypo

@@ -18,6 +18,9 @@ class QvReport {
 public:
     // binds hypo_gpu_kset_* by name: only runs with --qv need them (false: the device library does not provide them)
     bool bind();
+    // --qv-bed: binds hypo_gpu_kset_query_track as well (false: the library does not provide it).  From then on flush() asks with it
+    // instead of hypo_gpu_kset_query, and keeps the intervals of every polished text.
+    bool bind_track();
     // the set on the calling thread's context; max_bytes 0 = the library's default cap
     int begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes, size_t n_contigs);
     ReadSink sink();
@@ -32,6 +35,10 @@ public:
     // the table: one row per contig in draft order, then the sums as contig "*"
     void write(std::ostream& os, const std::vector<std::string>& names) const;
     std::string draft_qv() const, polished_qv() const;       // of the sums
+    // the track: "#contig start end missing_kmers", one line per interval of a polished text, contigs in draft order
+    void write_track(std::ostream& os, const std::vector<std::string>& names) const;
+    struct TrackSums { uint64_t intervals = 0, bases = 0, missing = 0; };
+    TrackSums track_sums() const;
 private:
     struct Row { uint64_t dm = 0, dt = 0, pm = 0, pt = 0; };
     Row sums() const;
@@ -40,6 +47,9 @@ private:
     int (*_size)(uint64_t*, uint64_t*) = nullptr;
     int (*_query)(const char*, const uint64_t*, uint32_t, uint64_t*, uint64_t*) = nullptr;
     int (*_end)(void) = nullptr;
+    int (*_track)(const char*, const uint64_t*, uint32_t, const uint8_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t) = nullptr;
+    struct Interval { uint64_t start, end, missing; };
+    std::vector<std::vector<Interval>> _intervals;           // per contig, of its polished text
     bool _open = false;
     uint32_t _k = 0;
     uint64_t _n_distinct = 0;

@@ -1,4 +1,4 @@
-// RunOutputs.hpp — the result files of one run: the polished FASTA, the VCF (--vcf) and the QV table (--qv).
+// RunOutputs.hpp — the result files of one run: the polished FASTA, the VCF (--vcf), the QV table (--qv) and its track (--qv-bed).
 // The records go to <output>.tmp, which takes the output's name only when every contig is in it and the file closed without an error:
 // a run that fails half way (a device error, a bad record three batches in) leaves no truncated file under the name the caller asked
 // for, and an earlier result under that name stays what it was.  A failing run removes its .tmp on the way out.
@@ -13,7 +13,7 @@ namespace hypo {
 
 class RunOutputs {
 public:
-    enum Which { FASTA = 0, VCF = 1, QV = 2 };
+    enum Which { FASTA = 0, VCF = 1, QV = 2, BED = 3, N_FILES = 4 };
     RunOutputs() {
         static bool cleanup_registered = false;
         if (!cleanup_registered) { cleanup_registered = true; std::atexit(discard); }
@@ -24,18 +24,19 @@ public:
     std::ofstream& open_fasta(const std::string& name) { return open(FASTA, name); }
     std::ofstream& open_vcf(const std::string& name) { return open(VCF, name); }          // (the VCF follows the FASTA: <vcf>.tmp until the run succeeds)
     std::ofstream& open_qv(const std::string& name) { return open(QV, name); }
+    std::ofstream& open_bed(const std::string& name) { return open(BED, name); }
     std::ofstream& fasta() { return _f[FASTA].os; }
     std::ofstream& vcf() { return _f[VCF].os; }
-    // every file is closed and checked before any takes its name, FASTA, VCF, QV in this order (`renamed` after each); a file that
+    // every file is closed and checked before any takes its name, FASTA, VCF, QV, BED in this order (`renamed` after each); a file that
     // cannot take its name takes those before it with it
     void commit(const std::function<void(Which)>& renamed) {
-        static const char* const label[3] = {"output", "VCF", "QV"};
-        for (int i = 0; i < 3; ++i) {
+        static const char* const label[N_FILES] = {"output", "VCF", "QV", "QV track"};
+        for (int i = 0; i < N_FILES; ++i) {
             if (_f[i].tmp.empty()) continue;
             _f[i].os.close();
             if (!_f[i].os) { std::fprintf(stderr, "[Hypo::Hypo] Error: writing the %s file (%s) failed!\n", label[i], _f[i].tmp.c_str()); std::exit(1); }
         }
-        for (int i = 0; i < 3; ++i) {
+        for (int i = 0; i < N_FILES; ++i) {
             if (_f[i].tmp.empty()) continue;
             if (std::rename(_f[i].tmp.c_str(), _f[i].name.c_str()) != 0) {
                 std::fprintf(stderr, "[Hypo::Hypo] Error: could not move %s to %s!\n", _f[i].tmp.c_str(), _f[i].name.c_str());
@@ -54,10 +55,10 @@ public:
 
 private:
     struct File { std::string name, tmp; std::ofstream os; };      // tmp: <name>.tmp while the run is writing it
-    File _f[3];
+    File _f[N_FILES];
     static RunOutputs*& live() { static RunOutputs* p = nullptr; return p; }
     std::ofstream& open(Which w, const std::string& name) {
-        static const char* const label[3] = {"Output", "VCF", "QV"};
+        static const char* const label[N_FILES] = {"Output", "VCF", "QV", "QV track"};
         File& f = _f[w];
         f.name = name; f.tmp = name + ".tmp";
         f.os.open(f.tmp);

@@ -31,6 +31,7 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     bool kmer_guard = false;               // new, opt-in: --kmer-guard (edits whose k-mers the reads do not support are left out)
     bool guard_records = false;            // new, opt-in: --guard-records (the guard decides clustered edits record by record; implies --kmer-guard)
     uint32_t guard_records_max = 8;        // new, opt-in: --guard-records-max (2..12: clusters of more records are decided whole)
+    std::string qv_bed_filename;           // new, opt-in: --qv-bed <file> (where the polished text has k-mers no read contains, as BED intervals)
     uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
 };
 

@@ -31,7 +31,8 @@ const struct option long_options[] = {
     {"ccs-windows", no_argument, nullptr, 1004}, {"host-arms", no_argument, nullptr, 1005}, {"require-device", no_argument, nullptr, 1006},
     {"vcf", required_argument, nullptr, 1007}, {"qv", required_argument, nullptr, 1008}, {"qv-k", required_argument, nullptr, 1009},
     {"qv-mem", required_argument, nullptr, 1010}, {"kmer-guard", no_argument, nullptr, 1011},
-    {"guard-records", no_argument, nullptr, 1012}, {"guard-records-max", required_argument, nullptr, 1013}, {nullptr, 0, nullptr, 0}};
+    {"guard-records", no_argument, nullptr, 1012}, {"guard-records-max", required_argument, nullptr, 1013},
+    {"qv-bed", required_argument, nullptr, 1014}, {nullptr, 0, nullptr, 0}};
 
 // Same layout as the reference's usage() (src/main.cpp:363-430): "Usage: hypo <args>", the mandatory block, the optional
 // block, every flag as "-x, --long <type>" followed by what it does and its default.  The wording is this build's own.
@@ -72,6 +73,7 @@ void usage() {
         {"    --kmer-guard", "[MI355X build] Keep only the edits the k-mers of the short reads support: edits closer than k - 1 draft bases form a cluster, and a cluster that puts more k-mers no read contains into the contig than it removes is left out of the output (its VCF records get FILTER kmer instead of PASS; the polished columns of --qv describe the guarded text). Uses the k-mer set of --qv (--qv-k, --qv-mem) with or without --qv and --vcf.", "off"},
         {"    --guard-records", "[MI355X build] Implies --kmer-guard, and decides a cluster of 2 to --guard-records-max edits record by record: of all subsets of the cluster's records the one whose text lacks the fewest k-mers of the reads is kept (among equals the one with the most records), the other records get FILTER kmer. A single bad edit then no longer costs its neighbours. Larger clusters are accepted or rejected whole, as with --kmer-guard.", "off"},
         {"    --guard-records-max <int>", "[MI355X build] Most records of a cluster --guard-records still decides one by one, 2 to 12 (a cluster of n records has 2^n subsets). Without --guard-records it has no effect.", "8"},
+        {"    --qv-bed <str>", "[MI355X build] Also write where the polished text (with --kmer-guard the guarded text) still disagrees with the short reads, as a BED file: a base is covered when a k-mer that no read contains (the missing k-mers of --qv) lies over it, every maximal run of covered bases of a contig is one line, contig, start, end (0-based, end exclusive) and the number of missing k-mers inside. Per contig the fourth column adds up to polished_missing of --qv. Uses the k-mer set of --qv (--qv-k, --qv-mem) with or without --qv, --vcf and --kmer-guard; the intervals are found on the device.", "no BED"},
         {"-h, --help", "Print the usage.", nullptr}};
     std::printf("\n Usage: hypo <args>\n\n ** Mandatory args:\n");
     for (const auto& e : mandatory) std::printf("\t%s\n\t%s\n\n", e.flag, e.what);
@@ -193,6 +195,7 @@ int main(int argc, char** argv) {
                 if (end == optarg || *end || v < 2 || v > 12) { std::fprintf(stderr, "[Hypo::] Error: Arg Error: --guard-records-max must be between 2 and 12 (a cluster of n records has 2^n subsets) %s!\n", optarg); std::exit(1); }
                 flags.guard_records_max = (uint32_t)v; break;
             }
+            case 1014: flags.qv_bed_filename = optarg; break;
             case 1002: {
                 flags.devices.clear();
                 for (const char* c = optarg; *c;) { flags.devices.push_back(std::atoi(c)); while (*c && *c != ',') ++c; if (*c == ',') ++c; }

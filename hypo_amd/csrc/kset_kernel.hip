@@ -12,6 +12,8 @@
 //     lookup is a read-only probe that ends at the key or at a free slot.  Windows and misses are summed per wave and added per
 //     sequence with one 64-bit add each (a lane whose stretch crosses into another sequence adds what it has first); the sums are
 //     integers, so their order does not matter.
+//   * kset_track_*_kernel (below, with comments of their own): the query kernel keeping its per-window answers as bit flags, and the
+//     passes that turn the flags into sorted intervals of missing k-mers.
 //   * kset_spans_kernel / kset_variants_kernel (below, with comments of their own): many short spans, and every subset of a few
 //     edits of many short sites, a group of 32 or 64 lanes per item; read-only probes, no LDS, no atomics.
 // Forward progress: every probe loop runs at most `slots` steps.  A lane of the insert or rehash kernel that finds neither its key
@@ -124,9 +126,13 @@ __global__ void __launch_bounds__(KS_THREADS) kset_rehash_kernel(const uint64_t*
     ks_wave_add(ctr, n_new);
 }
 
-__global__ void __launch_bounds__(KS_THREADS) kset_query_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off,
-                                                                 uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* __restrict__ table,
-                                                                 uint64_t slots, unsigned long long* total, unsigned long long* missing) {
+// The body of kset_query_kernel, and with TRACK of kset_track_flags_kernel (further down), which also keeps what the lane knows
+// anyway: the missing bits of the 32 windows that start in its stretch, and which of its 32 bytes begin a sequence.
+template <bool TRACK>
+__device__ __forceinline__ void ks_query_body(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n_seqs, uint64_t n,
+                                              uint32_t k, const uint64_t* __restrict__ table, uint64_t slots, unsigned long long* total,
+                                              unsigned long long* missing, const uint8_t* __restrict__ want, uint32_t* __restrict__ miss_bits,
+                                              uint32_t* __restrict__ begin_bits) {
     __shared__ __attribute__((aligned(16))) uint8_t sb[KS_BLOCK_BYTES + KS_HALO];
     const uint64_t b0 = (uint64_t)blockIdx.x * KS_BLOCK_BYTES;
     ks_stage(sb, bytes, b0, n);
@@ -137,6 +143,7 @@ __global__ void __launch_bounds__(KS_THREADS) kset_query_kernel(const uint8_t* _
     uint32_t seq = 0;
     uint64_t seq_end = 0;
     unsigned long long tot = 0, mis = 0;
+    uint32_t mbits = 0, bbits = 0;                              // TRACK: bit j speaks of position b0 + s0 + j
     if (b0 + (uint64_t)s0 < n) {
         // the sequence that holds the lane's first byte: the last one that starts at or before it (empty ones before it are skipped)
         const uint64_t g0 = b0 + (uint64_t)s0;
@@ -144,6 +151,8 @@ __global__ void __launch_bounds__(KS_THREADS) kset_query_kernel(const uint8_t* _
         while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] > g0) hi = mid; else lo = mid + 1; }
         seq = lo - 1;
         seq_end = off[lo];
+        bool wanted = true;                                     // TRACK: the sequence in hand gets intervals
+        if (TRACK) { bbits = off[seq] == g0; wanted = !want || want[seq]; }
         uint64_t fwd = 0, rc = 0;
         uint32_t run = 0;
         for (int p = s0; p < last; ++p) {
@@ -153,13 +162,24 @@ __global__ void __launch_bounds__(KS_THREADS) kset_query_kernel(const uint8_t* _
                 if (tot) { atomicAdd(total + seq, tot); if (mis) atomicAdd(missing + seq, mis); }
                 tot = mis = 0; run = 0;
                 do { ++seq; seq_end = off[seq + 1]; } while (seq_end == g);
+                if (TRACK) { if (p < s0 + KS_STRETCH) bbits |= 1u << (p - s0); wanted = !want || want[seq]; }
             }
             const uint32_t c = ks_base_code(sb[p]);
             if (c > 3) { run = 0; continue; }
             fwd = ((fwd << 2) | c) & mask;
             rc = (rc >> 2) | ((uint64_t)(3u - c) << rsh);
-            if (++run >= k) { ++tot; if (!ks_contains(table, slots, fwd < rc ? fwd : rc)) ++mis; }
+            if (++run >= k) {
+                ++tot;
+                if (!ks_contains(table, slots, fwd < rc ? fwd : rc)) {
+                    ++mis;
+                    if (TRACK && wanted) mbits |= 1u << (p - ((int)k - 1) - s0);   // the window's start: s0 <= p - k + 1 < s0 + KS_STRETCH
+                }
+            }
         }
+    }
+    if (TRACK) {                                                // every lane of the grid stores its two words, zero beyond n
+        const uint64_t w = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x;
+        miss_bits[w] = mbits; begin_bits[w] = bbits;
     }
     // per wave: the lanes that ended in the sequence of the wave's first lane are summed and added once, the others add their own
     const uint32_t lead = __shfl(seq, 0);
@@ -168,6 +188,193 @@ __global__ void __launch_bounds__(KS_THREADS) kset_query_kernel(const uint8_t* _
     for (int o = 32; o > 0; o >>= 1) { t += __shfl_xor(t, o); m += __shfl_xor(m, o); }
     if ((threadIdx.x & 63) == 0 && t) { atomicAdd(total + lead, t); if (m) atomicAdd(missing + lead, m); }
     if (!same && tot) { atomicAdd(total + seq, tot); if (mis) atomicAdd(missing + seq, mis); }
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_query_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off,
+                                                                 uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* __restrict__ table,
+                                                                 uint64_t slots, unsigned long long* total, unsigned long long* missing) {
+    ks_query_body<false>(bytes, off, n_seqs, n, k, table, slots, total, missing, nullptr, nullptr, nullptr);
+}
+
+// ---- where the missing windows are (hypo --qv-bed; DESIGN.md "k-mer QV track") -------------------------------------------------------
+// Flag word w speaks of positions [32 w, 32 w + 32) of the call's bytes: miss_bits has a bit per missing window START (of a sequence
+// that wants intervals), begin_bits a bit per first byte of a sequence.  kset_track_flags_kernel is the query kernel and stores the
+// two words of every lane of its grid, which has one workgroup more than the bytes need when n is a multiple of KS_BLOCK_BYTES:
+// position n, where the last interval may END, has a word too.  Everything after it is arithmetic on those words:
+//   * a base i is covered when a missing window starts in [i - k + 1, i].  Windows never cross a sequence end, so neither does the
+//     cover of one, and k <= 31 < 32: the covered bits of word w are an OR of k shifts of the 64 bits (miss[w] : miss[w - 1]),
+//     done with log2 k doubling steps.
+//   * an interval STARTS at a covered i whose predecessor is not covered or which begins a sequence, and ENDS (exclusive) at an i whose
+//     predecessor is covered and which is not covered or begins a sequence.  Intervals are disjoint and ascending, so the j-th start
+//     and the j-th end of the call belong together, and the interval's missing windows are the missing bits in front of its end less
+//     those in front of its start: no lane walks an interval.
+//   * kset_track_count_kernel: per workgroup the number of starts, ends and missing bits of its 256 words, one plain store.
+//   * kset_track_scan_kernel: ONE workgroup turns those into exclusive prefixes, a tile of KS_SCAN_THREADS sums per pass, and leaves
+//     the call's totals behind the last one.
+//   * kset_track_emit_kernel: the same marks again (cheaper than keeping them), a workgroup-wide exclusive scan, and every start /
+//     end bit writes its position and the missing bits in front of it into the slot of its rank.
+//   * kset_track_offsets_kernel / kset_track_finish_kernel: iv_off[s] = the intervals that start before off[s] (a binary search per
+//     sequence); then per interval the two counts become one and the positions become relative to the interval's sequence.
+// No kernel waits for another workgroup, none uses an atomic, and every value is a function of the flag words alone.
+// Bounds: flag words are indexed below n_words = gridDim.x * KS_THREADS of the flags kernel (the count and emit kernels are launched
+// with the same grid); sums below n_blocks, prefixes below 3 (n_blocks + 1); interval slots below `cap` (checked per store: the
+// caller sizes the arrays from the totals of the scan); iv_off below n_seqs + 1.  Loops: doubling steps <= 5, set bits of a word
+// <= 32, scan passes = ceil(n_blocks / KS_SCAN_THREADS), binary searches <= 64 steps.
+constexpr int KS_SCAN_THREADS = KS_THREADS;
+
+__global__ void __launch_bounds__(KS_THREADS) kset_track_flags_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off,
+                                                                       uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* __restrict__ table,
+                                                                       uint64_t slots, unsigned long long* total, unsigned long long* missing,
+                                                                       const uint8_t* __restrict__ want, uint32_t* __restrict__ miss_bits,
+                                                                       uint32_t* __restrict__ begin_bits) {
+    ks_query_body<true>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits);
+}
+
+// the start and end bits of a word from the missing bits of the word before it and its own, and its begin bits
+__device__ __forceinline__ void ks_track_marks(uint32_t m_prev, uint32_t m_cur, uint32_t begins, uint32_t k, uint32_t& starts, uint32_t& ends) {
+    uint64_t r = ((uint64_t)m_cur << 32) | m_prev;              // bit 32 + j: position j of the word
+    uint32_t width = 1;                                         // r holds the OR of its shifts by 0 .. width - 1
+    for (; 2 * width <= k; width *= 2) r |= r << width;
+    r |= r << (k - width);                                      // (k - width < width: no gap)
+    const uint32_t cov = (uint32_t)(r >> 32), cov_before = (uint32_t)(r >> 31);
+    starts = cov & (~cov_before | begins);
+    ends = cov_before & (~cov | begins);
+}
+
+// A workgroup has 8192 positions, so its three counts fit 16 bits each with room to spare and travel as one 64-bit word:
+// starts | ends << 16 | missing bits << 32.
+__device__ __forceinline__ uint64_t ks_track_word_counts(const uint32_t* __restrict__ miss_bits, const uint32_t* __restrict__ begin_bits, uint64_t w,
+                                                         uint32_t k, uint32_t& m_cur, uint32_t& starts, uint32_t& ends) {
+    const uint32_t m_prev = w ? miss_bits[w - 1] : 0u;
+    m_cur = miss_bits[w];
+    ks_track_marks(m_prev, m_cur, begin_bits[w], k, starts, ends);
+    return (uint64_t)__popc(starts) | ((uint64_t)__popc(ends) << 16) | ((uint64_t)__popc(m_cur) << 32);
+}
+
+__device__ __forceinline__ uint64_t ks_wave_inclusive(uint64_t v) {
+    const uint32_t lane = threadIdx.x & 63;
+    for (int o = 1; o < 64; o <<= 1) { const uint64_t u = __shfl_up(v, o); if (lane >= (uint32_t)o) v += u; }
+    return v;
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_track_count_kernel(const uint32_t* __restrict__ miss_bits, const uint32_t* __restrict__ begin_bits,
+                                                                       uint32_t k, uint64_t* __restrict__ sums) {
+    __shared__ uint64_t part[KS_THREADS / 64];
+    uint32_t m_cur, starts, ends;
+    uint64_t v = ks_track_word_counts(miss_bits, begin_bits, (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x, k, m_cur, starts, ends);
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = v;
+    __syncthreads();
+    if (threadIdx.x == 0) sums[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
+}
+
+// pre[3 b + f]: field f (0 starts, 1 ends, 2 missing bits) summed over the workgroups before b; pre[3 n_blocks + f]: the call's totals
+__global__ void __launch_bounds__(KS_SCAN_THREADS) kset_track_scan_kernel(const uint64_t* __restrict__ sums, uint32_t n_blocks, uint64_t* __restrict__ pre) {
+    constexpr int WAVES = KS_SCAN_THREADS / 64;
+    __shared__ uint64_t part[WAVES][3];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint64_t carry[3] = {0, 0, 0};
+    for (uint32_t base = 0; base < n_blocks; base += KS_SCAN_THREADS) {
+        const uint32_t i = base + threadIdx.x;
+        const uint64_t packed = i < n_blocks ? sums[i] : 0;
+        const uint64_t v[3] = {packed & 0xffffu, (packed >> 16) & 0xffffu, packed >> 32};
+        uint64_t inc[3];
+        for (int f = 0; f < 3; ++f) inc[f] = ks_wave_inclusive(v[f]);
+        if (lane == 63) for (int f = 0; f < 3; ++f) part[wave][f] = inc[f];
+        __syncthreads();
+        for (int f = 0; f < 3; ++f) {
+            uint64_t before = carry[f], all = 0;
+            for (int x = 0; x < WAVES; ++x) { const uint64_t t = part[x][f]; if ((uint32_t)x < wave) before += t; all += t; }
+            if (i < n_blocks) pre[3 * (uint64_t)i + f] = before + inc[f] - v[f];
+            carry[f] += all;
+        }
+        __syncthreads();                                        // (part is written again in the next pass)
+    }
+    if (threadIdx.x == 0) for (int f = 0; f < 3; ++f) pre[3 * (uint64_t)n_blocks + f] = carry[f];
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_track_emit_kernel(const uint32_t* __restrict__ miss_bits, const uint32_t* __restrict__ begin_bits,
+                                                                      uint32_t k, const uint64_t* __restrict__ pre, uint64_t cap,
+                                                                      uint64_t* __restrict__ iv_start, uint64_t* __restrict__ iv_end,
+                                                                      uint64_t* __restrict__ cnt_lo, uint64_t* __restrict__ cnt_hi) {
+    __shared__ uint64_t part[KS_THREADS / 64];
+    const uint64_t w = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x;
+    uint32_t m_cur, starts, ends;
+    const uint64_t v = ks_track_word_counts(miss_bits, begin_bits, w, k, m_cur, starts, ends);
+    const uint64_t inc = ks_wave_inclusive(v);
+    if ((threadIdx.x & 63) == 63) part[threadIdx.x >> 6] = inc;
+    __syncthreads();
+    uint64_t ex = inc - v;                                      // what the workgroup's lanes before this one counted
+    for (uint32_t x = 0; x < (threadIdx.x >> 6); ++x) ex += part[x];
+    uint64_t rank_s = pre[3 * (uint64_t)blockIdx.x] + (ex & 0xffffu), rank_e = pre[3 * (uint64_t)blockIdx.x + 1] + ((ex >> 16) & 0xffffu);
+    const uint64_t m_before = pre[3 * (uint64_t)blockIdx.x + 2] + (ex >> 32);
+    while (starts) {
+        const uint32_t j = (uint32_t)__ffs(starts) - 1;
+        starts &= starts - 1;
+        if (rank_s < cap) { iv_start[rank_s] = w * 32 + j; cnt_lo[rank_s] = m_before + __popc(m_cur & ((1u << j) - 1u)); }
+        ++rank_s;
+    }
+    while (ends) {
+        const uint32_t j = (uint32_t)__ffs(ends) - 1;
+        ends &= ends - 1;
+        if (rank_e < cap) { iv_end[rank_e] = w * 32 + j; cnt_hi[rank_e] = m_before + __popc(m_cur & ((1u << j) - 1u)); }
+        ++rank_e;
+    }
+}
+
+// iv_off[s] = the first interval that starts at or after off[s], s = 0 .. n_seqs (iv_start ascends)
+__global__ void __launch_bounds__(KS_THREADS) kset_track_offsets_kernel(const uint64_t* __restrict__ off, uint32_t n_seqs, const uint64_t* __restrict__ iv_start,
+                                                                         uint64_t n_iv, uint64_t* __restrict__ iv_off) {
+    const uint64_t s = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x;
+    if (s > n_seqs) return;
+    const uint64_t at = off[s];
+    uint64_t lo = 0, hi = n_iv;
+    while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (iv_start[mid] >= at) hi = mid; else lo = mid + 1; }
+    iv_off[s] = lo;
+}
+
+// per interval: cnt_hi becomes its missing windows, its positions become relative to the sequence that holds its start
+__global__ void __launch_bounds__(KS_THREADS) kset_track_finish_kernel(const uint64_t* __restrict__ off, uint32_t n_seqs, uint64_t n_iv,
+                                                                        uint64_t* __restrict__ iv_start, uint64_t* __restrict__ iv_end,
+                                                                        const uint64_t* __restrict__ cnt_lo, uint64_t* __restrict__ cnt_hi) {
+    const uint64_t j = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x;
+    if (j >= n_iv) return;
+    const uint64_t at = iv_start[j];
+    uint32_t lo = 1, hi = n_seqs;                               // first index in [1, n_seqs] with off[index] > at (off[n_seqs] = n > at)
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] > at) hi = mid; else lo = mid + 1; }
+    const uint64_t base = off[lo - 1];
+    iv_start[j] = at - base;
+    iv_end[j] -= base;
+    cnt_hi[j] -= cnt_lo[j];
+}
+
+uint32_t kset_track_blocks(uint64_t n) { return (uint32_t)(n / KS_BLOCK_BYTES + 1); }
+
+hipError_t kset_track_count_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table, uint64_t slots,
+                                unsigned long long* total, unsigned long long* missing, const uint8_t* want, uint32_t* miss_bits, uint32_t* begin_bits,
+                                uint64_t* sums, uint64_t* pre, hipStream_t st) {
+    const uint32_t blocks = kset_track_blocks(n);
+    kset_track_flags_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    kset_track_count_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(miss_bits, begin_bits, k, sums);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    kset_track_scan_kernel<<<dim3(1), dim3(KS_SCAN_THREADS), 0, st>>>(sums, blocks, pre);
+    return hipGetLastError();
+}
+
+hipError_t kset_track_emit_run(const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint32_t* miss_bits, const uint32_t* begin_bits,
+                               const uint64_t* pre, uint64_t n_iv, uint64_t* iv_off, uint64_t* iv_start, uint64_t* iv_end, uint64_t* cnt_lo,
+                               uint64_t* cnt_hi, hipStream_t st) {
+    hipError_t e = hipSuccess;
+    if (n_iv) {
+        kset_track_emit_kernel<<<dim3(kset_track_blocks(n)), dim3(KS_THREADS), 0, st>>>(miss_bits, begin_bits, k, pre, n_iv, iv_start, iv_end, cnt_lo, cnt_hi);
+        if ((e = hipGetLastError()) != hipSuccess) return e;
+    }
+    kset_track_offsets_kernel<<<dim3(n_seqs / KS_THREADS + 1), dim3(KS_THREADS), 0, st>>>(off, n_seqs, iv_start, n_iv, iv_off);
+    if ((e = hipGetLastError()) != hipSuccess || !n_iv) return e;
+    kset_track_finish_kernel<<<dim3((uint32_t)((n_iv + KS_THREADS - 1) / KS_THREADS)), dim3(KS_THREADS), 0, st>>>(off, n_seqs, n_iv, iv_start, iv_end, cnt_lo, cnt_hi);
+    return hipGetLastError();
 }
 
 // ---- many short spans (hypo --kmer-guard; DESIGN.md "k-mer guard") -------------------------------------------------------------------

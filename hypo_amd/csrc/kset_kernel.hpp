@@ -23,6 +23,20 @@ hipError_t kset_rehash_run(const uint64_t* old_table, uint64_t old_slots, uint64
 // ACGTacgt only, missing[s] += those whose canonical k-mer is not in the table.  total / missing must be zeroed by the caller.
 hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table,
                           uint64_t slots, unsigned long long* total, unsigned long long* missing, hipStream_t st);
+// The same query, and where the missing windows are (hypo --qv-bed; DESIGN.md "k-mer QV track"), in two steps with the caller
+// reading pre[3 blocks .. 3 blocks + 3) = (intervals, intervals, missing windows of wanted sequences) in between, blocks =
+// kset_track_blocks(n).  want: NULL or n_seqs bytes, 0 = no intervals for that sequence.  Work space: miss_bits / begin_bits of
+// 256 * blocks words each, sums of blocks and pre of 3 * (blocks + 1) 64-bit words; none needs clearing.
+//   count: total / missing as kset_query_run (zeroed by the caller), the flag words, their per-workgroup sums and the prefixes.
+//   emit:  iv_off[n_seqs + 1], and n_iv intervals in ascending order: iv_start / iv_end relative to the interval's sequence,
+//          cnt_hi = its missing windows (cnt_lo is work space).  Every array has n_iv entries; n_iv must be the total read from pre.
+uint32_t kset_track_blocks(uint64_t n);
+hipError_t kset_track_count_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table, uint64_t slots,
+                                unsigned long long* total, unsigned long long* missing, const uint8_t* want, uint32_t* miss_bits, uint32_t* begin_bits,
+                                uint64_t* sums, uint64_t* pre, hipStream_t st);
+hipError_t kset_track_emit_run(const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint32_t* miss_bits, const uint32_t* begin_bits,
+                               const uint64_t* pre, uint64_t n_iv, uint64_t* iv_off, uint64_t* iv_start, uint64_t* iv_end, uint64_t* cnt_lo,
+                               uint64_t* cnt_hi, hipStream_t st);
 // n_items pieces of spans: item i is bytes[item_lo[i], item_lo[i] + item_len[i]), no window crosses its ends; out[i] = (its windows
 // made of ACGTacgt only, those not in the table).  A group of `group` lanes (32 or 64) owns an item; the caller cuts a span into
 // items of at most KSET_SPAN_PIECE windows (consecutive items overlap by k - 1 bytes) and adds their results up.

@@ -452,6 +452,20 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
     const uint64_t* eb, const uint64_t* ee, const uint64_t* ao, const uint32_t* al,
     uint32_t* best_mask, uint64_t* best_total, uint64_t* best_missing,
     uint64_t* var_total /* may be NULL */, uint64_t* var_missing /* may be NULL */);
+/* hypo_gpu_kset_query, and WHERE the missing windows are (hypo --qv-bed; DESIGN.md "k-mer QV track").  Additive to ABI 11: callers
+ * bind it by name.  bytes, off, n_seqs, total and missing are those of hypo_gpu_kset_query and receive the same values.  A base of
+ * a sequence is covered when a missing window contains it; the intervals of a sequence are its maximal runs of covered bases
+ * [start, end), relative to off[s], so missing windows that overlap or abut share one, end - start >= k, and start[j + 1] > end[j].
+ * An interval never joins two sequences.  iv_missing = the missing windows that start in [start, end - k]; over a sequence they add
+ * up to missing[s].  want (NULL: every sequence): want[s] == 0 gives sequence s no intervals; total and missing do not depend on
+ * it.  iv_off[n_seqs + 1] (iv_off[0] = 0): the intervals of s are [iv_off[s], iv_off[s + 1]) of iv_start / iv_end / iv_missing, in
+ * ascending order.  iv_off[n_seqs] > iv_cap: HYPO_E_WORKSPACE with total, missing and iv_off filled and the three arrays untouched;
+ * call again with room.  iv_cap == 0 (the three pointers may then be NULL) is the counting call; it returns 0 when there is no
+ * interval.  HYPO_E_INVALID: off[] decreasing, a NULL required pointer with n_seqs > 0, no set (as hypo_gpu_kset_query); a refused
+ * call changes nothing.  The answer is a function of the input alone.  Synchronous, on the calling thread's context. */
+int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n_seqs, const uint8_t* want /* may be NULL */,
+    uint64_t* total, uint64_t* missing, uint64_t* iv_off /* n_seqs + 1 */,
+    uint64_t* iv_start, uint64_t* iv_end, uint64_t* iv_missing, uint64_t iv_cap);
 
 /* Kernel timing with HIP events on the stream the kernels run on ----------------------------------
  * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each records
