@@ -307,7 +307,8 @@ hypo::PoaParams make_params(const HypoScoreParams* s, const HypoWindowBatch* in,
 
 struct Carver {                                       // lays arrays out in one device buffer, 256-byte aligned
     size_t at = 0;
-    size_t take(size_t bytes) { const size_t o = at; at += (bytes + 255) / 256 * 256; return o; }
+    static size_t pad(size_t bytes) { return (bytes + 255) / 256 * 256; }
+    size_t take(size_t bytes) { const size_t o = at; at += pad(bytes); return o; }
 };
 
 
@@ -1123,6 +1124,59 @@ int ks_resize(Ctx::KSet& ks, uint64_t slots, hipStream_t st) {
     if (slots > ks.peak_slots) ks.peak_slots = slots;
     return HYPO_OK;
 }
+// The entry points that need a live set: the lock, the device, `ks`.
+#define HYPO_KSET_ENTRY() \
+    HYPO_LOCKED(); \
+    HYPO_ON_DEVICE(); \
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called"); \
+    Ctx::KSet& ks = g_ctx.ks; \
+    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)")
+
+// rel[i] = off[i] - off[0], i = 0 .. n_seqs, of offsets that must not decrease
+int ks_rel_offsets(const uint64_t* off, uint32_t n_seqs, std::vector<uint64_t>& rel) {
+    rel.resize((size_t)n_seqs + 1);
+    for (uint32_t i = 0; i <= n_seqs; ++i) {
+        if (off[i] < off[0] || (i && off[i] < off[i - 1])) return fail(HYPO_E_INVALID, "off[] must not decrease (entry %u)", i);
+        rel[i] = off[i] - off[0];
+    }
+    return HYPO_OK;
+}
+
+// What the two sequence queries do alike once their arguments are checked, for the n = rel[n_seqs] > 0 bytes at `bytes`: the
+// arenas (ks.off of off_bytes, the offsets first), bytes and offsets up, zeroed sums, the caller's kernels through
+// launch(d_off, d_tot, d_mis), total / missing on their way down (the caller synchronises).
+template <class Launch>
+int ks_query_seqs(Ctx::KSet& ks, const char* bytes, const std::vector<uint64_t>& rel, uint32_t n_seqs, size_t off_bytes, uint64_t* total,
+                  uint64_t* missing, Launch launch) {
+    hipStream_t st = g_ctx.stream;
+    const uint64_t n = rel[n_seqs];
+    HIP_TRY(ks.in.alloc(n));
+    HIP_TRY(ks.off.alloc(off_bytes));
+    HIP_TRY(ks.res.alloc((size_t)n_seqs * 16));
+    unsigned long long* d_tot = (unsigned long long*)ks.res.p;
+    unsigned long long* d_mis = d_tot + n_seqs;
+    HIP_TRY(h2d(ks.in.p, bytes, n, st));
+    HIP_TRY(hipMemcpyAsync(ks.off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(ks.res.p, 0, (size_t)n_seqs * 16, st));
+    HIP_TRY(launch((char*)ks.off.p, d_tot, d_mis));
+    HIP_TRY(hipMemcpyAsync(total, d_tot, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(missing, d_mis, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    return HYPO_OK;
+}
+
+// A run of n_win windows as pieces of at most KSET_SPAN_PIECE: f(first window, the piece's bytes), each piece with the k - 1 bytes
+// its last window needs.
+uint64_t ks_n_pieces(uint64_t n_win) { return (n_win + hypo::KSET_SPAN_PIECE - 1) / hypo::KSET_SPAN_PIECE; }
+template <class F> void ks_pieces(uint64_t n_win, uint32_t k, F f) {
+    for (uint64_t w = 0; w < n_win; w += hypo::KSET_SPAN_PIECE)
+        f(w, (uint32_t)(n_win - w < hypo::KSET_SPAN_PIECE ? n_win - w : hypo::KSET_SPAN_PIECE) + k - 1);
+}
+
+int ks_group() {                                       // lanes per item; HYPO_KSET_SPAN_GROUP = 32 | 64 overrides (profiles/guard_rate.py)
+    const char* g = getenv("HYPO_KSET_SPAN_GROUP");
+    const int v = g ? atoi(g) : 0;
+    return v == 64 || v == 32 ? v : hypo::KSET_SPAN_GROUP;
+}
 }  // namespace
 
 extern "C" {
@@ -1149,11 +1203,7 @@ int hypo_gpu_kset_begin(uint32_t k, uint64_t expected_distinct, uint64_t max_byt
 }
 
 int hypo_gpu_kset_add(const char* bytes, uint64_t n) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    Ctx::KSet& ks = g_ctx.ks;
-    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    HYPO_KSET_ENTRY();
     if (n < ks.k) return HYPO_OK;                                       // holds no k-mer
     if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
     hipStream_t st = g_ctx.stream;
@@ -1200,53 +1250,31 @@ int hypo_gpu_kset_size(uint64_t* n_distinct, uint64_t* table_bytes) {
 }
 
 int hypo_gpu_kset_query(const char* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t* total, uint64_t* missing) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    Ctx::KSet& ks = g_ctx.ks;
-    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    HYPO_KSET_ENTRY();
     if (!n_seqs) return HYPO_OK;
     if (!off || !total || !missing) return fail(HYPO_E_INVALID, "NULL buffer");
-    std::vector<uint64_t> rel((size_t)n_seqs + 1);
-    for (uint32_t i = 0; i <= n_seqs; ++i) {
-        if (off[i] < off[0] || (i && off[i] < off[i - 1])) return fail(HYPO_E_INVALID, "off[] must not decrease (entry %u)", i);
-        rel[i] = off[i] - off[0];
-    }
-    const uint64_t n = rel[n_seqs];
+    std::vector<uint64_t> rel;
+    if (const int rc = ks_rel_offsets(off, n_seqs, rel)) return rc;
     for (uint32_t i = 0; i < n_seqs; ++i) total[i] = missing[i] = 0;
-    if (!n) return HYPO_OK;
+    if (!rel[n_seqs]) return HYPO_OK;
     if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
     hipStream_t st = g_ctx.stream;
-    HIP_TRY(ks.in.alloc(n));
-    HIP_TRY(ks.off.alloc(rel.size() * 8));
-    HIP_TRY(ks.res.alloc((size_t)n_seqs * 16));
-    unsigned long long* d_tot = (unsigned long long*)ks.res.p;
-    unsigned long long* d_mis = d_tot + n_seqs;
-    HIP_TRY(h2d(ks.in.p, bytes + off[0], n, st));
-    HIP_TRY(hipMemcpyAsync(ks.off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(ks.res.p, 0, (size_t)n_seqs * 16, st));
-    HIP_TRY(hypo::kset_query_run((const uint8_t*)ks.in.p, (const uint64_t*)ks.off.p, n_seqs, n, ks.k, ks.table, ks.slots, d_tot, d_mis, st));
-    HIP_TRY(hipMemcpyAsync(total, d_tot, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(missing, d_mis, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    const int rc = ks_query_seqs(ks, bytes + off[0], rel, n_seqs, rel.size() * 8, total, missing, [&](char* d_off, unsigned long long* d_tot, unsigned long long* d_mis) {
+        return hypo::kset_query_run((const uint8_t*)ks.in.p, (const uint64_t*)d_off, n_seqs, rel[n_seqs], ks.k, ks.table, ks.slots, d_tot, d_mis, st);
+    });
+    if (rc != HYPO_OK) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return HYPO_OK;
 }
 
 int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n_seqs, const uint8_t* want, uint64_t* total, uint64_t* missing,
                               uint64_t* iv_off, uint64_t* iv_start, uint64_t* iv_end, uint64_t* iv_missing, uint64_t iv_cap) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    Ctx::KSet& ks = g_ctx.ks;
-    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    HYPO_KSET_ENTRY();
     if (iv_cap && (!iv_start || !iv_end || !iv_missing)) return fail(HYPO_E_INVALID, "NULL buffer");
     if (!n_seqs) { if (iv_off) iv_off[0] = 0; return HYPO_OK; }
     if (!off || !total || !missing || !iv_off) return fail(HYPO_E_INVALID, "NULL buffer");
-    std::vector<uint64_t> rel((size_t)n_seqs + 1);
-    for (uint32_t i = 0; i <= n_seqs; ++i) {
-        if (off[i] < off[0] || (i && off[i] < off[i - 1])) return fail(HYPO_E_INVALID, "off[] must not decrease (entry %u)", i);
-        rel[i] = off[i] - off[0];
-    }
+    std::vector<uint64_t> rel;
+    if (const int rc = ks_rel_offsets(off, n_seqs, rel)) return rc;
     const uint64_t n = rel[n_seqs];
     if (n && !bytes) return fail(HYPO_E_INVALID, "NULL buffer");
     for (uint32_t i = 0; i < n_seqs; ++i) total[i] = missing[i] = 0;
@@ -1254,49 +1282,42 @@ int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n
     if (!n) return HYPO_OK;
     hipStream_t st = g_ctx.stream;
     // `in`: the bytes.  `off`: the offsets, the want bytes, then what indexes the bytes: the two flag words per 32 positions, the
-    // per-workgroup sums and their prefixes.  `res`: total / missing first; once those and the number of intervals are on the
-    // host, iv_off and the intervals (a grown arena loses nothing that is still needed).
+    // per-workgroup sums and their prefixes.  `res`: total / missing first.
     const uint32_t blocks = hypo::kset_track_blocks(n);
     const size_t n_words = (size_t)blocks * 256;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t at_want = pad(rel.size() * 8), at_miss = at_want + pad(n_seqs), at_begin = at_miss + pad(n_words * 4),
-                 at_sums = at_begin + pad(n_words * 4), at_pre = at_sums + pad((size_t)blocks * 8), off_bytes = at_pre + pad(((size_t)blocks + 1) * 24);
-    HIP_TRY(ks.in.alloc(n));
-    HIP_TRY(ks.off.alloc(off_bytes));
-    HIP_TRY(ks.res.alloc((size_t)n_seqs * 16));
+    Carver co;
+    co.take(rel.size() * 8);
+    const size_t at_want = co.take(n_seqs), at_miss = co.take(n_words * 4), at_begin = co.take(n_words * 4), at_sums = co.take((size_t)blocks * 8),
+                 at_pre = co.take(((size_t)blocks + 1) * 24);
+    const int rc = ks_query_seqs(ks, bytes + off[0], rel, n_seqs, co.at, total, missing, [&](char* d, unsigned long long* d_tot, unsigned long long* d_mis) {
+        if (want) { const hipError_t e = hipMemcpyAsync(d + at_want, want, n_seqs, hipMemcpyHostToDevice, st); if (e != hipSuccess) return e; }
+        return hypo::kset_track_count_run((const uint8_t*)ks.in.p, (const uint64_t*)d, n_seqs, n, ks.k, ks.table, ks.slots, d_tot, d_mis,
+                                          want ? (const uint8_t*)(d + at_want) : nullptr, (uint32_t*)(d + at_miss), (uint32_t*)(d + at_begin),
+                                          (uint64_t*)(d + at_sums), (uint64_t*)(d + at_pre), st);
+    });
+    if (rc != HYPO_OK) return rc;
     char* const d_off = (char*)ks.off.p;
-    unsigned long long* d_tot = (unsigned long long*)ks.res.p;
-    unsigned long long* d_mis = d_tot + n_seqs;
     const uint64_t* d_pre = (const uint64_t*)(d_off + at_pre);
-    HIP_TRY(h2d(ks.in.p, bytes + off[0], n, st));
-    HIP_TRY(hipMemcpyAsync(d_off, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-    if (want) HIP_TRY(hipMemcpyAsync(d_off + at_want, want, n_seqs, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(ks.res.p, 0, (size_t)n_seqs * 16, st));
-    HIP_TRY(hypo::kset_track_count_run((const uint8_t*)ks.in.p, (const uint64_t*)d_off, n_seqs, n, ks.k, ks.table, ks.slots, d_tot, d_mis,
-                                       want ? (const uint8_t*)(d_off + at_want) : nullptr, (uint32_t*)(d_off + at_miss), (uint32_t*)(d_off + at_begin),
-                                       (uint64_t*)(d_off + at_sums), (uint64_t*)(d_off + at_pre), st));
     uint64_t sums[3] = {0, 0, 0};                               // starts, ends, missing windows of the wanted sequences
-    HIP_TRY(hipMemcpyAsync(total, d_tot, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(missing, d_mis, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipMemcpyAsync(sums, d_pre + 3 * (size_t)blocks, 24, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if (sums[0] != sums[1]) return fail(HYPO_E_HIP, "k-mer track: internal error: %llu interval starts, %llu ends", (unsigned long long)sums[0], (unsigned long long)sums[1]);
+    // total / missing and the number of intervals are on the host: `res` now takes iv_off and the intervals (a grown arena loses
+    // nothing that is still needed)
     const uint64_t n_iv = sums[0];
-    const size_t at_iv = pad(rel.size() * 8), iv_bytes = pad((size_t)n_iv * 8);
-    HIP_TRY(ks.res.alloc(at_iv + 4 * iv_bytes));
+    Carver cv;
+    cv.take(rel.size() * 8);
+    const size_t o_start = cv.take((size_t)n_iv * 8), o_end = cv.take((size_t)n_iv * 8), o_lo = cv.take((size_t)n_iv * 8), o_hi = cv.take((size_t)n_iv * 8);
+    HIP_TRY(ks.res.alloc(cv.at));
     char* const d_res = (char*)ks.res.p;
-    uint64_t* const d_start = (uint64_t*)(d_res + at_iv);
-    uint64_t* const d_end = (uint64_t*)(d_res + at_iv + iv_bytes);
-    uint64_t* const d_lo = (uint64_t*)(d_res + at_iv + 2 * iv_bytes);
-    uint64_t* const d_hi = (uint64_t*)(d_res + at_iv + 3 * iv_bytes);
     HIP_TRY(hypo::kset_track_emit_run((const uint64_t*)d_off, n_seqs, n, ks.k, (const uint32_t*)(d_off + at_miss), (const uint32_t*)(d_off + at_begin), d_pre, n_iv,
-                                      (uint64_t*)d_res, d_start, d_end, d_lo, d_hi, st));
+                                      (uint64_t*)d_res, (uint64_t*)(d_res + o_start), (uint64_t*)(d_res + o_end), (uint64_t*)(d_res + o_lo), (uint64_t*)(d_res + o_hi), st));
     HIP_TRY(hipMemcpyAsync(iv_off, d_res, rel.size() * 8, hipMemcpyDeviceToHost, st));
     const bool fits = n_iv <= iv_cap;
     if (fits && n_iv) {
-        HIP_TRY(d2h(iv_start, d_start, (size_t)n_iv * 8, st));
-        HIP_TRY(d2h(iv_end, d_end, (size_t)n_iv * 8, st));
-        HIP_TRY(d2h(iv_missing, d_hi, (size_t)n_iv * 8, st));
+        HIP_TRY(d2h(iv_start, d_res + o_start, (size_t)n_iv * 8, st));
+        HIP_TRY(d2h(iv_end, d_res + o_end, (size_t)n_iv * 8, st));
+        HIP_TRY(d2h(iv_missing, d_res + o_hi, (size_t)n_iv * 8, st));
     }
     HIP_TRY(hipStreamSynchronize(st));
     if (!fits) return fail(HYPO_E_WORKSPACE, "%llu intervals, room for %llu: call again with arrays of that size", (unsigned long long)n_iv, (unsigned long long)iv_cap);
@@ -1304,20 +1325,16 @@ int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n
 }
 
 int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_t* lo, const uint64_t* hi, uint32_t n_spans, uint64_t* total, uint64_t* missing) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    Ctx::KSet& ks = g_ctx.ks;
-    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    HYPO_KSET_ENTRY();
     if (!n_spans) return HYPO_OK;
     if (!lo || !hi || !total || !missing) return fail(HYPO_E_INVALID, "NULL buffer");
     // a span longer than KSET_SPAN_PIECE windows becomes several items (each carries the k - 1 bytes its last window needs)
     const uint32_t k = ks.k;
+    auto windows = [&](uint32_t s) { const uint64_t len = hi[s] - lo[s]; return len >= k ? len - k + 1 : 0; };
     uint64_t n_items = 0;
     for (uint32_t s = 0; s < n_spans; ++s) {
         if (lo[s] > hi[s] || hi[s] > n_bytes) return fail(HYPO_E_INVALID, "span %u = [%llu, %llu) of %llu bytes", s, (unsigned long long)lo[s], (unsigned long long)hi[s], (unsigned long long)n_bytes);
-        const uint64_t len = hi[s] - lo[s];
-        if (len >= k) n_items += (len - k + 1 + hypo::KSET_SPAN_PIECE - 1) / hypo::KSET_SPAN_PIECE;
+        n_items += ks_n_pieces(windows(s));
     }
     for (uint32_t s = 0; s < n_spans; ++s) total[s] = missing[s] = 0;
     if (!n_items) return HYPO_OK;
@@ -1326,19 +1343,10 @@ int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_
     std::vector<uint64_t> item_lo((size_t)n_items);
     std::vector<uint32_t> item_len((size_t)n_items);
     size_t it = 0;
-    for (uint32_t s = 0; s < n_spans; ++s) {
-        const uint64_t len = hi[s] - lo[s];
-        if (len < k) continue;
-        const uint64_t n_win = len - k + 1;
-        for (uint64_t w = 0; w < n_win; w += hypo::KSET_SPAN_PIECE, ++it) {
-            item_lo[it] = lo[s] + w;
-            item_len[it] = (uint32_t)(n_win - w < hypo::KSET_SPAN_PIECE ? n_win - w : hypo::KSET_SPAN_PIECE) + k - 1;
-        }
-    }
-    int group = hypo::KSET_SPAN_GROUP;
-    if (const char* g = getenv("HYPO_KSET_SPAN_GROUP")) group = atoi(g) == 64 ? 64 : atoi(g) == 32 ? 32 : group;   // (profiles/guard_rate.py)
+    for (uint32_t s = 0; s < n_spans; ++s)
+        ks_pieces(windows(s), k, [&](uint64_t w, uint32_t bytes_) { item_lo[it] = lo[s] + w; item_len[it++] = bytes_; });
     hipStream_t st = g_ctx.stream;
-    const size_t lo_bytes = ((size_t)n_items * 8 + 255) & ~(size_t)255;
+    const size_t lo_bytes = Carver::pad((size_t)n_items * 8);
     HIP_TRY(ks.in.alloc(n_bytes));
     HIP_TRY(ks.off.alloc(lo_bytes + (size_t)n_items * 4));
     HIP_TRY(ks.res.alloc((size_t)n_items * 8));
@@ -1346,27 +1354,20 @@ int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_
     HIP_TRY(h2d(ks.off.p, item_lo.data(), (size_t)n_items * 8, st));
     HIP_TRY(h2d((char*)ks.off.p + lo_bytes, item_len.data(), (size_t)n_items * 4, st));
     HIP_TRY(hypo::kset_spans_run((const uint8_t*)ks.in.p, (const uint64_t*)ks.off.p, (const uint32_t*)((const char*)ks.off.p + lo_bytes), (uint32_t)n_items, k,
-                                 ks.table, ks.slots, (uint2*)ks.res.p, group, st));
+                                 ks.table, ks.slots, (uint2*)ks.res.p, ks_group(), st));
     std::vector<uint2> res((size_t)n_items);
     HIP_TRY(d2h(res.data(), ks.res.p, (size_t)n_items * 8, st));
     HIP_TRY(hipStreamSynchronize(st));
     it = 0;
-    for (uint32_t s = 0; s < n_spans; ++s) {
-        const uint64_t len = hi[s] - lo[s];
-        if (len < k) continue;
-        for (uint64_t w = 0; w < len - k + 1; w += hypo::KSET_SPAN_PIECE, ++it) { total[s] += res[it].x; missing[s] += res[it].y; }
-    }
+    for (uint32_t s = 0; s < n_spans; ++s)
+        for (uint64_t i = ks_n_pieces(windows(s)); i; --i, ++it) { total[s] += res[it].x; missing[s] += res[it].y; }
     return HYPO_OK;
 }
 
 int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char* alts, uint64_t n_alt_bytes, const uint64_t* lo, const uint64_t* hi,
                                  const uint32_t* edit_off, uint32_t n_sites, const uint64_t* eb, const uint64_t* ee, const uint64_t* ao, const uint32_t* al,
                                  uint32_t* best_mask, uint64_t* best_total, uint64_t* best_missing, uint64_t* var_total, uint64_t* var_missing) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    Ctx::KSet& ks = g_ctx.ks;
-    if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
+    HYPO_KSET_ENTRY();
     if (!n_sites) return HYPO_OK;
     if (!bytes || !lo || !hi || !edit_off || !best_mask || !best_total || !best_missing) return fail(HYPO_E_INVALID, "NULL buffer");
     // everything is checked before a buffer is touched: the kernels trust what they are given
@@ -1408,8 +1409,7 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
             for (uint32_t j = 0; j < n; ++j) if ((m >> j) & 1u) len += (int64_t)al[e0 + j] - (int64_t)(ee[e0 + j] - eb[e0 + j]);
             const uint32_t n_win = len >= (int64_t)k ? (uint32_t)len - k + 1 : 0;
             if (!n_win) items.push_back(make_uint4(s, m, 0, 0));
-            for (uint32_t w = 0; w < n_win; w += hypo::KSET_SPAN_PIECE)
-                items.push_back(make_uint4(s, m, w, (n_win - w < hypo::KSET_SPAN_PIECE ? n_win - w : hypo::KSET_SPAN_PIECE) + k - 1));
+            ks_pieces(n_win, k, [&](uint64_t w, uint32_t bytes_) { items.push_back(make_uint4(s, m, (uint32_t)w, bytes_)); });
         }
         vars_before += 1ull << n;
         if (items.size() >= (1ull << 31)) return fail(HYPO_E_CAPACITY, "%llu pieces of variants in one call: split the call", (unsigned long long)items.size());
@@ -1418,26 +1418,19 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
     n_items = items.size();
     const uint32_t n_edits = edit_off[n_sites] - e_first;
     const bool want_vars = var_total || var_missing;
-    int group = hypo::KSET_SPAN_GROUP;
-    if (const char* g = getenv("HYPO_KSET_SPAN_GROUP")) group = atoi(g) == 64 ? 64 : atoi(g) == 32 ? 32 : group;   // (profiles/guard_rate.py)
     hipStream_t st = g_ctx.stream;
     // ks.in: bytes | alts.  ks.off: site_lo | eb | ee | ao | items | edit_off | al | site_item | var_off.  ks.res: item pairs |
     // best_total | best_missing | var_total | var_missing | best_mask.  Every section starts at a multiple of 256 bytes.
-    auto up = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t alt_at = up((size_t)n_bytes);
-    size_t o = 0;
-    auto take = [&](size_t bytes_) { const size_t at = o; o = up(o + bytes_); return at; };
-    const size_t o_lo = take((size_t)n_sites * 8), o_eb = take((size_t)n_edits * 8), o_ee = take((size_t)n_edits * 8), o_ao = take((size_t)n_edits * 8),
-                 o_items = take((size_t)n_items * 16), o_eoff = take(((size_t)n_sites + 1) * 4), o_al = take((size_t)n_edits * 4),
-                 o_sitem = take(((size_t)n_sites + 1) * 4), o_voff = take(((size_t)n_sites + 1) * 4);
-    const size_t off_bytes = o;
-    o = 0;
-    const size_t r_item = take((size_t)n_items * 8), r_bt = take((size_t)n_sites * 8), r_bm = take((size_t)n_sites * 8),
-                 r_vt = take(want_vars ? (size_t)n_vars * 8 : 0), r_vm = take(want_vars ? (size_t)n_vars * 8 : 0), r_mask = take((size_t)n_sites * 4);
-    const size_t res_bytes = o;
+    const size_t alt_at = Carver::pad((size_t)n_bytes);
+    Carver co, cr;
+    const size_t o_lo = co.take((size_t)n_sites * 8), o_eb = co.take((size_t)n_edits * 8), o_ee = co.take((size_t)n_edits * 8), o_ao = co.take((size_t)n_edits * 8),
+                 o_items = co.take((size_t)n_items * 16), o_eoff = co.take(((size_t)n_sites + 1) * 4), o_al = co.take((size_t)n_edits * 4),
+                 o_sitem = co.take(((size_t)n_sites + 1) * 4), o_voff = co.take(((size_t)n_sites + 1) * 4);
+    const size_t r_item = cr.take((size_t)n_items * 8), r_bt = cr.take((size_t)n_sites * 8), r_bm = cr.take((size_t)n_sites * 8),
+                 r_vt = cr.take(want_vars ? (size_t)n_vars * 8 : 0), r_vm = cr.take(want_vars ? (size_t)n_vars * 8 : 0), r_mask = cr.take((size_t)n_sites * 4);
     HIP_TRY(ks.in.alloc(alt_at + (size_t)n_alt_bytes));
-    HIP_TRY(ks.off.alloc(off_bytes));
-    HIP_TRY(ks.res.alloc(res_bytes));
+    HIP_TRY(ks.off.alloc(co.at));
+    HIP_TRY(ks.res.alloc(cr.at));
     char* d_in = (char*)ks.in.p; char* d_off = (char*)ks.off.p; char* d_res = (char*)ks.res.p;
     if (n_bytes) HIP_TRY(h2d(d_in, bytes, n_bytes, st));
     if (n_alt_bytes) HIP_TRY(h2d(d_in + alt_at, alts, n_alt_bytes, st));
@@ -1457,7 +1450,7 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
                                     (const uint4*)(d_off + o_items), (uint32_t)n_items, (const uint32_t*)(d_off + o_sitem), (const uint32_t*)(d_off + o_voff), n_sites, k,
                                     ks.table, ks.slots, (uint2*)(d_res + r_item), (uint32_t*)(d_res + r_mask), (unsigned long long*)(d_res + r_bt),
                                     (unsigned long long*)(d_res + r_bm), want_vars ? (unsigned long long*)(d_res + r_vt) : nullptr,
-                                    want_vars ? (unsigned long long*)(d_res + r_vm) : nullptr, group, st));
+                                    want_vars ? (unsigned long long*)(d_res + r_vm) : nullptr, ks_group(), st));
     HIP_TRY(d2h(best_mask, d_res + r_mask, (size_t)n_sites * 4, st));
     HIP_TRY(d2h(best_total, d_res + r_bt, (size_t)n_sites * 8, st));
     HIP_TRY(d2h(best_missing, d_res + r_bm, (size_t)n_sites * 8, st));

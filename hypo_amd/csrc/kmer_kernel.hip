@@ -1,10 +1,8 @@
 // kmer_kernel.hip — the solid k-mer set built from the short reads on the device (replaces KMC run with -k<k> -ci2 -cs<4c>
 // -cx<4c> and suk::SolidKmers::initialise, external/suk/src/SolidKmers.cpp:68-208).  Three kernels over one direct-address count
 // table of 4^k counters, indexed by the canonical code min(fwd, rc) (A0 C1 G2 T3, MSB-first):
-//   * kmer_count_kernel: a 256-lane workgroup stages 8 KiB of sequence bytes (+ 32 bytes behind them) into LDS with 16-byte loads;
-//     every lane rolls the forward and reverse-complement codes over its 32-byte stretch (+ k - 1 bytes of the next one) and counts
-//     the k-mers that START in its stretch, so every k-mer of the input is counted once.  Any byte other than ACGTacgt (N, IUPAC, the
-//     record separator) restarts the run.  A counter is raised by a compare-and-swap loop on the dword that holds it, and never past
+//   * kmer_count_kernel: staging and the per-lane rolling codes are those of kmer_roll.hpp; the lane counts the k-mers that START
+//     in its stretch.  A counter is raised by a compare-and-swap loop on the dword that holds it, and never past
 //     `sat` = 4c + 1 ("above -cx"): exact under any contention (a poly-A run raises one counter millions of times) and the carry of a
 //     1- or 2-byte counter can never reach its neighbour.  A lane that reads a saturated counter issues no atomic at all.
 //   * kmer_histogram_kernel: 16-byte reads of the table, per-workgroup bins in LDS, one 64-bit global add per non-zero bin and workgroup.
@@ -12,25 +10,16 @@
 //     count[canon(y)] and applies the cut-offs and the homopolymer rule (symmetric under reverse complement), so both strands of a
 //     solid canonical k-mer are set without atomics and the words are deterministic.  Popcounts of the words (all bits, and the bits
 //     of canonical codes) are summed per wave and added once per wave.
-// Bounds: the count kernel reads bytes [0, n) only (LDS beyond n holds a separator), table indices are < 4^k by construction
-// (both codes are masked to 2k bits), the fill kernel writes words [0, 4^k / 64).
+// Bounds: the count kernel reads as kmer_roll.hpp says, table indices are < 4^k by construction (both codes are masked to 2k
+// bits), the fill kernel writes words [0, 4^k / 64).
 #include <hip/hip_runtime.h>
 #include "kmer_kernel.hpp"
+#include "kmer_roll.hpp"
 
 namespace hypo {
 
-constexpr int KC_THREADS = 256;
-constexpr int KC_STRETCH = 32;                                  // bytes whose k-mers one lane counts
-constexpr int KC_BLOCK_BYTES = KC_THREADS * KC_STRETCH;         // 8 KiB per workgroup
-constexpr int KC_HALO = 32;                                     // >= k - 1 for k <= 17, a multiple of 16
 constexpr int KH_THREADS = 256;
 constexpr int KF_THREADS = 256;
-
-// 0..3 for ACGTacgt, 4 for every other byte (b | 0x20 folds the case and nothing else onto 'a', 'c', 'g', 't')
-__device__ __forceinline__ uint32_t base_code(uint32_t b) {
-    const uint32_t l = b | 0x20u;
-    return l == 'a' ? 0u : l == 'c' ? 1u : l == 'g' ? 2u : l == 't' ? 3u : 4u;
-}
 
 // counter of code `c` += 1 unless it holds `sat` already.  Counters of 8 (wide = 0) or 16 bits inside 32-bit words.
 template <int WIDE>
@@ -47,37 +36,15 @@ __device__ __forceinline__ void count_one(uint32_t* table32, uint64_t c, uint32_
 }
 
 template <int WIDE>
-__global__ void __launch_bounds__(KC_THREADS) kmer_count_kernel(const uint8_t* __restrict__ bytes, uint64_t n, uint32_t k,
+__global__ void __launch_bounds__(KR_THREADS) kmer_count_kernel(const uint8_t* __restrict__ bytes, uint64_t n, uint32_t k,
                                                                  uint32_t* __restrict__ table32, uint32_t sat) {
-    __shared__ __attribute__((aligned(16))) uint8_t sb[KC_BLOCK_BYTES + KC_HALO];
-    const uint64_t b0 = (uint64_t)blockIdx.x * KC_BLOCK_BYTES;
-    const int t = threadIdx.x;
-    for (int x = t * 16; x < KC_BLOCK_BYTES + KC_HALO; x += KC_THREADS * 16) {
-        const uint64_t g = b0 + (uint64_t)x;
-        uint4 v;
-        if (g + 16 <= n) {
-            v = *(const uint4*)(bytes + g);                     // (g is a multiple of 16 and the buffer 256-byte aligned)
-        } else {
-            uint8_t tmp[16];
-            for (int i = 0; i < 16; ++i) tmp[i] = g + i < n ? bytes[g + i] : (uint8_t)'\n';
-            v = *(const uint4*)tmp;
-        }
-        *(uint4*)(sb + x) = v;
-    }
-    __syncthreads();
-    const uint64_t mask = (k >= 32) ? ~0ull : ((1ull << (2 * k)) - 1);
-    const uint32_t rsh = 2 * (k - 1);
-    const int s0 = t * KC_STRETCH;
-    const int last = s0 + KC_STRETCH + (int)k - 1;              // exclusive end of the bytes this lane reads
-    uint64_t fwd = 0, rc = 0;
-    uint32_t run = 0;
-    for (int p = s0; p < last; ++p) {
-        const uint32_t c = base_code(sb[p]);
-        if (c > 3) { run = 0; continue; }
-        fwd = ((fwd << 2) | c) & mask;
-        rc = (rc >> 2) | ((uint64_t)(3u - c) << rsh);
-        if (++run >= k) count_one<WIDE>(table32, fwd < rc ? fwd : rc, sat);      // starts at p - k + 1 >= s0
-    }
+    __shared__ __attribute__((aligned(16))) uint8_t sb[KR_BLOCK_BYTES + KR_HALO];
+    kmer_stage(sb, bytes, (uint64_t)blockIdx.x * KR_BLOCK_BYTES, n);
+    const int s0 = threadIdx.x * KR_STRETCH;
+    const int last = s0 + KR_STRETCH + (int)k - 1;              // exclusive end of the bytes this lane reads
+    KmerRoll roll(k);
+    for (int p = s0; p < last; ++p)
+        if (roll.push(sb[p])) count_one<WIDE>(table32, roll.canon(), sat);             // starts at p - k + 1 >= s0
 }
 
 template <int WIDE>
@@ -147,9 +114,9 @@ __global__ void __launch_bounds__(KF_THREADS) solid_fill_kernel(const void* __re
 
 hipError_t kmer_count_run(const uint8_t* bytes, uint64_t n, uint32_t k, void* table, int wide, uint32_t sat, hipStream_t st) {
     if (!n) return hipSuccess;
-    const uint64_t blocks = (n + KC_BLOCK_BYTES - 1) / KC_BLOCK_BYTES;
-    if (wide) kmer_count_kernel<1><<<dim3((uint32_t)blocks), dim3(KC_THREADS), 0, st>>>(bytes, n, k, (uint32_t*)table, sat);
-    else kmer_count_kernel<0><<<dim3((uint32_t)blocks), dim3(KC_THREADS), 0, st>>>(bytes, n, k, (uint32_t*)table, sat);
+    const uint64_t blocks = (n + KR_BLOCK_BYTES - 1) / KR_BLOCK_BYTES;
+    if (wide) kmer_count_kernel<1><<<dim3((uint32_t)blocks), dim3(KR_THREADS), 0, st>>>(bytes, n, k, (uint32_t*)table, sat);
+    else kmer_count_kernel<0><<<dim3((uint32_t)blocks), dim3(KR_THREADS), 0, st>>>(bytes, n, k, (uint32_t*)table, sat);
     return hipGetLastError();
 }
 

@@ -3,7 +3,7 @@
 // stops at k = 17; this one is open addressing with linear probing over 64-bit slots.  The key is the canonical code min(fwd, rc)
 // itself (A0 C1 G2 T3, MSB-first, 2k <= 62 bits), all-ones marks a free slot, the home slot is the high half of
 // mix64(key) * slots (any number of slots, no modulo).  Keys are never removed or changed, so a slot goes from free to one key once.
-//   * kset_insert_kernel: bytes staged through LDS and fwd / rc rolled per lane exactly as kmer_count_kernel does.  A lane LOADS its
+//   * kset_insert_kernel: bytes staged through LDS and fwd / rc rolled per lane by kmer_roll.hpp, as in kmer_count_kernel.  A lane LOADS its
 //     slot first: the key is there already for all but the first occurrence of a k-mer (29 of 30 at 30x) and no atomic is issued.
 //     Only a free slot gets a 64-bit compare-and-swap; a lane that loses it to another key goes on to the next slot, one that loses
 //     it to its own key is done.  New keys are summed per wave and added to the table's counter once per wave.
@@ -15,26 +15,20 @@
 //   * kset_track_*_kernel (below, with comments of their own): the query kernel keeping its per-window answers as bit flags, and the
 //     passes that turn the flags into sorted intervals of missing k-mers.
 //   * kset_spans_kernel / kset_variants_kernel (below, with comments of their own): many short spans, and every subset of a few
-//     edits of many short sites, a group of 32 or 64 lanes per item; read-only probes, no LDS, no atomics.
+//     edits of many short sites, a group of 32 or 64 lanes per item; read-only probes, no LDS, no atomics.  Both are ks_group_scan
+//     with another source of bytes.
 // Forward progress: every probe loop runs at most `slots` steps.  A lane of the insert or rehash kernel that finds neither its key
 // nor a free slot sets the overflow flag and leaves; lanes in a long probe look at the flag every 64 steps and leave too.  The host
 // keeps the table at most half full, so the flag says "internal error", but no input can make a kernel spin.
-// Bounds: bytes [0, n) are read (LDS beyond n holds a separator), slot indices are < slots by construction, total / missing
-// indices are < n_seqs (a lane's sequence comes from a search in off[0 .. n_seqs] for a position < n = off[n_seqs]).
+// Bounds: bytes are read as kmer_roll.hpp says, slot indices are < slots by construction, total / missing indices are < n_seqs
+// (a lane's sequence comes from ks_seq_of, a search in off[0 .. n_seqs] for a position < n = off[n_seqs]).
 #include <hip/hip_runtime.h>
 #include "kset_kernel.hpp"
+#include "kmer_roll.hpp"
 
 namespace hypo {
 
-constexpr int KS_THREADS = 256;
-constexpr int KS_STRETCH = 32;                                  // bytes whose k-mers one lane handles
-constexpr int KS_BLOCK_BYTES = KS_THREADS * KS_STRETCH;         // 8 KiB per workgroup
-constexpr int KS_HALO = 32;                                     // >= k - 1 for k <= 31, a multiple of 16
-
-__device__ __forceinline__ uint32_t ks_base_code(uint32_t b) {   // 0..3 for ACGTacgt, 4 for every other byte
-    const uint32_t l = b | 0x20u;
-    return l == 'a' ? 0u : l == 'c' ? 1u : l == 'g' ? 2u : l == 't' ? 3u : 4u;
-}
+constexpr int KS_THREADS = KR_THREADS;                         // every kernel of this file
 
 __device__ __forceinline__ uint64_t ks_mix64(uint64_t x) {      // the 64-bit finaliser of MurmurHash3 (public domain)
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
@@ -73,21 +67,11 @@ __device__ __forceinline__ bool ks_contains(const uint64_t* __restrict__ table, 
     return false;
 }
 
-// bytes [b0, b0 + KS_BLOCK_BYTES + KS_HALO) of the input into LDS with 16-byte loads; '\n' beyond n
-__device__ __forceinline__ void ks_stage(uint8_t* sb, const uint8_t* __restrict__ bytes, uint64_t b0, uint64_t n) {
-    for (int x = threadIdx.x * 16; x < KS_BLOCK_BYTES + KS_HALO; x += KS_THREADS * 16) {
-        const uint64_t g = b0 + (uint64_t)x;
-        uint4 v;
-        if (g + 16 <= n) {
-            v = *(const uint4*)(bytes + g);                     // (g is a multiple of 16 and the buffer 256-byte aligned)
-        } else {
-            uint8_t tmp[16];
-            for (int i = 0; i < 16; ++i) tmp[i] = g + i < n ? bytes[g + i] : (uint8_t)'\n';
-            v = *(const uint4*)tmp;
-        }
-        *(uint4*)(sb + x) = v;
-    }
-    __syncthreads();
+// the last sequence that starts at or before `pos` < n = off[n_seqs] (empty ones before it are skipped): an upper-bound search
+__device__ __forceinline__ uint32_t ks_seq_of(const uint64_t* __restrict__ off, uint32_t n_seqs, uint64_t pos) {
+    uint32_t lo = 1, hi = n_seqs;                               // first index in [1, n_seqs] with off[index] > pos
+    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] > pos) hi = mid; else lo = mid + 1; }
+    return lo - 1;
 }
 
 __device__ __forceinline__ void ks_wave_add(unsigned long long* dst, uint32_t v) {
@@ -97,21 +81,14 @@ __device__ __forceinline__ void ks_wave_add(unsigned long long* dst, uint32_t v)
 
 __global__ void __launch_bounds__(KS_THREADS) kset_insert_kernel(const uint8_t* __restrict__ bytes, uint64_t n, uint32_t k,
                                                                   uint64_t* table, uint64_t slots, unsigned long long* ctr) {
-    __shared__ __attribute__((aligned(16))) uint8_t sb[KS_BLOCK_BYTES + KS_HALO];
-    ks_stage(sb, bytes, (uint64_t)blockIdx.x * KS_BLOCK_BYTES, n);
-    const uint64_t mask = (1ull << (2 * k)) - 1;
-    const uint32_t rsh = 2 * (k - 1);
-    const int s0 = threadIdx.x * KS_STRETCH;
-    const int last = s0 + KS_STRETCH + (int)k - 1;              // exclusive end of the bytes this lane reads
-    uint64_t fwd = 0, rc = 0;
-    uint32_t run = 0, n_new = 0;
-    for (int p = s0; p < last; ++p) {
-        const uint32_t c = ks_base_code(sb[p]);
-        if (c > 3) { run = 0; continue; }
-        fwd = ((fwd << 2) | c) & mask;
-        rc = (rc >> 2) | ((uint64_t)(3u - c) << rsh);
-        if (++run >= k) n_new += ks_insert(table, slots, fwd < rc ? fwd : rc, ctr);   // starts at p - k + 1 >= s0
-    }
+    __shared__ __attribute__((aligned(16))) uint8_t sb[KR_BLOCK_BYTES + KR_HALO];
+    kmer_stage(sb, bytes, (uint64_t)blockIdx.x * KR_BLOCK_BYTES, n);
+    const int s0 = threadIdx.x * KR_STRETCH;
+    const int last = s0 + KR_STRETCH + (int)k - 1;              // exclusive end of the bytes this lane reads
+    KmerRoll roll(k);
+    uint32_t n_new = 0;
+    for (int p = s0; p < last; ++p)
+        if (roll.push(sb[p])) n_new += ks_insert(table, slots, roll.canon(), ctr);     // starts at p - k + 1 >= s0
     ks_wave_add(ctr, n_new);
 }
 
@@ -133,47 +110,36 @@ __device__ __forceinline__ void ks_query_body(const uint8_t* __restrict__ bytes,
                                               uint32_t k, const uint64_t* __restrict__ table, uint64_t slots, unsigned long long* total,
                                               unsigned long long* missing, const uint8_t* __restrict__ want, uint32_t* __restrict__ miss_bits,
                                               uint32_t* __restrict__ begin_bits) {
-    __shared__ __attribute__((aligned(16))) uint8_t sb[KS_BLOCK_BYTES + KS_HALO];
-    const uint64_t b0 = (uint64_t)blockIdx.x * KS_BLOCK_BYTES;
-    ks_stage(sb, bytes, b0, n);
-    const uint64_t mask = (1ull << (2 * k)) - 1;
-    const uint32_t rsh = 2 * (k - 1);
-    const int s0 = threadIdx.x * KS_STRETCH;
-    const int last = s0 + KS_STRETCH + (int)k - 1;
+    __shared__ __attribute__((aligned(16))) uint8_t sb[KR_BLOCK_BYTES + KR_HALO];
+    const uint64_t b0 = (uint64_t)blockIdx.x * KR_BLOCK_BYTES;
+    kmer_stage(sb, bytes, b0, n);
+    const int s0 = threadIdx.x * KR_STRETCH;
+    const int last = s0 + KR_STRETCH + (int)k - 1;
     uint32_t seq = 0;
     uint64_t seq_end = 0;
     unsigned long long tot = 0, mis = 0;
     uint32_t mbits = 0, bbits = 0;                              // TRACK: bit j speaks of position b0 + s0 + j
     if (b0 + (uint64_t)s0 < n) {
-        // the sequence that holds the lane's first byte: the last one that starts at or before it (empty ones before it are skipped)
         const uint64_t g0 = b0 + (uint64_t)s0;
-        uint32_t lo = 1, hi = n_seqs;                           // first index in [1, n_seqs] with off[index] > g0 (off[n_seqs] = n > g0)
-        while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] > g0) hi = mid; else lo = mid + 1; }
-        seq = lo - 1;
-        seq_end = off[lo];
+        seq = ks_seq_of(off, n_seqs, g0);                       // the sequence that holds the lane's first byte
+        seq_end = off[seq + 1];
         bool wanted = true;                                     // TRACK: the sequence in hand gets intervals
         if (TRACK) { bbits = off[seq] == g0; wanted = !want || want[seq]; }
-        uint64_t fwd = 0, rc = 0;
-        uint32_t run = 0;
+        KmerRoll roll(k);
         for (int p = s0; p < last; ++p) {
             const uint64_t g = b0 + (uint64_t)p;
             if (g >= n) break;
             if (g == seq_end) {                                  // the next sequence starts here (g < n: there is one that holds g)
                 if (tot) { atomicAdd(total + seq, tot); if (mis) atomicAdd(missing + seq, mis); }
-                tot = mis = 0; run = 0;
+                tot = mis = 0; roll.reset();
                 do { ++seq; seq_end = off[seq + 1]; } while (seq_end == g);
-                if (TRACK) { if (p < s0 + KS_STRETCH) bbits |= 1u << (p - s0); wanted = !want || want[seq]; }
+                if (TRACK) { if (p < s0 + KR_STRETCH) bbits |= 1u << (p - s0); wanted = !want || want[seq]; }
             }
-            const uint32_t c = ks_base_code(sb[p]);
-            if (c > 3) { run = 0; continue; }
-            fwd = ((fwd << 2) | c) & mask;
-            rc = (rc >> 2) | ((uint64_t)(3u - c) << rsh);
-            if (++run >= k) {
-                ++tot;
-                if (!ks_contains(table, slots, fwd < rc ? fwd : rc)) {
-                    ++mis;
-                    if (TRACK && wanted) mbits |= 1u << (p - ((int)k - 1) - s0);   // the window's start: s0 <= p - k + 1 < s0 + KS_STRETCH
-                }
+            if (!roll.push(sb[p])) continue;
+            ++tot;
+            if (!ks_contains(table, slots, roll.canon())) {
+                ++mis;
+                if (TRACK && wanted) mbits |= 1u << (p - ((int)k - 1) - s0);   // the window's start: s0 <= p - k + 1 < s0 + KR_STRETCH
             }
         }
     }
@@ -199,7 +165,7 @@ __global__ void __launch_bounds__(KS_THREADS) kset_query_kernel(const uint8_t* _
 // ---- where the missing windows are (hypo --qv-bed; DESIGN.md "k-mer QV track") -------------------------------------------------------
 // Flag word w speaks of positions [32 w, 32 w + 32) of the call's bytes: miss_bits has a bit per missing window START (of a sequence
 // that wants intervals), begin_bits a bit per first byte of a sequence.  kset_track_flags_kernel is the query kernel and stores the
-// two words of every lane of its grid, which has one workgroup more than the bytes need when n is a multiple of KS_BLOCK_BYTES:
+// two words of every lane of its grid, which has one workgroup more than the bytes need when n is a multiple of KR_BLOCK_BYTES:
 // position n, where the last interval may END, has a word too.  Everything after it is arithmetic on those words:
 //   * a base i is covered when a missing window starts in [i - k + 1, i].  Windows never cross a sequence end, so neither does the
 //     cover of one, and k <= 31 < 32: the covered bits of word w are an OR of k shifts of the 64 bits (miss[w] : miss[w - 1]),
@@ -340,15 +306,13 @@ __global__ void __launch_bounds__(KS_THREADS) kset_track_finish_kernel(const uin
     const uint64_t j = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x;
     if (j >= n_iv) return;
     const uint64_t at = iv_start[j];
-    uint32_t lo = 1, hi = n_seqs;                               // first index in [1, n_seqs] with off[index] > at (off[n_seqs] = n > at)
-    while (lo < hi) { const uint32_t mid = lo + (hi - lo) / 2; if (off[mid] > at) hi = mid; else lo = mid + 1; }
-    const uint64_t base = off[lo - 1];
+    const uint64_t base = off[ks_seq_of(off, n_seqs, at)];      // (off[n_seqs] = n > at)
     iv_start[j] = at - base;
     iv_end[j] -= base;
     cnt_hi[j] -= cnt_lo[j];
 }
 
-uint32_t kset_track_blocks(uint64_t n) { return (uint32_t)(n / KS_BLOCK_BYTES + 1); }
+uint32_t kset_track_blocks(uint64_t n) { return (uint32_t)(n / KR_BLOCK_BYTES + 1); }
 
 hipError_t kset_track_count_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table, uint64_t slots,
                                 unsigned long long* total, unsigned long long* missing, const uint8_t* want, uint32_t* miss_bits, uint32_t* begin_bits,
@@ -386,8 +350,7 @@ hipError_t kset_track_emit_run(const uint64_t* off, uint32_t n_seqs, uint64_t n,
 // code is their bit-reversed interleave (MSB-first), the reverse complement the interleave of their complements.  No LDS, no
 // per-lane loop over bytes.  Hits and misses are counted with two more ballots, so the sums are wave-uniform and the group's first
 // lane stores them; no atomics, and the output is a pure function of the input.
-// Bounds: a lane reads bytes[lo + x] for x < len only (lo + len <= n is checked by the caller); items and out are indexed below
-// n_items; the probe is ks_contains (slot indices < slots, at most `slots` steps).
+// All of that is ks_group_scan; a kernel reads its item's descriptor and says where byte x of the item is.
 __device__ __forceinline__ uint64_t ks_spread(uint64_t x) {     // bit j of the low 32 bits to bit 2j
     x &= 0xffffffffull;
     x = (x | (x << 16)) & 0x0000ffff0000ffffull;
@@ -407,21 +370,17 @@ template <int G> __device__ __forceinline__ uint32_t ks_window_bits(uint64_t lo,
     return (uint32_t)(l ? (lo >> l) | (hi << (64 - l)) : lo);
 }
 
-template <int G>
-__global__ void __launch_bounds__(KS_THREADS) kset_spans_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ item_lo,
-                                                                 const uint32_t* __restrict__ item_len, uint32_t n_items, uint32_t k,
-                                                                 const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out) {
+// The item of the calling lane's group goes through the set: `fetch(x)` is byte x < len of the item, out[item] = (windows, misses).
+template <int G, class Fetch>
+__device__ __forceinline__ void ks_group_scan(Fetch fetch, bool have, uint32_t len, uint32_t k, const uint64_t* __restrict__ table,
+                                              uint64_t slots, uint2* __restrict__ out, uint64_t item) {
     static_assert(G == 32 || G == 64, "a half-wave or a wave");
     const uint32_t lane = threadIdx.x & 63, l = lane & (G - 1), half = G == 64 ? 0 : lane >> 5;
-    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
-    const bool have = item < n_items;
-    const uint64_t lo = have ? item_lo[item] : 0;
-    const uint32_t len = have ? item_len[item] : 0;
     const uint32_t n_win = len >= k ? len - k + 1 : 0;
     const uint32_t kmask = (uint32_t)((1ull << k) - 1);
     auto load_masks = [&](uint32_t at, uint64_t& b0, uint64_t& b1, uint64_t& bad) {   // bytes [at, at + G) of the item (wave-uniform call)
         const uint32_t x = at + l;
-        const uint32_t c = x < len ? ks_base_code(bytes[lo + x]) : 4u;
+        const uint32_t c = x < len ? base_code(fetch(x)) : 4u;
         b0 = ks_group_part<G>(__ballot(c & 1u), half);
         b1 = ks_group_part<G>(__ballot(c & 2u), half);
         bad = ks_group_part<G>(__ballot(c > 3u), half);
@@ -429,7 +388,8 @@ __global__ void __launch_bounds__(KS_THREADS) kset_spans_kernel(const uint8_t* _
     uint64_t c0, c1, cb, n0, n1, nb;                           // the masks of the pass's G bytes, and of the G bytes after them
     load_masks(0, c0, c1, cb);
     uint32_t tot = 0, mis = 0;
-    for (uint32_t base = 0; __any(base < n_win); base += G) {   // (both halves of a wave stay in the loop until the longer item is done)
+    // (both halves of a wave stay in the loop until the longer item is done; variant lengths differ per mask)
+    for (uint32_t base = 0; __any(base < n_win); base += G) {
         load_masks(base + G, n0, n1, nb);
         const bool in = base + l < n_win;
         const bool ok = in && (ks_window_bits<G>(cb, nb, l) & kmask) == 0;
@@ -447,6 +407,18 @@ __global__ void __launch_bounds__(KS_THREADS) kset_spans_kernel(const uint8_t* _
     if (have && l == 0) out[item] = make_uint2(tot, mis);
 }
 
+// Bounds: a lane reads bytes[lo + x] for x < len only (lo + len <= n is checked by the caller); items and out are indexed below
+// n_items; the probe is ks_contains (slot indices < slots, at most `slots` steps).
+template <int G>
+__global__ void __launch_bounds__(KS_THREADS) kset_spans_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ item_lo,
+                                                                 const uint32_t* __restrict__ item_len, uint32_t n_items, uint32_t k,
+                                                                 const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out) {
+    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
+    const bool have = item < n_items;
+    const uint64_t lo = have ? item_lo[item] : 0;
+    ks_group_scan<G>([&](uint32_t x) { return (uint32_t)bytes[lo + x]; }, have, have ? item_len[item] : 0, k, table, slots, out, item);
+}
+
 hipError_t kset_spans_run(const uint8_t* bytes, const uint64_t* item_lo, const uint32_t* item_len, uint32_t n_items, uint32_t k,
                           const uint64_t* table, uint64_t slots, uint2* out, int group, hipStream_t st) {
     if (!n_items) return hipSuccess;
@@ -461,8 +433,8 @@ hipError_t kset_spans_run(const uint8_t* bytes, const uint64_t* item_lo, const u
 // An item is a piece of ONE variant of a site: x = site, y = mask, z = the piece's first byte in the variant's text, w = its length
 // (at most KSET_SPAN_PIECE windows, as the spans' pieces).  The variant's text exists nowhere: byte p of variant `mask` of a site
 // is found by walking the site's (at most KSET_MAX_EDITS) edits in order with two running positions, `sp` in bytes and `vp` in the
-// variant, and comes from `alts` inside an edit whose bit is set, from `bytes` otherwise.  A lane loads one such byte a pass; from
-// there on the kernel is kset_spans_kernel: three ballots, carried masks, the bit-reversed interleave, ks_contains, ballot counts.
+// variant, and comes from `alts` inside an edit whose bit is set, from `bytes` otherwise.  A lane loads one such byte a pass; the
+// rest is ks_group_scan, as for the spans.
 // No LDS, no atomics, no scratch; item i's pair goes to out[i] and kset_variants_reduce_kernel adds the pieces up.
 // Bounds: a lane asks for byte p of its item's variant only for p < z + w <= the variant's length (the caller computed both from the
 // same edits), so the walk ends inside the site: bytes is read at [lo, hi) of the site, alts at [ao[e], ao[e] + al[e]) of an edit
@@ -500,42 +472,12 @@ __global__ void __launch_bounds__(KS_THREADS) kset_variants_kernel(const uint8_t
                                                                     const uint64_t* __restrict__ ao, const uint32_t* __restrict__ al,
                                                                     const uint4* __restrict__ items, uint32_t n_items, uint32_t k,
                                                                     const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out) {
-    static_assert(G == 32 || G == 64, "a half-wave or a wave");
-    const uint32_t lane = threadIdx.x & 63, l = lane & (G - 1), half = G == 64 ? 0 : lane >> 5;
     const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
     const bool have = item < n_items;
     const uint4 it = have ? items[item] : make_uint4(0, 0, 0, 0);
-    const uint32_t len = it.w;
     const uint64_t lo = have ? site_lo[it.x] : 0;
     const uint32_t e0 = have ? edit_off[it.x] : 0, e1 = have ? edit_off[it.x + 1] : 0;
-    const uint32_t n_win = len >= k ? len - k + 1 : 0;
-    const uint32_t kmask = (uint32_t)((1ull << k) - 1);
-    auto load_masks = [&](uint32_t at, uint64_t& b0, uint64_t& b1, uint64_t& bad) {   // bytes [at, at + G) of the item (wave-uniform call)
-        const uint32_t x = at + l;
-        const uint32_t c = x < len ? ks_base_code(ks_variant_byte(bytes, alts, lo, e0, e1, eb, ee, ao, al, it.y, it.z + x)) : 4u;
-        b0 = ks_group_part<G>(__ballot(c & 1u), half);
-        b1 = ks_group_part<G>(__ballot(c & 2u), half);
-        bad = ks_group_part<G>(__ballot(c > 3u), half);
-    };
-    uint64_t c0, c1, cb, n0, n1, nb;
-    load_masks(0, c0, c1, cb);
-    uint32_t tot = 0, mis = 0;
-    for (uint32_t base = 0; __any(base < n_win); base += G) {   // (variant lengths differ per mask: both halves stay until the longer is done)
-        load_masks(base + G, n0, n1, nb);
-        const bool in = base + l < n_win;
-        const bool ok = in && (ks_window_bits<G>(cb, nb, l) & kmask) == 0;
-        bool miss = false;
-        if (ok) {
-            const uint32_t h0 = ks_window_bits<G>(c0, n0, l) & kmask, h1 = ks_window_bits<G>(c1, n1, l) & kmask;
-            const uint64_t fwd = (ks_spread(__brev(h1) >> (32 - k)) << 1) | ks_spread(__brev(h0) >> (32 - k));
-            const uint64_t rc = (ks_spread(~h1 & kmask) << 1) | ks_spread(~h0 & kmask);
-            miss = !ks_contains(table, slots, fwd < rc ? fwd : rc);
-        }
-        tot += (uint32_t)__popcll(ks_group_part<G>(__ballot(ok), half));
-        mis += (uint32_t)__popcll(ks_group_part<G>(__ballot(miss), half));
-        c0 = n0; c1 = n1; cb = nb;
-    }
-    if (have && l == 0) out[item] = make_uint2(tot, mis);
+    ks_group_scan<G>([&](uint32_t x) { return ks_variant_byte(bytes, alts, lo, e0, e1, eb, ee, ao, al, it.y, it.z + x); }, have, it.w, k, table, slots, out, item);
 }
 
 // One lane per site: the pieces of every variant are added up (the site's items are in mask order, a variant's pieces next to each
@@ -583,7 +525,7 @@ hipError_t kset_variants_run(const uint8_t* bytes, const uint8_t* alts, const ui
 
 hipError_t kset_insert_run(const uint8_t* bytes, uint64_t n, uint32_t k, uint64_t* table, uint64_t slots, unsigned long long* ctr, hipStream_t st) {
     if (!n) return hipSuccess;
-    const uint64_t blocks = (n + KS_BLOCK_BYTES - 1) / KS_BLOCK_BYTES;
+    const uint64_t blocks = (n + KR_BLOCK_BYTES - 1) / KR_BLOCK_BYTES;
     kset_insert_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, n, k, table, slots, ctr);
     return hipGetLastError();
 }
@@ -599,7 +541,7 @@ hipError_t kset_rehash_run(const uint64_t* old_table, uint64_t old_slots, uint64
 hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table,
                           uint64_t slots, unsigned long long* total, unsigned long long* missing, hipStream_t st) {
     if (!n || !n_seqs) return hipSuccess;
-    const uint64_t blocks = (n + KS_BLOCK_BYTES - 1) / KS_BLOCK_BYTES;
+    const uint64_t blocks = (n + KR_BLOCK_BYTES - 1) / KR_BLOCK_BYTES;
     kset_query_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing);
     return hipGetLastError();
 }
