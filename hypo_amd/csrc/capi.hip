@@ -132,13 +132,16 @@ struct Ctx {
     ArmsSet arms[2];
     // the short reads of the contig batch in hand (hypo_gpu_reads_upload): the support kernels vote with them, hypo_gpu_arms_build
     // (reads == NULL) cuts them into arms
+    struct DevReads {                                      // the arrays of a HypoArmsReads in device memory (reads_to_device)
+        const uint32_t *rb = nullptr, *re = nullptr, *qae = nullptr, *cigar_off = nullptr, *cigar = nullptr, *file_rank = nullptr;
+        const uint64_t* seq_off = nullptr; const uint8_t* reads2 = nullptr;
+    };
     struct ResidentReads {
         DevBuf data, work; bool ready = false;
-        uint32_t n = 0; uint64_t n_cig = 0, reads2_bytes = 0; uint32_t max_span = 0; uint64_t sum_span = 0;
+        uint32_t n = 0; uint64_t reads2_bytes = 0; uint32_t max_span = 0; uint64_t sum_span = 0;
         uint64_t total_len = 0;                            // the coordinate space the reads were checked against
         std::vector<uint32_t> ctg_min_rb, ctg_max_re;      // per contig index of read_contig: what its reads span (later calls check their tables against it)
-        const uint32_t *rb = nullptr, *re = nullptr, *qae = nullptr, *cigar_off = nullptr, *cigar = nullptr, *read_contig = nullptr, *file_rank = nullptr;
-        const uint64_t* seq_off = nullptr; const uint8_t* reads2 = nullptr;
+        DevReads dev; const uint32_t* read_contig = nullptr;
     } rr;
     DevBuf solid_set; uint32_t solid_k = 0;            // hypo_gpu_solid_set_upload
     // hypo_gpu_kmer_count_begin .. _end: the count table (4^k counters of 1 or 2 bytes, exact size), the bytes of the call in hand,
@@ -187,6 +190,15 @@ Ctx& cur() { return g_ctxs[(tl_slot >= 0 && tl_slot < kMaxDevices) ? tl_slot : 0
 #define HYPO_LOCKED() std::lock_guard<std::recursive_mutex> hypo_lock_(cur().mu)
 // the device of the context is made current for the calling thread (hypo_gpu_init did that for its own thread only)
 #define HYPO_ON_DEVICE() do { if (g_ctx.ready) HIP_TRY(hipSetDevice(g_ctx.device)); } while (0)
+// How an entry point that works on the calling thread's context begins: its lock, its device, and that hypo_gpu_init made it.
+#define HYPO_ENTRY() \
+    HYPO_LOCKED(); \
+    HYPO_ON_DEVICE(); \
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called")
+// The votes also need the reads of hypo_gpu_reads_upload.
+#define HYPO_VOTE_ENTRY() \
+    HYPO_ENTRY(); \
+    if (!g_ctx.rr.ready) return fail(HYPO_E_INVALID, "no resident reads: call hypo_gpu_reads_upload first")
 
 // Host memory -> device memory on `st`.  On return the host range may be reused (as with hipMemcpyAsync out of pageable
 // memory); when `src` is page-locked the copy is queued as it is and the caller's usual rule applies (leave it alone until the
@@ -287,6 +299,8 @@ std::mutex g_shard_mu;                               // one sharded call at a ti
 constexpr int kNcclUint8 = 1;                         // ncclUint8 (rccl.h)
 
 
+int check_k(uint32_t k) { return k < 2 || k > 31 ? fail(HYPO_E_INVALID, "k=%u out of range 2..31", k) : HYPO_OK; }
+
 int check_scores(const HypoScoreParams* s) {
     if (!s) return fail(HYPO_E_INVALID, "scores == NULL");
     if (s->sr_gap > 0 || s->lr_gap > 0)
@@ -310,6 +324,66 @@ struct Carver {                                       // lays arrays out in one 
     static size_t pad(size_t bytes) { return (bytes + 255) / 256 * 256; }
     size_t take(size_t bytes) { const size_t o = at; at += pad(bytes); return o; }
 };
+
+// A device buffer that a Carver laid out, on the stream that fills it: dev.u32(o) / .u64(o) / .u8(o) / .at<T>(o) is the array at byte
+// offset o with the element type named; dev.up(o, src, bytes) sends host memory there (nothing for an empty array).
+struct DevAt {
+    char* base; hipStream_t st;
+    template <class T> T* at(size_t off) const { return (T*)(base + off); }
+    uint32_t* u32(size_t off) const { return at<uint32_t>(off); }
+    uint64_t* u64(size_t off) const { return at<uint64_t>(off); }
+    uint8_t* u8(size_t off) const { return at<uint8_t>(off); }
+    hipError_t up(size_t off, const void* src, size_t bytes) const { return bytes ? h2d(base + off, src, bytes, st) : hipSuccess; }
+};
+
+// ---- the alignment records of a HypoArmsReads: checked on the host, then on the device -------------------------------------------
+// What is wrong with record a, in the order the checks are reported (0: nothing).  read_contig: NULL where the call has none.
+// Inlined into both record loops: ten million records per contig batch go through it.
+enum ReadFault { READ_OK = 0, READ_SPAN, READ_ORDER, READ_SEQ, READ_CIGAR, READ_CONTIG };
+__attribute__((always_inline)) inline ReadFault read_fault(const HypoArmsReads& A, uint32_t a, uint64_t total_len, const uint32_t* read_contig) {
+    if (A.re[a] <= A.rb[a] || A.re[a] > total_len) return READ_SPAN;
+    if (a && A.rb[a - 1] > A.rb[a]) return READ_ORDER;
+    if (A.seq_off[a] + ((uint64_t)A.qae[a] + 3) / 4 > A.reads2_bytes) return READ_SEQ;
+    if (A.cigar_off[a] > A.cigar_off[a + 1]) return READ_CIGAR;
+    if (read_contig && read_contig[a] >= 0x01000000u) return READ_CONTIG;
+    return READ_OK;
+}
+int read_fail(ReadFault why, const HypoArmsReads& A, uint32_t a, uint64_t total_len, const uint32_t* read_contig) {
+    switch (why) {
+    case READ_SPAN: return fail(HYPO_E_INVALID, "alignment %u: span [%u, %u) outside the %llu bases", a, A.rb[a], A.re[a], (unsigned long long)total_len);
+    case READ_ORDER: return fail(HYPO_E_INVALID, "alignments are not sorted by reference start (alignment %u)", a);
+    case READ_SEQ: return fail(HYPO_E_INVALID, "alignment %u: read outside reads2", a);
+    case READ_CIGAR: return fail(HYPO_E_INVALID, "alignment %u: cigar_off decreases", a);
+    default: return fail(HYPO_E_INVALID, "alignment %u: contig index %u out of range", a, read_contig[a]);
+    }
+}
+
+// The arrays of `A` behind what `c` holds already, in `buf` (sized here for all of it); `R` gets the device pointers.
+int reads_to_device(Carver& c, DevBuf& buf, const HypoArmsReads& A, hipStream_t st, Ctx::DevReads& R) {
+    const size_t na = A.n_alignments, n_cig = na ? A.cigar_off[na] : 0;
+    const size_t o_rb = c.take(na * 4), o_re = c.take(na * 4), o_qae = c.take(na * 4), o_soff = c.take(na * 8), o_reads = c.take(A.reads2_bytes),
+                 o_coff = c.take((na + 1) * 4), o_cig = c.take(n_cig * 4), o_rank = c.take(A.file_rank ? na * 4 : 0);
+    HIP_TRY(buf.alloc(c.at));
+    const DevAt d{(char*)buf.p, st};
+    HIP_TRY(d.up(o_rb, A.rb, na * 4)); HIP_TRY(d.up(o_re, A.re, na * 4)); HIP_TRY(d.up(o_qae, A.qae, na * 4)); HIP_TRY(d.up(o_soff, A.seq_off, na * 8));
+    HIP_TRY(d.up(o_reads, A.reads2, A.reads2_bytes)); if (na) HIP_TRY(d.up(o_coff, A.cigar_off, (na + 1) * 4)); HIP_TRY(d.up(o_cig, A.cigar, n_cig * 4));
+    if (A.file_rank) HIP_TRY(d.up(o_rank, A.file_rank, na * 4));
+    R.rb = d.u32(o_rb); R.re = d.u32(o_re); R.qae = d.u32(o_qae); R.seq_off = d.u64(o_soff); R.reads2 = d.u8(o_reads); R.cigar_off = d.u32(o_coff); R.cigar = d.u32(o_cig);
+    R.file_rank = A.file_rank ? d.u32(o_rank) : nullptr;
+    return HYPO_OK;
+}
+
+// What the three votes do alike once their tables are in `d`, whose tail from o_cov to `end` holds the two arrays of n counters:
+// the counters zeroed, the entry's kernel through launch(cov, sup) (an error code: the entry names its own kernel in it), both arrays down to the host, the stream drained.
+template <class Launch>
+int vote_run(const DevAt& d, size_t o_cov, size_t o_sup, size_t end, uint64_t n, uint32_t* coverage, uint32_t* support, Launch launch) {
+    HIP_TRY(hipMemsetAsync(d.u32(o_cov), 0, end - o_cov, d.st));
+    if (const int rc = launch(d.u32(o_cov), d.u32(o_sup))) return rc;
+    HIP_TRY(d2h(coverage, d.u32(o_cov), n * 4, d.st));
+    HIP_TRY(d2h(support, d.u32(o_sup), n * 4, d.st));
+    HIP_TRY(hipStreamSynchronize(d.st));
+    return HYPO_OK;
+}
 
 
 // First-use costs of a HIP process — loading this library's code objects onto the device, the occupancy queries, the side
@@ -518,9 +592,7 @@ size_t hypo_gpu_poa_workspace_bytes(uint32_t n_windows, uint32_t n_arms) {
 
 int hypo_gpu_poa_batch_device(const HypoScoreParams* scores, const HypoWindowBatch* in, HypoConsensusBatch* out,
                               void* workspace, size_t workspace_bytes, void* hip_stream) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     int rc = check_scores(scores);
     if (rc) return rc;
     if (!in || !out) return fail(HYPO_E_INVALID, "NULL batch");
@@ -572,9 +644,7 @@ int hypo_gpu_poa_slot_layout(const HypoWindowBatch* in, uint64_t* off) {
 // Queues one batch: upload, kernels, download of the results into the caller's buffers, all on the slot's stream; returns
 // without waiting.  `in` and `out` buffers must stay untouched until hypo_gpu_poa_batch_end(ticket).
 int hypo_gpu_poa_batch_begin(const HypoScoreParams* scores, const HypoWindowBatch* in, HypoConsensusBatch* out, int* ticket) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     int rc = check_scores(scores);
     if (rc) return rc;
     if (!in || !out || !ticket) return fail(HYPO_E_INVALID, "NULL batch");
@@ -859,10 +929,8 @@ int hypo_gpu_solid_scan_device(const uint8_t* packed4, uint64_t n_bases, uint32_
                                uint64_t* solid_pos_words, uint64_t* kids, uint64_t kids_cap,
                                uint64_t* word_rank, uint64_t* n_solid,
                                void* workspace, size_t workspace_bytes, void* hip_stream) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    if (k < 2 || k > 31) return fail(HYPO_E_INVALID, "k=%u out of range 2..31", k);
+    HYPO_ENTRY();
+    if (const int rc = check_k(k)) return rc;
     if ((n_bases && !packed4) || !bits || (n_bases && !solid_pos_words)) return fail(HYPO_E_INVALID, "NULL buffer");
     if (!workspace || workspace_bytes < hypo::scan_workspace_bytes(n_bases))
         return fail(HYPO_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, hypo::scan_workspace_bytes(n_bases));
@@ -875,10 +943,8 @@ int hypo_gpu_solid_scan_device(const uint8_t* packed4, uint64_t n_bases, uint32_
 }
 
 int hypo_gpu_solid_set_upload(const uint64_t* bits, uint32_t k) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    if (k < 2 || k > 31) return fail(HYPO_E_INVALID, "k=%u out of range 2..31", k);
+    HYPO_ENTRY();
+    if (const int rc = check_k(k)) return rc;
     if (!bits) return fail(HYPO_E_INVALID, "NULL buffer");
     const uint64_t bit_words = (1ull << (2 * k)) / 64 ? (1ull << (2 * k)) / 64 : 1;
     g_ctx.solid_k = 0;
@@ -892,10 +958,8 @@ int hypo_gpu_solid_set_upload(const uint64_t* bits, uint32_t k) {
 int hypo_gpu_solid_scan(const uint8_t* packed4, uint64_t n_bases, uint32_t k, const uint64_t* bits,
                         uint64_t* solid_pos_words, uint64_t* kids, uint64_t kids_cap,
                         uint64_t* word_rank, uint64_t* n_solid) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    if (k < 2 || k > 31) return fail(HYPO_E_INVALID, "k=%u out of range 2..31", k);
+    HYPO_ENTRY();
+    if (const int rc = check_k(k)) return rc;
     if ((n_bases && !packed4) || (n_bases && !solid_pos_words)) return fail(HYPO_E_INVALID, "NULL buffer");
     if (!bits && g_ctx.solid_k != k) return fail(HYPO_E_INVALID, "bitset_words == NULL but no %u-mer set was uploaded (hypo_gpu_solid_set_upload)", k);
     const uint64_t nw = (n_bases + 63) / 64, nbytes = (n_bases + 1) / 2, bit_words = (1ull << (2 * k)) / 64 ? (1ull << (2 * k)) / 64 : 1;
@@ -930,10 +994,8 @@ int hypo_gpu_solid_scan(const uint8_t* packed4, uint64_t n_bases, uint32_t k, co
 // position with the positions, for hypo_gpu_support_kmers (2 x 2 GB at 250 Mbp / k = 15, where nearly every position is marked).
 int hypo_gpu_solid_scan_keep(uint32_t handle, const uint8_t* packed4, uint64_t n_bases, uint32_t k,
                              uint64_t* solid_pos_words, uint64_t* word_rank, uint64_t* n_solid) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    if (k < 2 || k > 31) return fail(HYPO_E_INVALID, "k=%u out of range 2..31", k);
+    HYPO_ENTRY();
+    if (const int rc = check_k(k)) return rc;
     if ((n_bases && !packed4) || (n_bases && !solid_pos_words)) return fail(HYPO_E_INVALID, "NULL buffer");
     if (g_ctx.solid_k != k) return fail(HYPO_E_INVALID, "no %u-mer set was uploaded (hypo_gpu_solid_set_upload)", k);
     if (handle >= (1u << 24) || n_bases >= 0xfffffff0ull) return fail(HYPO_E_INVALID, "handle or contig length out of range");
@@ -974,9 +1036,7 @@ int hypo_gpu_solid_scan_keep(uint32_t handle, const uint8_t* packed4, uint64_t n
 }
 
 int hypo_gpu_solid_release(uint32_t handle) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     Ctx& cx = g_ctx;
     auto drop = [&cx](Ctx::KeptScan& ks) {
         const size_t kb = (size_t)ks.n * (ks.k <= 16 ? 4 : 8), sb = (size_t)ks.n * 4;
@@ -1001,9 +1061,7 @@ int hypo_gpu_solid_release(uint32_t handle) {
 static constexpr uint64_t kKmerPiece = (uint64_t)256 << 20;     // bytes per kernel launch of hypo_gpu_kmer_count_add
 
 int hypo_gpu_kmer_count_begin(uint32_t k, uint32_t coverage) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     if (k < 5 || k > 17) return fail(HYPO_E_INVALID, "k=%u out of range 5..17 (the count table holds 4^k counters: %.1f GiB at k = %u)",
                                      k, k <= 31 ? (double)(1ull << (2 * k)) / (1 << 30) : 0.0, k);
     if (coverage < 1 || coverage > HYPO_KMER_MAX_COVERAGE) return fail(HYPO_E_INVALID, "coverage %u out of range 1..%u", coverage, HYPO_KMER_MAX_COVERAGE);
@@ -1024,9 +1082,7 @@ int hypo_gpu_kmer_count_begin(uint32_t k, uint32_t coverage) {
 }
 
 int hypo_gpu_kmer_count_add(const char* bytes, uint64_t n) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     Ctx::KmerCount& kc = g_ctx.kc;
     if (!kc.k) return fail(HYPO_E_INVALID, "no count table (hypo_gpu_kmer_count_begin)");
     if (!n) return HYPO_OK;
@@ -1047,9 +1103,7 @@ int hypo_gpu_kmer_count_add(const char* bytes, uint64_t n) {
 }
 
 int hypo_gpu_kmer_histogram(uint64_t* hist, uint32_t n_bins) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     Ctx::KmerCount& kc = g_ctx.kc;
     if (!kc.k) return fail(HYPO_E_INVALID, "no count table (hypo_gpu_kmer_count_begin)");
     if (!hist || n_bins != 4 * kc.cov + 1) return fail(HYPO_E_INVALID, "hist needs 4c + 1 = %u bins (got %u)", 4 * kc.cov + 1, n_bins);
@@ -1061,9 +1115,7 @@ int hypo_gpu_kmer_histogram(uint64_t* hist, uint32_t n_bins) {
 }
 
 int hypo_gpu_solid_set_build(uint32_t lower, uint32_t upper, int exclude_hp, uint64_t* bits, uint64_t* n_bits, uint64_t* n_canonical) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     Ctx::KmerCount& kc = g_ctx.kc;
     if (!kc.k) return fail(HYPO_E_INVALID, "no count table (hypo_gpu_kmer_count_begin)");
     if (!bits) return fail(HYPO_E_INVALID, "NULL buffer");
@@ -1126,9 +1178,7 @@ int ks_resize(Ctx::KSet& ks, uint64_t slots, hipStream_t st) {
 }
 // The entry points that need a live set: the lock, the device, `ks`.
 #define HYPO_KSET_ENTRY() \
-    HYPO_LOCKED(); \
-    HYPO_ON_DEVICE(); \
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called"); \
+    HYPO_ENTRY(); \
     Ctx::KSet& ks = g_ctx.ks; \
     if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)")
 
@@ -1182,9 +1232,7 @@ int ks_group() {                                       // lanes per item; HYPO_K
 extern "C" {
 
 int hypo_gpu_kset_begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     if (k < 12 || k > 31) return fail(HYPO_E_INVALID, "k=%u out of range 12..31 (the key is the 2k-bit canonical code in a 64-bit slot)", k);
     if (!max_bytes) max_bytes = g_ctx.mem_free_at_init / 2;            // default cap: half of what the device had free at init
     const uint64_t max_slots = max_bytes / 8;
@@ -1509,9 +1557,7 @@ static int edit_run_list(const uint4* dlist, const std::vector<uint4>& list, Nee
 extern "C" {
 
 int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run_off, uint32_t* runs, uint64_t runs_cap) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     if (!in || !run_off || (in->n_pairs && (!dist || !in->a_off || !in->b_off))) return fail(HYPO_E_INVALID, "NULL buffer");
     const uint32_t np = in->n_pairs;
     run_off[0] = 0;
@@ -1642,9 +1688,7 @@ int hypo_gpu_host_unregister(void* p) {
 // ---- support votes on the device (kernels in support_kernel.hip) -----------------------------------------
 
 int hypo_gpu_reads_upload(const HypoArmsReads* A, const uint32_t* read_contig, uint64_t total_len) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
     auto& rr = g_ctx.rr;
     rr.ready = false;
     if (!A || !read_contig) return fail(HYPO_E_INVALID, "NULL argument");
@@ -1653,18 +1697,14 @@ int hypo_gpu_reads_upload(const HypoArmsReads* A, const uint32_t* read_contig, u
     uint32_t max_span = 0; uint64_t sum_span = 0;
     rr.ctg_min_rb.clear(); rr.ctg_max_re.clear();
     {   // every record is checked before anything is sent (10 M records per 50 Mbp batch: 40 ms on one thread, so eight share them)
-        struct Part { uint32_t bad = 0xffffffffu, max_span = 0; uint64_t sum_span = 0; std::vector<uint32_t> lo, hi; };
+        struct Part { uint32_t bad = 0xffffffffu; ReadFault why = READ_OK; uint32_t max_span = 0; uint64_t sum_span = 0; std::vector<uint32_t> lo, hi; };
         const int P = na >= (1u << 18) ? 8 : 1;
         std::vector<Part> part((size_t)P);
-        auto bad_record = [&](uint32_t a) -> bool {
-            return A->re[a] <= A->rb[a] || A->re[a] > total_len || (a && A->rb[a - 1] > A->rb[a]) || A->seq_off[a] + ((uint64_t)A->qae[a] + 3) / 4 > A->reads2_bytes ||
-                   A->cigar_off[a] > A->cigar_off[a + 1] || read_contig[a] >= 0x01000000u;
-        };
         auto run = [&](int t) {
             Part& pt = part[(size_t)t];
             const uint32_t a0 = (uint32_t)((uint64_t)na * (uint64_t)t / (uint64_t)P), a1 = (uint32_t)((uint64_t)na * ((uint64_t)t + 1) / (uint64_t)P);
             for (uint32_t a = a0; a < a1; ++a) {
-                if (bad_record(a)) { pt.bad = a; return; }
+                if (const ReadFault why = read_fault(*A, a, total_len, read_contig)) { pt.bad = a; pt.why = why; return; }
                 const uint32_t span = A->re[a] - A->rb[a];
                 pt.max_span = span > pt.max_span ? span : pt.max_span;
                 pt.sum_span += span;
@@ -1679,14 +1719,7 @@ int hypo_gpu_reads_upload(const HypoArmsReads* A, const uint32_t* read_contig, u
         run(0);
         for (auto& x : th) x.join();
         for (const Part& pt : part) {
-            if (pt.bad != 0xffffffffu) {                       // (parts are in record order: this is the first bad record)
-                const uint32_t a = pt.bad;
-                if (A->re[a] <= A->rb[a] || A->re[a] > total_len) return fail(HYPO_E_INVALID, "alignment %u: span [%u, %u) outside the %llu bases", a, A->rb[a], A->re[a], (unsigned long long)total_len);
-                if (a && A->rb[a - 1] > A->rb[a]) return fail(HYPO_E_INVALID, "alignments are not sorted by reference start (alignment %u)", a);
-                if (A->seq_off[a] + ((uint64_t)A->qae[a] + 3) / 4 > A->reads2_bytes) return fail(HYPO_E_INVALID, "alignment %u: read outside reads2", a);
-                if (A->cigar_off[a] > A->cigar_off[a + 1]) return fail(HYPO_E_INVALID, "alignment %u: cigar_off decreases", a);
-                return fail(HYPO_E_INVALID, "alignment %u: contig index %u out of range", a, read_contig[a]);
-            }
+            if (pt.bad != 0xffffffffu) return read_fail(pt.why, *A, pt.bad, total_len, read_contig);      // (parts are in record order: this is the first bad record)
             max_span = pt.max_span > max_span ? pt.max_span : max_span;
             sum_span += pt.sum_span;
             if (pt.lo.size() > rr.ctg_min_rb.size()) { rr.ctg_min_rb.resize(pt.lo.size(), 0xffffffffu); rr.ctg_max_re.resize(pt.lo.size(), 0u); }
@@ -1697,68 +1730,49 @@ int hypo_gpu_reads_upload(const HypoArmsReads* A, const uint32_t* read_contig, u
         }
     }
     rr.total_len = total_len;
-    const uint64_t n_cig = na ? A->cigar_off[na] : 0;
     Carver c;
-    const size_t o_rb = c.take((size_t)na * 4), o_re = c.take((size_t)na * 4), o_qae = c.take((size_t)na * 4), o_soff = c.take((size_t)na * 8),
-                 o_reads = c.take(A->reads2_bytes), o_coff = c.take((size_t)(na + 1) * 4), o_cig = c.take(n_cig * 4), o_ctg = c.take((size_t)na * 4),
-                 o_rank = c.take(A->file_rank ? (size_t)na * 4 : 0);
-    HIP_TRY(rr.data.alloc(c.at ? c.at : 256));
-    char* d = (char*)rr.data.p;
+    const size_t o_ctg = c.take((size_t)na * 4);
     hipStream_t st = g_ctx.stream;
-#define UP(off, src, bytes) do { if (bytes) HIP_TRY(h2d(d + (off), (src), (bytes), st)); } while (0)
-    UP(o_rb, A->rb, (size_t)na * 4); UP(o_re, A->re, (size_t)na * 4); UP(o_qae, A->qae, (size_t)na * 4); UP(o_soff, A->seq_off, (size_t)na * 8);
-    UP(o_reads, A->reads2, A->reads2_bytes); if (na) UP(o_coff, A->cigar_off, (size_t)(na + 1) * 4); UP(o_cig, A->cigar, n_cig * 4); UP(o_ctg, read_contig, (size_t)na * 4);
-    if (A->file_rank) UP(o_rank, A->file_rank, (size_t)na * 4);
-#undef UP
+    if (const int rc = reads_to_device(c, rr.data, *A, st, rr.dev)) return rc;
+    const DevAt d{(char*)rr.data.p, st};
+    HIP_TRY(d.up(o_ctg, read_contig, (size_t)na * 4));
     HIP_TRY(hipStreamSynchronize(st));                          // the caller may release its arrays
-    rr.file_rank = A->file_rank ? (const uint32_t*)(d + o_rank) : nullptr;
-    rr.n = na; rr.n_cig = n_cig; rr.reads2_bytes = A->reads2_bytes; rr.max_span = max_span; rr.sum_span = sum_span;
-    rr.rb = (const uint32_t*)(d + o_rb); rr.re = (const uint32_t*)(d + o_re); rr.qae = (const uint32_t*)(d + o_qae); rr.seq_off = (const uint64_t*)(d + o_soff);
-    rr.reads2 = (const uint8_t*)(d + o_reads); rr.cigar_off = (const uint32_t*)(d + o_coff); rr.cigar = (const uint32_t*)(d + o_cig); rr.read_contig = (const uint32_t*)(d + o_ctg);
+    rr.n = na; rr.reads2_bytes = A->reads2_bytes; rr.max_span = max_span; rr.sum_span = sum_span; rr.read_contig = d.u32(o_ctg);
     rr.ready = true;
     return HYPO_OK;
 }
 
 static hypo::SupportReads support_reads_of(const Ctx& c) {
     hypo::SupportReads R;
-    R.n_alignments = c.rr.n; R.rb = c.rr.rb; R.re = c.rr.re; R.qae = c.rr.qae; R.seq_off = c.rr.seq_off; R.reads2 = c.rr.reads2; R.read_contig = c.rr.read_contig;
+    const Ctx::DevReads& d = c.rr.dev;
+    R.n_alignments = c.rr.n; R.rb = d.rb; R.re = d.re; R.qae = d.qae; R.seq_off = d.seq_off; R.reads2 = d.reads2; R.read_contig = c.rr.read_contig;
     R.mean_span = c.rr.n ? (uint32_t)(c.rr.sum_span / c.rr.n) : 0u;
     return R;
 }
 
 int hypo_gpu_support_kmers(uint32_t k, uint64_t n_solid, const uint32_t* spos, const uint64_t* kids, uint32_t* coverage, uint32_t* support) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    if (!g_ctx.rr.ready) return fail(HYPO_E_INVALID, "no resident reads: call hypo_gpu_reads_upload first");
-    if (k < 2 || k > 31) return fail(HYPO_E_INVALID, "k=%u out of range 2..31", k);
+    HYPO_VOTE_ENTRY();
+    if (const int rc = check_k(k)) return rc;
     if (n_solid >= 0xfffffff0ull) return fail(HYPO_E_CAPACITY, "%llu solid k-mers exceed the 32-bit counters of the boundary", (unsigned long long)n_solid);
     if (n_solid && (!spos || !kids || !coverage || !support)) return fail(HYPO_E_INVALID, "NULL buffer");
     if (!n_solid) return HYPO_OK;
     for (uint64_t i = 1; i < n_solid; ++i) if (spos[i - 1] >= spos[i]) return fail(HYPO_E_INVALID, "solid positions are not increasing (entry %llu)", (unsigned long long)i);
     Carver c;
     const size_t o_sp = c.take(n_solid * 4), o_kd = c.take(n_solid * 8), o_cov = c.take(n_solid * 4), o_sup = c.take(n_solid * 4);
-    auto& wk = g_ctx.rr.work;
-    HIP_TRY(wk.alloc(c.at));
-    char* d = (char*)wk.p;
-    hipStream_t st = g_ctx.stream;
-    HIP_TRY(h2d(d + o_sp, spos, n_solid * 4, st));
-    HIP_TRY(h2d(d + o_kd, kids, n_solid * 8, st));
-    HIP_TRY(hipMemsetAsync(d + o_cov, 0, c.at - o_cov, st));
-    HIP_TRY(hypo::support_kmers(support_reads_of(g_ctx), k, (uint32_t)n_solid, (const uint32_t*)(d + o_sp), (const uint64_t*)(d + o_kd), (uint32_t*)(d + o_cov), (uint32_t*)(d + o_sup), st));
-    HIP_TRY(d2h(coverage, d + o_cov, n_solid * 4, st));
-    HIP_TRY(d2h(support, d + o_sup, n_solid * 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return HYPO_OK;
+    HIP_TRY(g_ctx.rr.work.alloc(c.at));
+    const DevAt d{(char*)g_ctx.rr.work.p, g_ctx.stream};
+    HIP_TRY(h2d(d.u32(o_sp), spos, n_solid * 4, d.st));
+    HIP_TRY(h2d(d.u64(o_kd), kids, n_solid * 8, d.st));
+    return vote_run(d, o_cov, o_sup, c.at, n_solid, coverage, support, [&](uint32_t* cov, uint32_t* sup) -> int {
+        HIP_TRY(hypo::support_kmers(support_reads_of(g_ctx), k, (uint32_t)n_solid, d.u32(o_sp), d.u64(o_kd), cov, sup, d.st));
+        return HYPO_OK;
+    });
 }
 
 int hypo_gpu_support_kmers_kept(uint32_t k, uint32_t n_contigs, const uint32_t* handles, const uint32_t* contig_base,
                                 uint32_t* coverage, uint32_t* support, uint64_t* n_solid_total) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    if (!g_ctx.rr.ready) return fail(HYPO_E_INVALID, "no resident reads: call hypo_gpu_reads_upload first");
-    if (k < 2 || k > 31) return fail(HYPO_E_INVALID, "k=%u out of range 2..31", k);
+    HYPO_VOTE_ENTRY();
+    if (const int rc = check_k(k)) return rc;
     if (n_contigs && (!handles || !contig_base)) return fail(HYPO_E_INVALID, "NULL argument");
     uint64_t ns = 0;
     for (uint32_t c = 0; c < n_contigs; ++c) {
@@ -1777,32 +1791,25 @@ int hypo_gpu_support_kmers_kept(uint32_t k, uint32_t n_contigs, const uint32_t* 
     const size_t kid_bytes = narrow ? 4 : 8;
     Carver c;
     const size_t o_sp = c.take(ns * 4), o_kd = c.take(ns * kid_bytes), o_cov = c.take(ns * 4), o_sup = c.take(ns * 4);
-    auto& wk = g_ctx.rr.work;
-    HIP_TRY(wk.alloc(c.at));
-    char* d = (char*)wk.p;
-    hipStream_t st = g_ctx.stream;
+    HIP_TRY(g_ctx.rr.work.alloc(c.at));
+    const DevAt d{(char*)g_ctx.rr.work.p, g_ctx.stream};
     uint64_t at = 0;
     for (uint32_t ci = 0; ci < n_contigs; ++ci) {
         const Ctx::KeptScan& ks = g_ctx.kept[handles[ci]];
         if (!ks.n) continue;
-        HIP_TRY(hypo::add_base(ks.spos, (uint32_t*)(d + o_sp) + at, ks.n, contig_base[ci], st));
-        HIP_TRY(hipMemcpyAsync(d + o_kd + at * kid_bytes, ks.kids, ks.n * kid_bytes, hipMemcpyDeviceToDevice, st));
+        HIP_TRY(hypo::add_base(ks.spos, d.u32(o_sp) + at, ks.n, contig_base[ci], d.st));
+        HIP_TRY(hipMemcpyAsync(d.u8(o_kd + at * kid_bytes), ks.kids, ks.n * kid_bytes, hipMemcpyDeviceToDevice, d.st));
         at += ks.n;
     }
-    HIP_TRY(hipMemsetAsync(d + o_cov, 0, c.at - o_cov, st));
-    if (narrow) HIP_TRY(hypo::support_kmers32(support_reads_of(g_ctx), k, (uint32_t)ns, (const uint32_t*)(d + o_sp), (const uint32_t*)(d + o_kd), (uint32_t*)(d + o_cov), (uint32_t*)(d + o_sup), st));
-    else HIP_TRY(hypo::support_kmers(support_reads_of(g_ctx), k, (uint32_t)ns, (const uint32_t*)(d + o_sp), (const uint64_t*)(d + o_kd), (uint32_t*)(d + o_cov), (uint32_t*)(d + o_sup), st));
-    HIP_TRY(d2h(coverage, d + o_cov, ns * 4, st));
-    HIP_TRY(d2h(support, d + o_sup, ns * 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return HYPO_OK;
+    return vote_run(d, o_cov, o_sup, c.at, ns, coverage, support, [&](uint32_t* cov, uint32_t* sup) -> int {
+        if (narrow) HIP_TRY(hypo::support_kmers32(support_reads_of(g_ctx), k, (uint32_t)ns, d.u32(o_sp), d.u32(o_kd), cov, sup, d.st));
+        else HIP_TRY(hypo::support_kmers(support_reads_of(g_ctx), k, (uint32_t)ns, d.u32(o_sp), d.u64(o_kd), cov, sup, d.st));
+        return HYPO_OK;
+    });
 }
 
 int hypo_gpu_support_minimizers(const HypoMegaWindows* W, uint32_t* coverage, uint32_t* support) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    if (!g_ctx.rr.ready) return fail(HYPO_E_INVALID, "no resident reads: call hypo_gpu_reads_upload first");
+    HYPO_VOTE_ENTRY();
     if (!W || !W->n_contigs || !W->contig_base || !W->reg_base || !W->win_even || !W->info_base || !W->start || !W->mw_off) return fail(HYPO_E_INVALID, "NULL argument");
     const uint32_t nc = W->n_contigs;
     const uint64_t n_start = W->reg_base[nc], n_ent = W->mw_off[W->n_info];
@@ -1836,35 +1843,28 @@ int hypo_gpu_support_minimizers(const HypoMegaWindows* W, uint32_t* coverage, ui
     Carver c;
     const size_t o_cb = c.take((size_t)nc * 4), o_rbase = c.take((size_t)(nc + 1) * 4), o_even = c.take(nc), o_ib = c.take((size_t)nc * 4), o_start = c.take(n_start * 4),
                  o_off = c.take((size_t)(W->n_info + 2) * 4), o_rel = c.take(n_ent * 4), o_min = c.take(n_ent * 4), o_cov = c.take(n_ent * 4), o_sup = c.take(n_ent * 4);
-    auto& wk = g_ctx.rr.work;
-    HIP_TRY(wk.alloc(c.at));
-    char* d = (char*)wk.p;
-    hipStream_t st = g_ctx.stream;
-#define UP(off, src, bytes) do { if (bytes) HIP_TRY(h2d(d + (off), (src), (bytes), st)); } while (0)
-    UP(o_cb, W->contig_base, (size_t)nc * 4); UP(o_rbase, W->reg_base, (size_t)(nc + 1) * 4); UP(o_even, W->win_even, nc); UP(o_ib, W->info_base, (size_t)nc * 4);
-    UP(o_start, W->start, n_start * 4); UP(o_off, W->mw_off, (size_t)(W->n_info + 1) * 4); UP(o_rel, W->rel_pos, n_ent * 4); UP(o_min, W->minimisers, n_ent * 4);
-    UP(o_off + (size_t)(W->n_info + 1) * 4, W->mw_off + W->n_info, 4);          // the pad entry: an empty range behind the last info
-#undef UP
-    HIP_TRY(hipMemsetAsync(d + o_cov, 0, c.at - o_cov, st));
+    HIP_TRY(g_ctx.rr.work.alloc(c.at));
+    const DevAt d{(char*)g_ctx.rr.work.p, g_ctx.stream};
+    HIP_TRY(d.up(o_cb, W->contig_base, (size_t)nc * 4)); HIP_TRY(d.up(o_rbase, W->reg_base, (size_t)(nc + 1) * 4)); HIP_TRY(d.up(o_even, W->win_even, nc));
+    HIP_TRY(d.up(o_ib, W->info_base, (size_t)nc * 4)); HIP_TRY(d.up(o_start, W->start, n_start * 4)); HIP_TRY(d.up(o_off, W->mw_off, (size_t)(W->n_info + 1) * 4));
+    HIP_TRY(d.up(o_rel, W->rel_pos, n_ent * 4)); HIP_TRY(d.up(o_min, W->minimisers, n_ent * 4));
+    HIP_TRY(d.up(o_off + (size_t)(W->n_info + 1) * 4, W->mw_off + W->n_info, 4));          // the pad entry: an empty range behind the last info
     hypo::MegaWindows M;
-    M.contig_base = (const uint32_t*)(d + o_cb); M.reg_base = (const uint32_t*)(d + o_rbase); M.win_even = (const uint8_t*)(d + o_even); M.info_base = (const uint32_t*)(d + o_ib);
-    M.start = (const uint32_t*)(d + o_start); M.mw_off = (const uint32_t*)(d + o_off); M.rel_pos = (uint32_t*)(d + o_rel); M.minimisers = (const uint32_t*)(d + o_min);
-    HIP_TRY(hypo::support_minimizers(support_reads_of(g_ctx), M, nc, W->n_info, (uint32_t*)(d + o_cov), (uint32_t*)(d + o_sup), st));
-    HIP_TRY(d2h(coverage, d + o_cov, n_ent * 4, st));
-    HIP_TRY(d2h(support, d + o_sup, n_ent * 4, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    return HYPO_OK;
+    M.contig_base = d.u32(o_cb); M.reg_base = d.u32(o_rbase); M.win_even = d.u8(o_even); M.info_base = d.u32(o_ib);
+    M.start = d.u32(o_start); M.mw_off = d.u32(o_off); M.rel_pos = d.u32(o_rel); M.minimisers = d.u32(o_min);
+    return vote_run(d, o_cov, o_sup, c.at, n_ent, coverage, support, [&](uint32_t* cov, uint32_t* sup) -> int {
+        HIP_TRY(hypo::support_minimizers(support_reads_of(g_ctx), M, nc, W->n_info, cov, sup, d.st));
+        return HYPO_OK;
+    });
 }
 
 // ---- arm selection on the device (kernels in arms_kernel.hip) ------------------------------------------
 
 // which = 0: short reads -> SHORT windows; 1: long reads over the pseudo regions of Contig::prepare_long_windows -> LONG windows
 static int arms_build_impl(int which, const HypoArmsRegions* R, const HypoArmsReads* A, uint8_t* region_valid, HypoArmsSummary* sum) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
+    HYPO_ENTRY();
     auto& AS = g_ctx.arms[which];
     const bool long_mode = which == 1;
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
     if (!R || !region_valid || !sum) return fail(HYPO_E_INVALID, "NULL argument");
     // reads == NULL: the reads hypo_gpu_reads_upload left on the device (already checked there)
     const bool resident = A == nullptr;
@@ -1873,7 +1873,7 @@ static int arms_build_impl(int which, const HypoArmsRegions* R, const HypoArmsRe
     if (resident) { Ares.n_alignments = g_ctx.rr.n; Ares.reads2_bytes = g_ctx.rr.reads2_bytes; A = &Ares; }
     if (!R->n_regions || !R->start || !R->type || (!long_mode && !R->info) || !R->contig4 || (R->n_anchor_kmers && !R->anchor_kmers)) return fail(HYPO_E_INVALID, "NULL buffer in regions");
     if (!resident && A->n_alignments && (!A->rb || !A->re || !A->qae || !A->seq_off || !A->reads2 || !A->cigar_off || !A->cigar)) return fail(HYPO_E_INVALID, "NULL buffer in reads");
-    if (R->k < 2 || R->k > 31) return fail(HYPO_E_INVALID, "k=%u out of range 2..31", R->k);
+    if (const int rc = check_k(R->k)) return rc;
     AS.ready = false;
     const uint32_t nr = R->n_regions, na = A->n_alignments;
     const uint64_t total_len = R->start[nr];
@@ -1886,10 +1886,7 @@ static int arms_build_impl(int which, const HypoArmsRegions* R, const HypoArmsRe
         max_span = g_ctx.rr.max_span; sum_span = g_ctx.rr.sum_span;
     }
     for (uint32_t a = 0; a < (resident ? 0u : na); ++a) {
-        if (A->re[a] <= A->rb[a] || A->re[a] > total_len) return fail(HYPO_E_INVALID, "alignment %u: span [%u, %u) outside the %llu bases", a, A->rb[a], A->re[a], (unsigned long long)total_len);
-        if (a && A->rb[a - 1] > A->rb[a]) return fail(HYPO_E_INVALID, "alignments are not sorted by reference start (alignment %u)", a);
-        if (A->seq_off[a] + ((uint64_t)A->qae[a] + 3) / 4 > A->reads2_bytes) return fail(HYPO_E_INVALID, "alignment %u: read outside reads2", a);
-        if (A->cigar_off[a] > A->cigar_off[a + 1]) return fail(HYPO_E_INVALID, "alignment %u: cigar_off decreases", a);
+        if (const ReadFault why = read_fault(*A, a, total_len, nullptr)) return read_fail(why, *A, a, total_len, nullptr);
         const uint32_t span = A->re[a] - A->rb[a];
         max_span = span > max_span ? span : max_span;
         sum_span += span;
@@ -1900,38 +1897,22 @@ static int arms_build_impl(int which, const HypoArmsRegions* R, const HypoArmsRe
     if (na && max_span > 16384u && (uint64_t)max_span * na > 64ull * sum_span)
         return fail(HYPO_E_CAPACITY, "an alignment spans %u reference bases, more than 64 x the mean span (%llu): arm selection stays on the host",
                     max_span, (unsigned long long)(sum_span / na));
-    const uint64_t n_cig = resident ? g_ctx.rr.n_cig : (na ? A->cigar_off[na] : 0);
     hipStream_t st = g_ctx.stream;
     DevBuf &dIn = AS.arena[0], &dWork = AS.arena[1], &dBatch = AS.arena[2];
-    // inputs
+    // inputs: the regions, then the reads unless they are resident
     Carver ci;
     const size_t o_start = ci.take((size_t)(nr + 1) * 4), o_type = ci.take(nr + 1), o_info = ci.take((size_t)(nr + 1) * 4),
-                 o_anchor = ci.take(R->n_anchor_kmers * 8), o_contig = ci.take((total_len + 1) / 2), o_rb = ci.take(resident ? 0 : (size_t)na * 4), o_re = ci.take(resident ? 0 : (size_t)na * 4),
-                 o_qae = ci.take(resident ? 0 : (size_t)na * 4), o_soff = ci.take(resident ? 0 : (size_t)na * 8), o_reads = ci.take(resident ? 0 : A->reads2_bytes), o_coff = ci.take(resident ? 0 : (size_t)(na + 1) * 4),
-                 o_cig = ci.take(resident ? 0 : n_cig * 4), o_frank = ci.take((resident || !A->file_rank) ? 0 : (size_t)na * 4);
-    HIP_TRY(dIn.alloc(ci.at));
-    char* in = (char*)dIn.p;
-#define UP(off, src, bytes) do { if (bytes) HIP_TRY(h2d(in + (off), (src), (bytes), st)); } while (0)
-    UP(o_start, R->start, (size_t)(nr + 1) * 4); UP(o_type, R->type, (size_t)nr + 1); if (R->info) UP(o_info, R->info, (size_t)(nr + 1) * 4);
-    UP(o_anchor, R->anchor_kmers, R->n_anchor_kmers * 8); UP(o_contig, R->contig4, (total_len + 1) / 2);
-    if (!resident) {
-        UP(o_rb, A->rb, (size_t)na * 4); UP(o_re, A->re, (size_t)na * 4); UP(o_qae, A->qae, (size_t)na * 4); UP(o_soff, A->seq_off, (size_t)na * 8);
-        UP(o_reads, A->reads2, A->reads2_bytes); if (na) UP(o_coff, A->cigar_off, (size_t)(na + 1) * 4); UP(o_cig, A->cigar, n_cig * 4);
-        if (A->file_rank) UP(o_frank, A->file_rank, (size_t)na * 4);
-    }
-#undef UP
+                 o_anchor = ci.take(R->n_anchor_kmers * 8), o_contig = ci.take((total_len + 1) / 2);
+    Ctx::DevReads dr = g_ctx.rr.dev;
+    if (resident) HIP_TRY(dIn.alloc(ci.at));
+    else if (const int rc = reads_to_device(ci, dIn, *A, st, dr)) return rc;
+    const DevAt in{(char*)dIn.p, st};
+    HIP_TRY(in.up(o_start, R->start, (size_t)(nr + 1) * 4)); HIP_TRY(in.up(o_type, R->type, (size_t)nr + 1)); if (R->info) HIP_TRY(in.up(o_info, R->info, (size_t)(nr + 1) * 4));
+    HIP_TRY(in.up(o_anchor, R->anchor_kmers, R->n_anchor_kmers * 8)); HIP_TRY(in.up(o_contig, R->contig4, (total_len + 1) / 2));
     hypo::ArmsIn I;
-    I.n_regions = nr; I.reg_start = (const uint32_t*)(in + o_start); I.reg_type = (const uint8_t*)(in + o_type); I.reg_info = (const uint32_t*)(in + o_info);
-    I.anchor_kmers = (const uint64_t*)(in + o_anchor); I.k = R->k; I.contig4 = (const uint8_t*)(in + o_contig);
-    I.n_alignments = na; I.rb = (const uint32_t*)(in + o_rb); I.re = (const uint32_t*)(in + o_re); I.qae = (const uint32_t*)(in + o_qae);
-    I.seq_off = (const uint64_t*)(in + o_soff); I.reads2 = (const uint8_t*)(in + o_reads); I.cigar_off = (const uint32_t*)(in + o_coff);
-    I.cigar = (const uint32_t*)(in + o_cig); I.max_span = max_span; I.long_mode = long_mode ? 1u : 0u;
-    I.file_rank = (!resident && A->file_rank) ? (const uint32_t*)(in + o_frank) : nullptr;
-    if (resident) {
-        const auto& rr = g_ctx.rr;
-        I.file_rank = rr.file_rank;
-        I.rb = rr.rb; I.re = rr.re; I.qae = rr.qae; I.seq_off = rr.seq_off; I.reads2 = rr.reads2; I.cigar_off = rr.cigar_off; I.cigar = rr.cigar;
-    }
+    I.n_regions = nr; I.reg_start = in.u32(o_start); I.reg_type = in.u8(o_type); I.reg_info = in.u32(o_info); I.anchor_kmers = in.u64(o_anchor); I.k = R->k; I.contig4 = in.u8(o_contig);
+    I.n_alignments = na; I.rb = dr.rb; I.re = dr.re; I.qae = dr.qae; I.seq_off = dr.seq_off; I.reads2 = dr.reads2; I.cigar_off = dr.cigar_off; I.cigar = dr.cigar;
+    I.file_rank = dr.file_rank; I.max_span = max_span; I.long_mode = long_mode ? 1u : 0u;
     // work arrays that do not depend on the number of touched regions
     Carver cw;
     const size_t scan_n = nr > na ? nr : na;
@@ -1944,16 +1925,16 @@ static int arms_build_impl(int which, const HypoArmsRegions* R, const HypoArmsRe
     const size_t fixed_work = cw.at;
     // the candidate arrays follow: a read of span s touches at most s / (shortest region) + 2 regions; sized after phase 1
     HIP_TRY(dWork.alloc(fixed_work));
-    char* wk = (char*)dWork.p;
-    uint64_t* tot = (uint64_t*)(wk + w_tot);             // [0] touched regions, [1] windows, [2] arms, [3] arm bytes, [4] draft bytes, [5] slot bytes, [6] bad records
+    const DevAt wk{(char*)dWork.p, st};
+    uint64_t* tot = wk.u64(w_tot);             // [0] touched regions, [1] windows, [2] arms, [3] arm bytes, [4] draft bytes, [5] slot bytes, [6] bad records
     HIP_TRY(hipMemsetAsync(tot, 0, 64, st));
-    HIP_TRY(hypo::arms_phase1(I, (uint32_t*)(wk + w_bind), (uint32_t*)(wk + w_nt), (uint32_t*)(tot + 6), st));
-    HIP_TRY(hypo::scan32((const uint32_t*)(wk + w_nt), na, (uint64_t*)(wk + w_toff), (uint64_t*)(wk + w_bsum), tot + 0, st));
+    HIP_TRY(hypo::arms_phase1(I, wk.u32(w_bind), wk.u32(w_nt), (uint32_t*)(tot + 6), st));
+    HIP_TRY(hypo::scan32(wk.u32(w_nt), na, wk.u64(w_toff), wk.u64(w_bsum), tot + 0, st));
     hypo::ArmsOut O{};
     if (long_mode) {      // slots for the minimizers of every LONG window's draft (Filter::initialise): one per base at most
-        O.reg_min_len = (uint32_t*)(wk + w_minlen); O.reg_min_off = (const uint64_t*)(wk + w_minoff); O.reg_min_cnt = (uint32_t*)(wk + w_mincnt);
+        O.reg_min_len = wk.u32(w_minlen); O.reg_min_off = wk.u64(w_minoff); O.reg_min_cnt = wk.u32(w_mincnt);
         HIP_TRY(hypo::arms_long_minlen(I, O, st));
-        HIP_TRY(hypo::scan32(O.reg_min_len, nr, (uint64_t*)(wk + w_minoff), (uint64_t*)(wk + w_bsum), tot + 7, st));
+        HIP_TRY(hypo::scan32(O.reg_min_len, nr, wk.u64(w_minoff), wk.u64(w_bsum), tot + 7, st));
     }
     uint64_t h_tot[8] = {0};
     HIP_TRY(hipMemcpyAsync(h_tot, tot, 64, hipMemcpyDeviceToHost, st));
@@ -1965,20 +1946,18 @@ static int arms_build_impl(int which, const HypoArmsRegions* R, const HypoArmsRe
     Carver cc;
     const size_t c_bp = cc.take(n_touch * 4), c_cand = cc.take(n_touch * 8), c_dmin = cc.take(long_mode ? h_tot[7] * 4 + 16 : 0);
     HIP_TRY(dCand.alloc(cc.at));
-    char* cd = (char*)dCand.p;
-    if (long_mode) { O.draft_min = (uint32_t*)(cd + c_dmin); HIP_TRY(hypo::arms_long_draftmin(I, O, st)); }
-    O.reg_flags = (uint32_t*)(wk + w_flags); O.reg_valid = (uint32_t*)(wk + w_valid); O.reg_counts = (uint4*)(wk + w_counts); O.reg_arms = (uint32_t*)(wk + w_arms);
-    O.reg_bytes = (uint32_t*)(wk + w_bytes); O.reg_bytes_int = (uint32_t*)(wk + w_bint); O.reg_bytes_pre = (uint32_t*)(wk + w_bpre);
-    O.reg_draft_bytes = (uint32_t*)(wk + w_dbytes); O.reg_slot = (uint32_t*)(wk + w_slot);
-    O.reg_arm_off = (const uint64_t*)(wk + w_armoff); O.reg_byte_off = (const uint64_t*)(wk + w_byteoff); O.reg_draft_off = (const uint64_t*)(wk + w_droff);
-    O.reg_slot_off = (const uint64_t*)(wk + w_slotoff); O.win_index = (uint32_t*)(wk + w_widx);
-    HIP_TRY(hypo::arms_phase2(I, (const uint32_t*)(wk + w_bind), (const uint32_t*)(wk + w_nt), (const uint64_t*)(wk + w_toff), (uint32_t*)(cd + c_bp), (uint2*)(cd + c_cand), O, st));
-    uint64_t* bsum = (uint64_t*)(wk + w_bsum);
-    HIP_TRY(hypo::scan32(O.reg_valid, nr, (uint64_t*)(wk + w_winoff), bsum, tot + 1, st));
-    HIP_TRY(hypo::scan32(O.reg_arms, nr, (uint64_t*)(wk + w_armoff), bsum, tot + 2, st));
-    HIP_TRY(hypo::scan32(O.reg_bytes, nr, (uint64_t*)(wk + w_byteoff), bsum, tot + 3, st));
-    HIP_TRY(hypo::scan32(O.reg_draft_bytes, nr, (uint64_t*)(wk + w_droff), bsum, tot + 4, st));
-    HIP_TRY(hypo::scan32(O.reg_slot, nr, (uint64_t*)(wk + w_slotoff), bsum, tot + 5, st));
+    const DevAt cd{(char*)dCand.p, st};
+    if (long_mode) { O.draft_min = cd.u32(c_dmin); HIP_TRY(hypo::arms_long_draftmin(I, O, st)); }
+    O.reg_flags = wk.u32(w_flags); O.reg_valid = wk.u32(w_valid); O.reg_counts = wk.at<uint4>(w_counts); O.reg_arms = wk.u32(w_arms); O.reg_bytes = wk.u32(w_bytes);
+    O.reg_bytes_int = wk.u32(w_bint); O.reg_bytes_pre = wk.u32(w_bpre); O.reg_draft_bytes = wk.u32(w_dbytes); O.reg_slot = wk.u32(w_slot); O.reg_arm_off = wk.u64(w_armoff);
+    O.reg_byte_off = wk.u64(w_byteoff); O.reg_draft_off = wk.u64(w_droff); O.reg_slot_off = wk.u64(w_slotoff); O.win_index = wk.u32(w_widx);
+    HIP_TRY(hypo::arms_phase2(I, wk.u32(w_bind), wk.u32(w_nt), wk.u64(w_toff), cd.u32(c_bp), cd.at<uint2>(c_cand), O, st));
+    uint64_t* bsum = wk.u64(w_bsum);
+    HIP_TRY(hypo::scan32(O.reg_valid, nr, wk.u64(w_winoff), bsum, tot + 1, st));
+    HIP_TRY(hypo::scan32(O.reg_arms, nr, wk.u64(w_armoff), bsum, tot + 2, st));
+    HIP_TRY(hypo::scan32(O.reg_bytes, nr, wk.u64(w_byteoff), bsum, tot + 3, st));
+    HIP_TRY(hypo::scan32(O.reg_draft_bytes, nr, wk.u64(w_droff), bsum, tot + 4, st));
+    HIP_TRY(hypo::scan32(O.reg_slot, nr, wk.u64(w_slotoff), bsum, tot + 5, st));
     HIP_TRY(hipMemcpyAsync(h_tot, tot, 64, hipMemcpyDeviceToHost, st));
     std::vector<uint32_t> valid32(nr);
     HIP_TRY(hipMemcpyAsync(valid32.data(), O.reg_valid, (size_t)nr * 4, hipMemcpyDeviceToHost, st));
@@ -1992,12 +1971,10 @@ static int arms_build_impl(int which, const HypoArmsRegions* R, const HypoArmsRe
     const size_t b_win = cb.take(n_win * sizeof(HypoWindow)), b_wreg = cb.take(n_win * 4), b_alen = cb.take(n_arms * 4), b_aoff = cb.take(n_arms * 8),
                  b_arms2 = cb.take(arm_bytes + 16), b_draft = cb.take(draft_bytes + 16), b_ooff = cb.take((n_win + 1) * 8);
     HIP_TRY(dBatch.alloc(cb.at));
-    char* bt = (char*)dBatch.p;
-    O.windows = (HypoWindow*)(bt + b_win); O.win_region = (uint32_t*)(bt + b_wreg); O.arm_len = (uint32_t*)(bt + b_alen); O.arm_off = (uint64_t*)(bt + b_aoff);
-    O.arms2 = (uint8_t*)(bt + b_arms2); O.draft4 = (uint8_t*)(bt + b_draft); O.out_off = (uint64_t*)(bt + b_ooff);
+    const DevAt bt{(char*)dBatch.p, st};
+    O.windows = bt.at<HypoWindow>(b_win); O.win_region = bt.u32(b_wreg); O.arm_len = bt.u32(b_alen); O.arm_off = bt.u64(b_aoff); O.arms2 = bt.u8(b_arms2); O.draft4 = bt.u8(b_draft); O.out_off = bt.u64(b_ooff);
     if (n_win) {
-        HIP_TRY(hypo::arms_phase3(I, (const uint32_t*)(wk + w_bind), (const uint32_t*)(wk + w_nt), (const uint64_t*)(wk + w_toff), (const uint2*)(cd + c_cand), O,
-                                  (const uint64_t*)(wk + w_winoff), st));
+        HIP_TRY(hypo::arms_phase3(I, wk.u32(w_bind), wk.u32(w_nt), wk.u64(w_toff), cd.at<uint2>(c_cand), O, wk.u64(w_winoff), st));
         HIP_TRY(hipMemcpyAsync(O.out_off + n_win, tot + 5, 8, hipMemcpyDeviceToDevice, st));
     }
     sum->n_windows = (uint32_t)n_win; sum->n_arms = (uint32_t)n_arms; sum->arms2_bytes = arm_bytes; sum->draft4_bytes = draft_bytes; sum->out_bytes = slot_bytes;
@@ -2007,12 +1984,14 @@ static int arms_build_impl(int which, const HypoArmsRegions* R, const HypoArmsRe
 int hypo_gpu_arms_build(const HypoArmsRegions* R, const HypoArmsReads* A, uint8_t* region_valid, HypoArmsSummary* sum) { return arms_build_impl(0, R, A, region_valid, sum); }
 int hypo_gpu_arms_build_long(const HypoArmsRegions* R, const HypoArmsReads* A, uint8_t* region_valid, HypoArmsSummary* sum) { return arms_build_impl(1, R, A, region_valid, sum); }
 
+static int check_batch(int which) {                   // download and POA need what hypo_gpu_arms_build (which = 0) / _long (1) left on the device
+    return g_ctx.arms[which].ready ? HYPO_OK : fail(HYPO_E_INVALID, "no resident batch: call hypo_gpu_arms_build%s first", which ? "_long" : "");
+}
+
 static int arms_download_impl(int which, HypoWindow* windows, uint32_t* win_region, uint32_t* arm_len, uint64_t* arm_off, uint8_t* arms2, uint8_t* draft4) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    HYPO_ENTRY();
+    if (const int rc = check_batch(which)) return rc;
     auto& AS = g_ctx.arms[which];
-    if (!AS.ready) return fail(HYPO_E_INVALID, "no resident batch: call hypo_gpu_arms_build%s first", which ? "_long" : "");
     const HypoArmsSummary& S = AS.sum; const hypo::ArmsOut& O = AS.out;
     hipStream_t st = g_ctx.stream;
     if (windows && S.n_windows) HIP_TRY(hipMemcpyAsync(windows, O.windows, (size_t)S.n_windows * sizeof(HypoWindow), hipMemcpyDeviceToHost, st));
@@ -2033,13 +2012,10 @@ int hypo_gpu_arms_download_long(HypoWindow* windows, uint32_t* win_region, uint3
 }
 
 static int arms_poa_impl(int which, const HypoScoreParams* scores, char* bases, uint64_t* off, uint32_t* len, uint8_t* status) {
-    HYPO_LOCKED();
-    HYPO_ON_DEVICE();
-    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
-    int rc = check_scores(scores);
-    if (rc) return rc;
+    HYPO_ENTRY();
+    if (const int rc = check_scores(scores)) return rc;
+    if (const int rc = check_batch(which)) return rc;
     auto& AS = g_ctx.arms[which];
-    if (!AS.ready) return fail(HYPO_E_INVALID, "no resident batch: call hypo_gpu_arms_build%s first", which ? "_long" : "");
     const HypoArmsSummary& S = AS.sum; const hypo::ArmsOut& O = AS.out;
     memset(&tl_stats, 0, sizeof(tl_stats));
     const uint32_t n = S.n_windows;

@@ -7,37 +7,9 @@ import numpy as np
 import pytest
 
 from hypo_amd import abi, capi, sim
+from capi_util import ArmsReads, exact_reads as _reads, ptr as _p
 
 pytestmark = pytest.mark.gpu
-
-
-class ArmsReads(C.Structure):                      # HypoArmsReads, include/hypo_gpu.h
-    _fields_ = [("n_alignments", C.c_uint32), ("rb", C.c_void_p), ("re", C.c_void_p), ("qae", C.c_void_p), ("seq_off", C.c_void_p),
-                ("reads2", C.c_void_p), ("reads2_bytes", C.c_uint64), ("cigar_off", C.c_void_p), ("cigar", C.c_void_p), ("file_rank", C.c_void_p)]
-
-
-def _p(a):
-    return a.ctypes.data_as(C.c_void_p)
-
-
-def _reads(codes, n_reads, read_len, rng):
-    """n_reads exact copies of stretches of the contig, sorted by start: (rb, re, qae, seq_off, reads2, cigar_off, cigar)."""
-    n = codes.size
-    rb = np.sort(rng.integers(0, n - read_len, size=n_reads)).astype(np.uint32)
-    keep = np.array([bool((codes[b:b + read_len] < 4).all()) for b in rb])       # (a read over an N would not pack in 2 bits)
-    rb = rb[keep]
-    m = rb.size
-    nb = (read_len + 3) // 4
-    reads2 = np.zeros(m * nb, dtype=np.uint8)
-    for i, b in enumerate(rb):
-        c = np.concatenate([codes[b:b + read_len], np.zeros((-read_len) % 4, np.uint8)]).reshape(-1, 4)
-        reads2[i * nb:(i + 1) * nb] = (c[:, 0] << 6) | (c[:, 1] << 4) | (c[:, 2] << 2) | c[:, 3]
-    re = (rb + read_len).astype(np.uint32)
-    qae = np.full(m, read_len, dtype=np.uint32)
-    seq_off = (np.arange(m, dtype=np.uint64) * nb).astype(np.uint64)
-    cigar_off = np.arange(m + 1, dtype=np.uint32)
-    cigar = np.full(m, (read_len << 4) | 0, dtype=np.uint32)
-    return rb, re, qae, seq_off, reads2, cigar_off, cigar
 
 
 @pytest.mark.parametrize("n_bases,k", [(300_001, 11), (1_000_000, 13)])
