@@ -19,6 +19,11 @@ HYPO_E_UNSUPPORTED = -7
 # hypo_gpu_kset_query_track: what hypo_amd.capi puts into the interval arrays before a call (no position or count is that large)
 TRACK_UNTOUCHED = 0xFFFFFFFFFFFFFFFF
 
+# hypo_gpu_kset_counts_enable / _mark / _spectrum (HYPO_KSET_MAX_TEXTS, HYPO_KSET_SPECTRUM_BINS): hist[count * 5 + min(copies, 4)]
+KSET_MAX_TEXTS = 4
+KSET_SPECTRUM_ROWS, KSET_SPECTRUM_COLS = 256, 5
+KSET_SPECTRUM_BINS = KSET_SPECTRUM_ROWS * KSET_SPECTRUM_COLS
+
 ST_OK = 0
 ST_CONS_OVERFLOW = 1
 ST_CAPACITY = 2

@@ -31,6 +31,7 @@ EXPORTS = [
     "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts",
     "hypo_gpu_kset_begin", "hypo_gpu_kset_add", "hypo_gpu_kset_size", "hypo_gpu_kset_query", "hypo_gpu_kset_end",
     "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants", "hypo_gpu_kset_query_track",
+    "hypo_gpu_kset_counts_enable", "hypo_gpu_kset_mark", "hypo_gpu_kset_spectrum",
 ]
 KSET_SPAN_PIECE = 2048        # windows per piece of a long span (kset_kernel.hpp)
 KSET_MAX_EDITS = 12           # edits of a site of hypo_gpu_kset_query_variants (HYPO_KSET_MAX_EDITS)
@@ -372,6 +373,39 @@ class HypoGpu:
             out = self.kset_query_track_rc(seqs_or_text, off, want, int(out[3][-1]))
         self._check(out[0])
         return out[1:]
+
+    def kset_counts_enable_rc(self, n_texts: int) -> int:
+        return int(self.lib.hypo_gpu_kset_counts_enable(C.c_uint32(n_texts)))
+
+    def kset_counts_enable(self, n_texts: int):
+        """after kset_begin, while the set is empty: kset_add counts every window from here on, and n_texts texts can be marked"""
+        self._check(self.kset_counts_enable_rc(n_texts))
+
+    def kset_mark_rc(self, text: int, seqs):
+        """(return code, windows, unmarked windows) of one call of hypo_gpu_kset_mark; nothing is checked here"""
+        seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs]
+        off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+        data = np.frombuffer(b"".join(seqs) + b"\0", dtype=np.uint8)      # (an empty text still has an address)
+        n_win, n_un = C.c_uint64(0), C.c_uint64(0)
+        rc = int(self.lib.hypo_gpu_kset_mark(C.c_uint32(text), _p(data), _p(off), C.c_uint32(len(seqs)), C.byref(n_win), C.byref(n_un)))
+        return rc, int(n_win.value), int(n_un.value)
+
+    def kset_mark(self, text: int, seqs):
+        """every window of the sequences adds 1 to its k-mer's copy number in `text`.  (windows, those whose k-mer is not in the set)"""
+        rc, n_win, n_un = self.kset_mark_rc(text, seqs)
+        self._check(rc)
+        return n_win, n_un
+
+    def kset_spectrum_rc(self, text: int):
+        hist = np.zeros(abi.KSET_SPECTRUM_BINS, dtype=np.uint64)
+        return int(self.lib.hypo_gpu_kset_spectrum(C.c_uint32(text), _p(hist))), hist.reshape(abi.KSET_SPECTRUM_ROWS, abi.KSET_SPECTRUM_COLS)
+
+    def kset_spectrum(self, text: int) -> np.ndarray:
+        """u64[256, 5]: [c, j] = the k-mers of the set seen c times in the reads (255: or more) and min(j, 4) times in `text`"""
+        rc, hist = self.kset_spectrum_rc(text)
+        self._check(rc)
+        return hist
 
     def kset_end(self):
         self._check(self.lib.hypo_gpu_kset_end())

@@ -159,10 +159,15 @@ struct Ctx {
     struct EditBufs { DevBuf a, b, a_off, b_off, res, pool, lists, ctr, moves, moves_off, vals, vals_off; EditKept kept; };
     EditBufs ed;
     // hypo_gpu_kset_begin .. _end: the hash table (exact size; replaced by a larger one when it grows), the number of keys in it, the
-    // bytes / offsets / results of the call in hand, the two counters of the kernels; what the growths cost (HYPO_KSET_STATS)
+    // bytes / offsets / results of the call in hand, the two counters of the kernels; what the growths cost (HYPO_KSET_STATS).
+    // hypo_gpu_kset_counts_enable: n_texts > 0, and `planes` (exact size, replaced with the table) holds the count bytes of the reads
+    // and n_texts planes of copy bytes (kset_kernel.hpp); `marked`: a text has been marked, the set takes no more reads
     struct KSet {
         uint64_t* table = nullptr; uint64_t slots = 0, max_slots = 0, count = 0; uint32_t k = 0; DevBuf in, off, res, ctr;
         uint32_t growths = 0; double grow_s = 0; uint64_t peak_slots = 0;
+        uint64_t max_bytes = 0; uint32_t n_texts = 0; uint32_t* planes = nullptr; bool marked = false;
+        uint64_t plane_bytes(uint64_t n_slots) const { return n_texts ? (1 + (uint64_t)n_texts) * hypo::ks_plane_words(n_slots) * 4 : 0; }
+        double slot_bytes() const { return n_texts ? 9.0 + n_texts : 8.0; }      // what max_bytes caps, per slot
     };
     KSet ks;
     size_t mem_free_at_init = 0;                       // hipMemGetInfo when the context was created (default cap of the k-mer set)
@@ -468,6 +473,7 @@ static void release_ctx(Ctx& c) {
         for (DevBuf* d : {&c.ed.a, &c.ed.b, &c.ed.a_off, &c.ed.b_off, &c.ed.res, &c.ed.pool, &c.ed.lists, &c.ed.ctr, &c.ed.moves, &c.ed.moves_off, &c.ed.vals, &c.ed.vals_off}) d->release();
         c.ed.kept = Ctx::EditKept();
         if (c.ks.table) (void)hipFree(c.ks.table);
+        if (c.ks.planes) (void)hipFree(c.ks.planes);
         for (DevBuf* d : {&c.ks.in, &c.ks.off, &c.ks.res, &c.ks.ctr}) d->release();
         c.ks = Ctx::KSet();
         c.bounce.release();
@@ -1153,25 +1159,34 @@ uint64_t ks_slots_for(uint64_t keys) {                 // the smallest table tha
     const uint64_t s = (uint64_t)((double)keys / hypo::KSET_MAX_LOAD) + 1;
     return s < hypo::KSET_MIN_SLOTS ? hypo::KSET_MIN_SLOTS : s;
 }
-// A fresh table of `slots` slots takes the keys of the present one (if any) and its place.
+// A fresh table of `slots` slots takes the keys of the present one (if any) and its place; with counts on, fresh planes beside it
+// take the count bytes (the copy bytes are zero until the set is closed, and a closed set does not grow).
 int ks_resize(Ctx::KSet& ks, uint64_t slots, hipStream_t st) {
     const double t0 = ks_now();
     uint64_t* fresh = nullptr;
+    uint32_t* fresh_planes = nullptr;
     hipError_t e = hipMalloc((void**)&fresh, slots * 8);
+    if (e == hipSuccess && ks.n_texts && (e = hipMalloc((void**)&fresh_planes, ks.plane_bytes(slots))) != hipSuccess) { (void)hipFree(fresh); fresh = nullptr; }
     if (e != hipSuccess) { (void)hipGetLastError(); return fail(HYPO_E_HIP, "hipMalloc of a k-mer set table of %.3f GiB (%llu k-mers in the set): %s",
-                                                                 (double)slots * 8 / (1u << 30), (unsigned long long)ks.count, hipGetErrorString(e)); }
+                                                                 (double)slots * ks.slot_bytes() / (1u << 30), (unsigned long long)ks.count, hipGetErrorString(e)); }
+    auto drop = [&] { (void)hipFree(fresh); if (fresh_planes) (void)hipFree(fresh_planes); };
     unsigned long long ctr[2] = {0, 0};
-    if ((e = hipMemsetAsync(fresh, 0xff, slots * 8, st)) == hipSuccess && (e = hipMemsetAsync(ks.ctr.p, 0, 16, st)) == hipSuccess && ks.table)
-        e = hypo::kset_rehash_run(ks.table, ks.slots, fresh, slots, (unsigned long long*)ks.ctr.p, st);
+    if ((e = hipMemsetAsync(fresh, 0xff, slots * 8, st)) == hipSuccess && (e = hipMemsetAsync(ks.ctr.p, 0, 16, st)) == hipSuccess && fresh_planes)
+        e = hipMemsetAsync(fresh_planes, 0, ks.plane_bytes(slots), st);
+    if (e == hipSuccess && ks.table)
+        e = ks.planes ? hypo::kset_rehash_count_run(ks.table, ks.slots, ks.planes, fresh, slots, fresh_planes, (unsigned long long*)ks.ctr.p, st)
+                      : hypo::kset_rehash_run(ks.table, ks.slots, fresh, slots, (unsigned long long*)ks.ctr.p, st);
     if (e == hipSuccess) e = hipMemcpyAsync(ctr, ks.ctr.p, 16, hipMemcpyDeviceToHost, st);
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(fresh); return fail(HYPO_E_HIP, "k-mer set: resizing to %llu slots: %s", (unsigned long long)slots, hipGetErrorString(e)); }
+    if (e != hipSuccess) { drop(); return fail(HYPO_E_HIP, "k-mer set: resizing to %llu slots: %s", (unsigned long long)slots, hipGetErrorString(e)); }
     if (ctr[1] || ctr[0] != ks.count) {
-        (void)hipFree(fresh);
+        drop();
         return fail(HYPO_E_HIP, "k-mer set: internal error: %llu of %llu keys moved into %llu slots (overflow flag %llu)", ctr[0],
                     (unsigned long long)ks.count, (unsigned long long)slots, ctr[1]);
     }
     if (ks.table) { (void)hipFree(ks.table); ++ks.growths; ks.grow_s += ks_now() - t0; }
+    if (ks.planes) (void)hipFree(ks.planes);
+    ks.planes = fresh_planes;
     ks.table = fresh; ks.slots = slots;
     if (slots > ks.peak_slots) ks.peak_slots = slots;
     return HYPO_OK;
@@ -1239,8 +1254,10 @@ int hypo_gpu_kset_begin(uint32_t k, uint64_t expected_distinct, uint64_t max_byt
     if (max_slots < 2) return fail(HYPO_E_INVALID, "max_bytes = %llu holds no table", (unsigned long long)max_bytes);
     Ctx::KSet& ks = g_ctx.ks;
     if (ks.table) { (void)hipFree(ks.table); ks.table = nullptr; }
+    if (ks.planes) { (void)hipFree(ks.planes); ks.planes = nullptr; }
     ks.k = 0; ks.slots = 0; ks.count = 0; ks.growths = 0; ks.grow_s = 0; ks.peak_slots = 0;
-    ks.max_slots = max_slots;
+    ks.n_texts = 0; ks.marked = false;
+    ks.max_slots = max_slots; ks.max_bytes = max_bytes;
     HIP_TRY(ks.ctr.alloc(16));
     uint64_t slots = ks_slots_for(expected_distinct < ((uint64_t)1 << 62) ? expected_distinct : ((uint64_t)1 << 62));
     if (slots > max_slots) slots = max_slots;
@@ -1252,6 +1269,7 @@ int hypo_gpu_kset_begin(uint32_t k, uint64_t expected_distinct, uint64_t max_byt
 
 int hypo_gpu_kset_add(const char* bytes, uint64_t n) {
     HYPO_KSET_ENTRY();
+    if (ks.marked) return fail(HYPO_E_INVALID, "the k-mer set is closed: a text has been marked (hypo_gpu_kset_mark)");
     if (n < ks.k) return HYPO_OK;                                       // holds no k-mer
     if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
     hipStream_t st = g_ctx.stream;
@@ -1262,21 +1280,24 @@ int hypo_gpu_kset_add(const char* bytes, uint64_t n) {
     if (need > ks.slots) {
         if (need > ks.max_slots)
             return fail(HYPO_E_CAPACITY, "the k-mer set holds %llu distinct %u-mers in a table of %.3f GiB; %llu more windows need %.3f GiB, the cap is %.3f GiB (--qv-mem)",
-                        (unsigned long long)ks.count, ks.k, (double)ks.slots * 8 / (1u << 30), (unsigned long long)(n - ks.k + 1),
-                        (double)need * 8 / (1u << 30), (double)ks.max_slots * 8 / (1u << 30));
+                        (unsigned long long)ks.count, ks.k, (double)ks.slots * ks.slot_bytes() / (1u << 30), (unsigned long long)(n - ks.k + 1),
+                        (double)need * ks.slot_bytes() / (1u << 30), (double)ks.max_slots * ks.slot_bytes() / (1u << 30));
         uint64_t slots = need > 2 * ks.slots ? need : 2 * ks.slots;
         if (slots > ks.max_slots) slots = ks.max_slots;
         const int rc = ks_resize(ks, slots, st);
         if (rc != HYPO_OK) return rc;
     }
     HIP_TRY(ks.in.alloc(n < kKmerPiece ? n : kKmerPiece));
-    // pieces as in hypo_gpu_kmer_count_add; a k-mer seen by two pieces is inserted twice, which changes nothing
+    // pieces as in hypo_gpu_kmer_count_add; a k-mer seen by two pieces is inserted twice, which changes nothing.  With counts on
+    // every WINDOW must be in one piece only: consecutive pieces overlap by exactly k - 1 bytes (the step below), so a window lies
+    // whole in the piece its first byte is new to, and inside a launch a lane owns the windows that start in its stretch.
     for (uint64_t at = 0;;) {
         const uint64_t m = n - at < kKmerPiece ? n - at : kKmerPiece;
         unsigned long long ctr[2] = {0, 0};
         HIP_TRY(h2d(ks.in.p, bytes + at, m, st));
         HIP_TRY(hipMemsetAsync(ks.ctr.p, 0, 16, st));
-        HIP_TRY(hypo::kset_insert_run((const uint8_t*)ks.in.p, m, ks.k, ks.table, ks.slots, (unsigned long long*)ks.ctr.p, st));
+        HIP_TRY(ks.planes ? hypo::kset_insert_count_run((const uint8_t*)ks.in.p, m, ks.k, ks.table, ks.slots, (unsigned long long*)ks.ctr.p, ks.planes, st)
+                          : hypo::kset_insert_run((const uint8_t*)ks.in.p, m, ks.k, ks.table, ks.slots, (unsigned long long*)ks.ctr.p, st));
         HIP_TRY(hipMemcpyAsync(ctr, ks.ctr.p, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));                   // (the caller may refill `bytes` when this returns)
         ks.count += ctr[0];
@@ -1293,7 +1314,7 @@ int hypo_gpu_kset_size(uint64_t* n_distinct, uint64_t* table_bytes) {
     const Ctx::KSet& ks = g_ctx.ks;
     if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)");
     if (n_distinct) *n_distinct = ks.count;
-    if (table_bytes) *table_bytes = ks.slots * 8;
+    if (table_bytes) *table_bytes = ks.slots * 8 + ks.plane_bytes(ks.slots);
     return HYPO_OK;
 }
 
@@ -1508,6 +1529,72 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
     return HYPO_OK;
 }
 
+// ---- read counts, copy numbers and the spectrum (hypo --qv-spectra) ---------------------------------------------------------------
+int hypo_gpu_kset_counts_enable(uint32_t n_texts) {
+    HYPO_KSET_ENTRY();
+    if (n_texts < 1 || n_texts > hypo::KSET_MAX_TEXTS) return fail(HYPO_E_INVALID, "n_texts = %u out of range 1..%u", n_texts, hypo::KSET_MAX_TEXTS);
+    if (ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set counts already");
+    if (ks.count) return fail(HYPO_E_INVALID, "the k-mer set holds %llu k-mers: counts are enabled while it is empty, right after hypo_gpu_kset_begin", (unsigned long long)ks.count);
+    const uint64_t max_slots = ks.max_bytes / (9 + n_texts);
+    if (max_slots < 2) return fail(HYPO_E_INVALID, "max_bytes = %llu holds no table with counts", (unsigned long long)ks.max_bytes);
+    // the (empty) table is replaced by one with its planes beside it, smaller when the cap of 9 + n_texts bytes a slot asks for it
+    const uint64_t was_max = ks.max_slots;
+    const uint32_t growths = ks.growths;
+    const double grow_s = ks.grow_s;
+    ks.n_texts = n_texts; ks.max_slots = max_slots;
+    const int rc = ks_resize(ks, ks.slots < max_slots ? ks.slots : max_slots, g_ctx.stream);
+    if (rc != HYPO_OK) { ks.n_texts = 0; ks.max_slots = was_max; return rc; }
+    ks.growths = growths; ks.grow_s = grow_s;                          // (nothing was moved)
+    return HYPO_OK;
+}
+
+int hypo_gpu_kset_mark(uint32_t text, const char* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t* n_windows, uint64_t* n_unmarked) {
+    HYPO_KSET_ENTRY();
+    if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)");
+    if (text >= ks.n_texts) return fail(HYPO_E_INVALID, "text = %u, the set has %u", text, ks.n_texts);
+    std::vector<uint64_t> rel(1, 0);
+    if (n_seqs) {
+        if (!off) return fail(HYPO_E_INVALID, "NULL buffer");
+        if (const int rc = ks_rel_offsets(off, n_seqs, rel)) return rc;
+        if (rel[n_seqs] && !bytes) return fail(HYPO_E_INVALID, "NULL buffer");
+    }
+    ks.marked = true;                                                  // from here on the copy bytes may be other than zero
+    unsigned long long sums[2] = {0, 0};
+    const uint64_t n = rel.back();
+    if (n) {
+        hipStream_t st = g_ctx.stream;
+        HIP_TRY(ks.in.alloc(n));
+        HIP_TRY(ks.off.alloc(rel.size() * 8));
+        HIP_TRY(ks.res.alloc(16));
+        HIP_TRY(h2d(ks.in.p, bytes + off[0], n, st));
+        HIP_TRY(hipMemcpyAsync(ks.off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
+        HIP_TRY(hipMemsetAsync(ks.res.p, 0, 16, st));
+        HIP_TRY(hypo::kset_mark_run((const uint8_t*)ks.in.p, (const uint64_t*)ks.off.p, n_seqs, n, ks.k, ks.table, ks.slots, ks.planes, text,
+                                    (unsigned long long*)ks.res.p, st));
+        HIP_TRY(hipMemcpyAsync(sums, ks.res.p, 16, hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    if (n_windows) *n_windows = sums[0];
+    if (n_unmarked) *n_unmarked = sums[1];
+    return HYPO_OK;
+}
+
+int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist) {
+    HYPO_KSET_ENTRY();
+    if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)");
+    if (text >= ks.n_texts) return fail(HYPO_E_INVALID, "text = %u, the set has %u", text, ks.n_texts);
+    if (!hist) return fail(HYPO_E_INVALID, "NULL buffer");
+    hipStream_t st = g_ctx.stream;
+    constexpr size_t kBytes = (size_t)hypo::KSET_HIST_BINS * 8;
+    static_assert(hypo::KSET_HIST_BINS == HYPO_KSET_SPECTRUM_BINS, "the header's size of hist[]");
+    HIP_TRY(ks.res.alloc(kBytes));
+    HIP_TRY(hipMemsetAsync(ks.res.p, 0, kBytes, st));
+    HIP_TRY(hypo::kset_spectrum_run(ks.planes, ks.slots, text, (unsigned long long*)ks.res.p, st));
+    HIP_TRY(hipMemcpyAsync(hist, ks.res.p, kBytes, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HYPO_OK;
+}
+
 int hypo_gpu_kset_end(void) {
     HYPO_LOCKED();
     HYPO_ON_DEVICE();
@@ -1516,6 +1603,7 @@ int hypo_gpu_kset_end(void) {
         fprintf(stderr, "[kset] k %u, %llu keys, %llu slots (peak %llu), %u growths in %.6f s\n", ks.k, (unsigned long long)ks.count,
                 (unsigned long long)ks.slots, (unsigned long long)ks.peak_slots, ks.growths, ks.grow_s);
     if (ks.table) HIP_TRY(hipFree(ks.table));
+    if (ks.planes) HIP_TRY(hipFree(ks.planes));
     for (DevBuf* d : {&ks.in, &ks.off, &ks.res, &ks.ctr}) d->release();
     ks = Ctx::KSet();
     return HYPO_OK;

@@ -5,6 +5,7 @@
 #include "EditVcf.hpp"
 #include "KmerGuard.hpp"
 #include "QvReport.hpp"
+#include "SpectraReport.hpp"
 #include <ctime>
 #include <omp.h>
 #include <sys/resource.h>
@@ -16,13 +17,15 @@
 namespace hypo {
 extern std::atomic<uint64_t> g_stage_counters[5];      // host/Contig.cpp
 
-// --vcf, --qv, --qv-bed, --kmer-guard: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
+// --vcf, --qv, --qv-bed, --qv-spectra, --kmer-guard: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
 struct Extras {
     EditScriptsFn edit_fn = nullptr, guard_edit_fn = nullptr;
     QvReport qv;
     KmerGuard guard;
-    bool qv_on = false, bed_on = false, guard_on = false;
+    SpectraReport spectra;
+    bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false;
     bool ask_on = false;                                   // --qv or --qv-bed: every contig's texts are put to the set
+    bool text_on = false;                                  // ... or --qv-spectra: every contig's texts are needed as strings
     bool set_on = false;                                   // ... or --kmer-guard: the set is built
     ReadSink qv_sink;                                      // (holds a pointer to qv: an Extras stays where it is)
     VcfStats vstats;
@@ -31,6 +34,15 @@ struct Extras {
         std::fprintf(stderr, "[Hypo::QV] Error: %s: %s\n", what, hypo_gpu_last_error());
         qv.end();
         std::exit(1);
+    }
+    // one contig's two texts to whoever wants them: the set's queries, then the marks of --qv-spectra
+    int texts(size_t contig, const std::string& draft, const std::string& polished) {
+        const int rc = ask_on ? qv.push(contig, draft, polished) : HYPO_OK;
+        return rc == HYPO_OK && spectra_on ? spectra.push(draft, polished) : rc;
+    }
+    int texts_flush() {
+        const int rc = ask_on ? qv.flush() : HYPO_OK;
+        return rc == HYPO_OK && spectra_on ? spectra.flush() : rc;
     }
     void qv_reads_done(const SolidBuildStats& st, bool shared_pass) {
         if (qv.read_size() != HYPO_OK) qv_fail("hypo_gpu_kset_size");
@@ -139,6 +151,12 @@ void Hypo::polish() {
 
 // ---- once per run, before the batches ----------------------------------------------------------------------------------------
 void Hypo::bind_extras(Extras& ex) {
+    // --qv-spectra: counts on the set, bound by name and only under the flag.  Checked first: its error names them.
+    ex.spectra_on = !_cFlags.qv_spectra_filename.empty();
+    if (ex.spectra_on && !(ex.spectra.bind() && ex.qv.bind())) {
+        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv-spectra needs hypo_gpu_kset_counts_enable, hypo_gpu_kset_mark and hypo_gpu_kset_spectrum, and hypo_gpu_kset_begin / _add / _size / _end, which the device library does not provide\n");
+        std::exit(1);
+    }
     // --qv-bed: the track query, bound by name and only under the flag, and the set it asks.  Checked first: its error names it.
     ex.bed_on = !_cFlags.qv_bed_filename.empty();
     if (ex.bed_on && !(ex.qv.bind_track() && ex.qv.bind())) {
@@ -176,13 +194,19 @@ void Hypo::bind_extras(Extras& ex) {
         std::exit(1);
     }
     ex.ask_on = ex.qv_on || ex.bed_on;
-    ex.set_on = ex.ask_on || ex.guard_on;
+    ex.text_on = ex.ask_on || ex.spectra_on;
+    ex.set_on = ex.text_on || ex.guard_on;
     if (ex.guard_on && !ex.ask_on) (void)ex.qv.bind();   // (the guard's check above found the entry points)
     if (ex.set_on) {
         // (sized for one k-mer per genome position; what the read errors add makes it grow)
         const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
         if (ex.qv.begin(_cFlags.qv_k, _cFlags.genome_size, cap, 0) != HYPO_OK) ex.qv_fail("the k-mer set could not be created");
         ex.qv_sink = ex.qv.sink();
+        // --qv-spectra: the set counts from its first k-mer on, and the reads reach it window by window, each once
+        if (ex.spectra_on) {
+            if (ex.spectra.enable() != HYPO_OK) ex.qv_fail("the k-mer set could not be made to count");
+            ex.qv_sink.exact = true;
+        }
     }
 }
 
@@ -692,7 +716,7 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
             writer_fatal("edit scripts");
     }
     // --qv: the draft and the polished text of every contig of the batch go to the k-mer set in one query on context 0
-    int qrc = ex.ask_on ? hypo_gpu_use_device(0) : HYPO_OK;
+    int qrc = ex.text_on ? hypo_gpu_use_device(0) : HYPO_OK;
     // --kmer-guard: the batch's records are made first, their clusters judged by the set, and every contig is written as
     // its draft with the accepted records applied
     if (ex.guard_on) {
@@ -702,24 +726,24 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
                 ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;
                 if (ex.edit_fn) vcf_write_records(vfile, *_contigs[c], recs, &rejected);
                 _contigs[c]->release_after_output();
-                return ex.ask_on ? ex.qv.push(c, draft, text) : HYPO_OK;
+                return ex.texts(c, draft, text);
             });
-        if (grc == HYPO_OK && ex.ask_on) qrc = ex.qv.flush();
+        if (grc == HYPO_OK) qrc = ex.texts_flush();
         if (grc != HYPO_OK || qrc != HYPO_OK) writer_fatal(grc != HYPO_OK ? "k-mer guard" : "k-mer set query");
         return;
     }
     for (uint32_t c = initial_cid; c < final_cid; ++c) {
-        if (ex.ask_on) {
+        if (ex.text_on) {
             const std::string text = _contigs[c]->polished_text();
             ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;      // (operator<<'s bytes)
-            if (qrc == HYPO_OK) qrc = ex.qv.push(c, _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()), text);
+            if (qrc == HYPO_OK) qrc = ex.texts(c, _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()), text);
         } else {
             ofile << *_contigs[c];
         }
         if (edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, ex.vstats);
         _contigs[c]->release_after_output();
     }
-    if (ex.ask_on && qrc == HYPO_OK) qrc = ex.qv.flush();
+    if (qrc == HYPO_OK) qrc = ex.texts_flush();
     if (qrc != HYPO_OK) writer_fatal("k-mer set query");
 }
 
@@ -727,6 +751,11 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
 void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
     start();
     if (_writer.joinable()) _writer.join();
+    // --qv-spectra: the two spectra leave the device before the set goes
+    if (ex.spectra_on) {
+        if (hypo_gpu_use_device(0) != HYPO_OK || ex.spectra.fetch(ex.qv.k(), ex.qv.n_distinct(), _cFlags.qv_reliable_min) != HYPO_OK) ex.qv_fail("hypo_gpu_kset_spectrum");
+        ex.spectra.write(out.open_spectra(_cFlags.qv_spectra_filename));
+    }
     // --qv: the table is formatted once, closed and checked like the others; the set has answered its last query
     if (ex.set_on) ex.qv.end();
     if (ex.qv_on) {
@@ -760,6 +789,9 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         if (w == RunOutputs::QV)
             std::fprintf(stdout, "[Hypo::Hypo] Info: QV %s (k = %u, %llu distinct read k-mers): draft %s, polished %s\n", _cFlags.qv_filename.c_str(), ex.qv.k(),
                          (unsigned long long)ex.qv.n_distinct(), ex.qv.draft_qv().c_str(), ex.qv.polished_qv().c_str());
+        if (w == RunOutputs::SPECTRA)
+            std::fprintf(stdout, "[Hypo::Hypo] Info: spectra %s (k = %u, reliable >= %u): completeness draft %s, polished %s\n", _cFlags.qv_spectra_filename.c_str(), ex.spectra.k(),
+                         ex.spectra.threshold(), ex.spectra.completeness(SpectraReport::DRAFT).c_str(), ex.spectra.completeness(SpectraReport::POLISHED).c_str());
         if (w == RunOutputs::BED) {
             const QvReport::TrackSums ts = ex.qv.track_sums();
             std::fprintf(stdout, "[Hypo::Hypo] Info: QV track %s (k = %u): %llu intervals covering %llu bases, %llu missing k-mers\n", _cFlags.qv_bed_filename.c_str(), ex.qv.k(),

@@ -32,6 +32,8 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     bool guard_records = false;            // new, opt-in: --guard-records (the guard decides clustered edits record by record; implies --kmer-guard)
     uint32_t guard_records_max = 8;        // new, opt-in: --guard-records-max (2..12: clusters of more records are decided whole)
     std::string qv_bed_filename;           // new, opt-in: --qv-bed <file> (where the polished text has k-mers no read contains, as BED intervals)
+    std::string qv_spectra_filename;       // new, opt-in: --qv-spectra <file> (copy-number spectrum and k-mer completeness of the draft and the polished text)
+    uint32_t qv_reliable_min = 0;          // new, opt-in: --qv-reliable-min (1..255: the least read count of a reliable k-mer; 0 = the valley of the read histogram)
     uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
 };
 

@@ -5,6 +5,7 @@
 #include <condition_variable>
 #include <dlfcn.h>
 #include <cstdio>
+#include <cstdlib>
 #include <cstring>
 #include <mutex>
 #include <thread>
@@ -211,9 +212,11 @@ double secs(std::chrono::steady_clock::time_point a) { return std::chrono::durat
 // The files through one parser thread and the pipe; consume(chunk, n, lead) on the calling thread, false (with `err` set) to stop.
 template <class Consume>
 int pump_reads(const std::vector<std::string>& files, uint32_t k, SolidBuildStats& stats, std::string& err, Consume consume) {
-    constexpr size_t kChunk = (size_t)256 << 20;
+    // HYPO_READ_CHUNK_KB: another chunk size (at least 4 KiB), so that a small read set comes in many chunks (tests/test_gpu_spectra.py)
+    size_t chunk_bytes = (size_t)256 << 20;
+    if (const char* kb = std::getenv("HYPO_READ_CHUNK_KB")) chunk_bytes = (size_t)std::max(4L, std::atol(kb)) << 10;
     int rc = SOLID_OK;
-    ChunkPipe pipe(kChunk, k);
+    ChunkPipe pipe(chunk_bytes, k);
     std::string perr;
     bool parse_ok = true;
     double parse_s = 0;
@@ -235,10 +238,11 @@ int pump_reads(const std::vector<std::string>& files, uint32_t k, SolidBuildStat
     return rc;
 }
 
-// one chunk into the second consumer
-int sink_chunk(ReadSink& sink, const char* chunk, size_t n, SolidBuildStats& stats, std::string& err) {
+// one chunk into the second consumer; lead: the bytes at its start that the chunk before it held already
+int sink_chunk(ReadSink& sink, const char* chunk, size_t n, size_t lead, SolidBuildStats& stats, std::string& err) {
+    const size_t skip = sink.exact && lead > sink.k - 1 ? lead - (sink.k - 1) : 0;
     const auto tc = std::chrono::steady_clock::now();
-    const int rc = sink.add(chunk, n);
+    const int rc = sink.add(chunk + skip, n - skip);
     stats.sink_s += secs(tc);
     if (rc == HYPO_OK) return SOLID_OK;
     err = hypo_gpu_last_error();
@@ -251,7 +255,7 @@ int stream_reads(const std::vector<std::string>& files, ReadSink& sink, SolidBui
     const auto t0 = std::chrono::steady_clock::now();
     stats = SolidBuildStats();
     if (files.empty()) { err = "no read files"; return SOLID_E_INPUT; }
-    const int rc = pump_reads(files, sink.k, stats, err, [&](const char* chunk, size_t n, size_t) { return sink_chunk(sink, chunk, n, stats, err); });
+    const int rc = pump_reads(files, sink.k, stats, err, [&](const char* chunk, size_t n, size_t lead) { return sink_chunk(sink, chunk, n, lead, stats, err); });
     stats.total_s = secs(t0);
     return rc;
 }
@@ -274,14 +278,15 @@ int build_solid_kmers(const std::vector<std::string>& files, uint32_t k, uint32_
     if (!api.bind()) { err = "the device library does not provide the k-mer counting entry points (hypo_gpu_kmer_*, ABI 9)"; return SOLID_E_DEVICE; }
     if (api.begin(k, coverage) != HYPO_OK) { err = hypo_gpu_last_error(); return SOLID_E_DEVICE; }
     struct End { KmerApi& a; ~End() { (void)a.end(); } } end_table{api};      // the table is freed on every way out
-    // (the chunks overlap by the longer of the two k-mers less one; the count table gets each from its own k - 1 bytes before the new ones)
+    // (the chunks overlap by the longer of the two k-mers less one; the count table gets each from its own k - 1 bytes before the new
+    // ones, and so does a sink that counts)
     const int rc = pump_reads(files, sink ? std::max(k, sink->k) : k, stats, err, [&](const char* chunk, size_t n, size_t lead) {
         const size_t skip = lead > k - 1 ? lead - (k - 1) : 0;
         const auto tc = std::chrono::steady_clock::now();
         const int arc = api.add(chunk + skip, n - skip);
         stats.count_s += secs(tc);
         if (arc != HYPO_OK) { err = hypo_gpu_last_error(); return (int)SOLID_E_DEVICE; }
-        return sink ? sink_chunk(*sink, chunk, n, stats, err) : (int)SOLID_OK;
+        return sink ? sink_chunk(*sink, chunk, n, lead, stats, err) : (int)SOLID_OK;
     });
     if (rc != SOLID_OK) return rc;
     auto th = std::chrono::steady_clock::now();

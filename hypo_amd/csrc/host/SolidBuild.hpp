@@ -30,7 +30,9 @@ enum { SOLID_OK = 0, SOLID_E_INPUT = 1, SOLID_E_UNDEFINED = 2, SOLID_E_DEVICE = 
 // An optional second consumer of the sequence bytes the parser produces (hypo --qv: the exact k-mer set of the reads, k-mers of
 // length k).  add(bytes, n) follows hypo_gpu_kmer_count_add's rules and returns HYPO_OK or a C-ABI error (-> SOLID_E_SINK, `err` =
 // hypo_gpu_last_error()).  Consecutive chunks overlap by at least k - 1 bytes.
-struct ReadSink { uint32_t k = 0; std::function<int(const char*, uint64_t)> add; };
+// exact: the sink counts windows, so it gets each chunk from its own k - 1 bytes before the new ones (a window in two chunks would
+// count twice); otherwise it gets the whole chunk, whose overlap may be longer when the solid k-mers are longer than its own.
+struct ReadSink { uint32_t k = 0; std::function<int(const char*, uint64_t)> add; bool exact = false; };
 
 // Counts the k-mers of `files` (FASTA / FASTQ, plain or gzip) on the calling thread's device context, picks the cut-offs, prints
 // the reference's cut-offs line and "Number of solid kmers found" line, and fills sk (words, num_solid = canonical count).

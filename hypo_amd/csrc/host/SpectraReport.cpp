@@ -1,0 +1,95 @@
+// SpectraReport.cpp — see SpectraReport.hpp.
+#include "SpectraReport.hpp"
+#include <dlfcn.h>
+#include <cstdio>
+#include "../../../include/hypo_gpu.h"
+
+namespace hypo {
+
+bool SpectraReport::bind() {
+    _enable = (decltype(_enable))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_counts_enable");
+    _mark = (decltype(_mark))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_mark");
+    _spectrum = (decltype(_spectrum))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_spectrum");
+    return _enable && _mark && _spectrum;
+}
+
+int SpectraReport::enable() {
+    for (auto& o : _off) o.assign(1, 0);
+    return _enable(N_TEXTS);
+}
+
+int SpectraReport::push(const std::string& draft, const std::string& polished) {
+    constexpr size_t kFlushAt = (size_t)512 << 20;           // text per batch of mark calls (QvReport's bound per query call)
+    _text[DRAFT] += draft; _off[DRAFT].push_back(_text[DRAFT].size());
+    _text[POLISHED] += polished; _off[POLISHED].push_back(_text[POLISHED].size());
+    return _text[DRAFT].size() + _text[POLISHED].size() >= kFlushAt ? flush() : HYPO_OK;
+}
+
+int SpectraReport::flush() {
+    for (int t = 0; t < N_TEXTS; ++t) {
+        if (_off[t].size() < 2) continue;
+        uint64_t unmarked = 0;
+        const int rc = _mark((uint32_t)t, _text[t].data(), _off[t].data(), (uint32_t)(_off[t].size() - 1), nullptr, &unmarked);
+        if (rc != HYPO_OK) return rc;
+        _asm_only[t] += unmarked;
+        _text[t].clear(); _off[t].assign(1, 0);
+    }
+    return HYPO_OK;
+}
+
+int SpectraReport::fetch(uint32_t k, uint64_t reads_distinct, uint32_t reliable_min) {
+    _k = k; _reads_distinct = reads_distinct;
+    for (int t = 0; t < N_TEXTS; ++t) {
+        std::string().swap(_text[t]);
+        _hist[t].assign((size_t)kRows * kCols, 0);
+        const int rc = _spectrum((uint32_t)t, _hist[t].data());
+        if (rc != HYPO_OK) return rc;
+    }
+    _given = reliable_min != 0;
+    _t = reliable_min;
+    if (!_given) {
+        // the valley of the read histogram: the smallest c in 2..254 at which it stops falling; 2 when it never does
+        auto h = [&](uint32_t c) { uint64_t s = 0; for (uint32_t j = 0; j < kCols; ++j) s += at(DRAFT, c, j); return s; };
+        _t = 2;
+        for (uint32_t c = 2; c < kRows - 1; ++c) if (h(c) <= h(c + 1)) { _t = c; break; }
+    }
+    return HYPO_OK;
+}
+
+void SpectraReport::sums(Text t, uint64_t& reliable, uint64_t& found) const {
+    reliable = found = 0;
+    for (uint32_t c = _t; c < kRows; ++c)
+        for (uint32_t j = 0; j < kCols; ++j) { reliable += at(t, c, j); if (j) found += at(t, c, j); }
+}
+
+std::string SpectraReport::completeness(Text t) const {
+    uint64_t reliable, found;
+    sums(t, reliable, found);
+    if (!reliable) return "NA";
+    char b[64];
+    std::snprintf(b, sizeof b, "%.6f", (double)found / (double)reliable);
+    return b;
+}
+
+void SpectraReport::write(std::ostream& os) const {
+    os << "##hypo-qv-spectra\tk=" << _k << "\treads_distinct=" << _reads_distinct << "\treliable_min=" << _t << '\t' << (_given ? "given" : "valley") << '\n';
+    os << "#text\treliable\tfound\tcompleteness\tasm_only_windows\n";
+    static const char* const name[N_TEXTS] = {"draft", "polished"};
+    for (int t = 0; t < N_TEXTS; ++t) {
+        uint64_t reliable, found;
+        sums((Text)t, reliable, found);
+        os << name[t] << '\t' << reliable << '\t' << found << '\t' << completeness((Text)t) << '\t' << _asm_only[t] << '\n';
+    }
+    os << "#multiplicity";
+    for (int t = 0; t < N_TEXTS; ++t)
+        for (uint32_t j = 0; j < kCols; ++j) os << '\t' << name[t] << "_cn" << j << (j + 1 == kCols ? "+" : "");
+    os << '\n';
+    for (uint32_t c = 1; c < kRows; ++c) {
+        os << c;
+        for (int t = 0; t < N_TEXTS; ++t)
+            for (uint32_t j = 0; j < kCols; ++j) os << '\t' << at((Text)t, c, j);
+        os << '\n';
+    }
+}
+
+}  // namespace hypo

@@ -32,7 +32,8 @@ const struct option long_options[] = {
     {"vcf", required_argument, nullptr, 1007}, {"qv", required_argument, nullptr, 1008}, {"qv-k", required_argument, nullptr, 1009},
     {"qv-mem", required_argument, nullptr, 1010}, {"kmer-guard", no_argument, nullptr, 1011},
     {"guard-records", no_argument, nullptr, 1012}, {"guard-records-max", required_argument, nullptr, 1013},
-    {"qv-bed", required_argument, nullptr, 1014}, {nullptr, 0, nullptr, 0}};
+    {"qv-bed", required_argument, nullptr, 1014}, {"qv-spectra", required_argument, nullptr, 1015},
+    {"qv-reliable-min", required_argument, nullptr, 1016}, {nullptr, 0, nullptr, 0}};
 
 // Same layout as the reference's usage() (src/main.cpp:363-430): "Usage: hypo <args>", the mandatory block, the optional
 // block, every flag as "-x, --long <type>" followed by what it does and its default.  The wording is this build's own.
@@ -74,6 +75,8 @@ void usage() {
         {"    --guard-records", "[MI355X build] Implies --kmer-guard, and decides a cluster of 2 to --guard-records-max edits record by record: of all subsets of the cluster's records the one whose text lacks the fewest k-mers of the reads is kept (among equals the one with the most records), the other records get FILTER kmer. A single bad edit then no longer costs its neighbours. Larger clusters are accepted or rejected whole, as with --kmer-guard.", "off"},
         {"    --guard-records-max <int>", "[MI355X build] Most records of a cluster --guard-records still decides one by one, 2 to 12 (a cluster of n records has 2^n subsets). Without --guard-records it has no effect.", "8"},
         {"    --qv-bed <str>", "[MI355X build] Also write where the polished text (with --kmer-guard the guarded text) still disagrees with the short reads, as a BED file: a base is covered when a k-mer that no read contains (the missing k-mers of --qv) lies over it, every maximal run of covered bases of a contig is one line, contig, start, end (0-based, end exclusive) and the number of missing k-mers inside. Per contig the fourth column adds up to polished_missing of --qv. Uses the k-mer set of --qv (--qv-k, --qv-mem) with or without --qv, --vcf and --kmer-guard; the intervals are found on the device.", "no BED"},
+        {"    --qv-spectra <str>", "[MI355X build] Also write the copy-number spectrum and the k-mer completeness of the draft and of the polished text (with --kmer-guard the guarded text) as a tab-separated file: the k-mer set of --qv also counts how often the short reads contain every k-mer, and per read multiplicity 1 to 255 the file tells how many distinct read k-mers the text contains 0, 1, 2, 3 and 4 or more times (Merqury's spectra-cn: a collapsed or duplicated stretch moves k-mers between the columns). Completeness is the share of the reliable read k-mers (seen at least --qv-reliable-min times) that the text contains; asm_only_windows are the text's k-mers no read contains, polished_missing of --qv. Uses --qv-k and --qv-mem, with or without --qv, --qv-bed, --vcf and --kmer-guard; counted and compared on the device.", "no spectra"},
+        {"    --qv-reliable-min <int>", "[MI355X build] Least number of times the short reads must contain a k-mer for it to count as reliable in the completeness of --qv-spectra, 1 to 255.", "the valley of the read k-mer histogram: the smallest multiplicity from 2 on at which it stops falling"},
         {"-h, --help", "Print the usage.", nullptr}};
     std::printf("\n Usage: hypo <args>\n\n ** Mandatory args:\n");
     for (const auto& e : mandatory) std::printf("\t%s\n\t%s\n\n", e.flag, e.what);
@@ -196,6 +199,13 @@ int main(int argc, char** argv) {
                 flags.guard_records_max = (uint32_t)v; break;
             }
             case 1014: flags.qv_bed_filename = optarg; break;
+            case 1015: flags.qv_spectra_filename = optarg; break;
+            case 1016: {
+                char* end = nullptr;
+                const long v = std::strtol(optarg, &end, 10);
+                if (end == optarg || *end || v < 1 || v > 255) { std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-reliable-min must be between 1 and 255 (the k-mer set counts up to 255) %s!\n", optarg); std::exit(1); }
+                flags.qv_reliable_min = (uint32_t)v; break;
+            }
             case 1002: {
                 flags.devices.clear();
                 for (const char* c = optarg; *c;) { flags.devices.push_back(std::atoi(c)); while (*c && *c != ',') ++c; if (*c == ',') ++c; }

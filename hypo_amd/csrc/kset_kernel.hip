@@ -17,6 +17,9 @@
 //   * kset_spans_kernel / kset_variants_kernel (below, with comments of their own): many short spans, and every subset of a few
 //     edits of many short sites, a group of 32 or 64 lanes per item; read-only probes, no LDS, no atomics.  Both are ks_group_scan
 //     with another source of bytes.
+//   * counts (hypo --qv-spectra; further down, with comments of their own): a count byte and up to four copy bytes per slot in planes
+//     beside the table, a saturating byte add that serves both, and the counted variants of the insert and rehash kernels, the mark
+//     kernel (the query body with a probe that returns the slot) and the spectrum kernel.
 // Forward progress: every probe loop runs at most `slots` steps.  A lane of the insert or rehash kernel that finds neither its key
 // nor a free slot sets the overflow flag and leaves; lanes in a long probe look at the flag every 64 steps and leave too.  The host
 // keeps the table at most half full, so the flag says "internal error", but no input can make a kernel spin.
@@ -38,16 +41,19 @@ __device__ __forceinline__ uint64_t ks_mix64(uint64_t x) {      // the 64-bit fi
 }
 __device__ __forceinline__ uint64_t ks_home(uint64_t key, uint64_t slots) { return __umul64hi(ks_mix64(key), slots); }
 
-// 1 when the key was new.  ctr[1]: the overflow flag.
-__device__ __forceinline__ uint32_t ks_insert(uint64_t* table, uint64_t slots, uint64_t key, unsigned long long* ctr) {
+// 1 when the key was new.  ctr[1]: the overflow flag.  AT (the counted kernels): *at = the key's slot, found or claimed, and
+// KSET_EMPTY for a lane that leaves without one (the overflow flag is then set).
+template <bool AT = false>
+__device__ __forceinline__ uint32_t ks_insert(uint64_t* table, uint64_t slots, uint64_t key, unsigned long long* ctr, uint64_t* at = nullptr) {
     uint64_t s = ks_home(key, slots);
+    if (AT) *at = KSET_EMPTY;
     for (uint64_t probe = 0; probe < slots; ++probe) {
         const uint64_t cur = __hip_atomic_load(table + s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (cur == key) return 0;
+        if (cur == key) { if (AT) *at = s; return 0; }
         if (cur == KSET_EMPTY) {
             const uint64_t prev = atomicCAS((unsigned long long*)(table + s), (unsigned long long)KSET_EMPTY, (unsigned long long)key);
-            if (prev == KSET_EMPTY) return 1;
-            if (prev == key) return 0;                          // lost the race to a lane with the same k-mer
+            if (prev == KSET_EMPTY) { if (AT) *at = s; return 1; }
+            if (prev == key) { if (AT) *at = s; return 0; }     // lost the race to a lane with the same k-mer
         }
         if (++s == slots) s = 0;
         if ((probe & 63) == 63 && __hip_atomic_load(ctr + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return 0;
@@ -56,6 +62,18 @@ __device__ __forceinline__ uint32_t ks_insert(uint64_t* table, uint64_t slots, u
     return 0;
 }
 
+// the key's slot, KSET_EMPTY when the set does not hold it
+__device__ __forceinline__ uint64_t ks_find(const uint64_t* __restrict__ table, uint64_t slots, uint64_t key) {
+    uint64_t s = ks_home(key, slots);
+    for (uint64_t probe = 0; probe < slots; ++probe) {
+        const uint64_t cur = table[s];
+        if (cur == key) return s;
+        if (cur == KSET_EMPTY) return KSET_EMPTY;
+        if (++s == slots) s = 0;
+    }
+    return KSET_EMPTY;
+}
+// (the same probe as a yes or no, kept as it is: the read-only kernels compile to other code when they go through ks_find)
 __device__ __forceinline__ bool ks_contains(const uint64_t* __restrict__ table, uint64_t slots, uint64_t key) {
     uint64_t s = ks_home(key, slots);
     for (uint64_t probe = 0; probe < slots; ++probe) {
@@ -79,37 +97,104 @@ __device__ __forceinline__ void ks_wave_add(unsigned long long* dst, uint32_t v)
     if ((threadIdx.x & 63) == 0 && v) atomicAdd(dst, (unsigned long long)v);
 }
 
-__global__ void __launch_bounds__(KS_THREADS) kset_insert_kernel(const uint8_t* __restrict__ bytes, uint64_t n, uint32_t k,
-                                                                  uint64_t* table, uint64_t slots, unsigned long long* ctr) {
+// Four slots' bytes share a 32-bit word of a plane (the count bytes of the reads, the copy bytes of a text): byte `slot` of `plane`
+// goes up by one and stops at 255, with a compare-and-swap on the word that holds it.  The lane loads first (relaxed, agent scope,
+// as ks_insert does): a byte that reads 255 stays 255 for good, so a hot key (poly-A, a read repeated a million times) costs no
+// atomic after its 255th occurrence.  Otherwise saturation is decided on the value the atomic returns: a swap that loses hands back
+// the word as it is now, the byte is looked at again in that word, and the sum is only ever swapped in against the word it was
+// made from, so no byte wraps and no neighbour is touched.  Lock-free: a swap fails only because another lane's went through, and a
+// word takes at most 4 * 255 increments before every byte of it is full, so the loop ends after at most 1021 rounds whatever the
+// input is.  Bounds: slot < slots, and a plane has ks_plane_words(slots) words.
+__device__ __forceinline__ void ks_byte_inc(uint32_t* plane, uint64_t slot) {
+    uint32_t* w = plane + (slot >> 2);
+    const uint32_t sh = 8u * (uint32_t)(slot & 3);
+    uint32_t cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    while (((cur >> sh) & 0xffu) != 0xffu) {
+        const uint32_t prev = atomicCAS(w, cur, cur + (1u << sh));
+        if (prev == cur) return;
+        cur = prev;
+    }
+}
+
+// The body of kset_insert_kernel, and with COUNT of kset_insert_count_kernel: the probe hands back the key's slot and the slot's
+// count byte goes up by one for every window.  A lane owns the windows that START in its stretch, so the windows of a launch are
+// disjoint and each is counted once; the pieces of a call overlap by exactly k - 1 bytes (hypo_gpu_kset_add), so no window is in two.
+template <bool COUNT>
+__device__ __forceinline__ void ks_insert_body(const uint8_t* __restrict__ bytes, uint64_t n, uint32_t k, uint64_t* table, uint64_t slots,
+                                               unsigned long long* ctr, uint32_t* counts) {
     __shared__ __attribute__((aligned(16))) uint8_t sb[KR_BLOCK_BYTES + KR_HALO];
     kmer_stage(sb, bytes, (uint64_t)blockIdx.x * KR_BLOCK_BYTES, n);
     const int s0 = threadIdx.x * KR_STRETCH;
     const int last = s0 + KR_STRETCH + (int)k - 1;              // exclusive end of the bytes this lane reads
     KmerRoll roll(k);
     uint32_t n_new = 0;
-    for (int p = s0; p < last; ++p)
-        if (roll.push(sb[p])) n_new += ks_insert(table, slots, roll.canon(), ctr);     // starts at p - k + 1 >= s0
+    for (int p = s0; p < last; ++p) {
+        if (!roll.push(sb[p])) continue;                        // (a window that ends at p starts at p - k + 1 >= s0)
+        if (COUNT) {
+            uint64_t at;
+            n_new += ks_insert<true>(table, slots, roll.canon(), ctr, &at);
+            if (at != KSET_EMPTY) ks_byte_inc(counts, at);
+        } else {
+            n_new += ks_insert(table, slots, roll.canon(), ctr);
+        }
+    }
+    ks_wave_add(ctr, n_new);
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_insert_kernel(const uint8_t* __restrict__ bytes, uint64_t n, uint32_t k,
+                                                                  uint64_t* table, uint64_t slots, unsigned long long* ctr) {
+    ks_insert_body<false>(bytes, n, k, table, slots, ctr, nullptr);
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_insert_count_kernel(const uint8_t* __restrict__ bytes, uint64_t n, uint32_t k,
+                                                                        uint64_t* table, uint64_t slots, unsigned long long* ctr,
+                                                                        uint32_t* counts) {
+    ks_insert_body<true>(bytes, n, k, table, slots, ctr, counts);
+}
+
+// COUNT: the key's count byte moves with it.  Every key of the old table is there once, so a slot of the new table is claimed by one
+// lane, which stores the slot's byte (the fresh plane is zero, and the copy bytes are still all zero when a table can grow).
+template <bool COUNT>
+__device__ __forceinline__ void ks_rehash_body(const uint64_t* __restrict__ old_table, uint64_t old_slots, uint64_t* table, uint64_t slots,
+                                               unsigned long long* ctr, const uint8_t* __restrict__ old_counts, uint8_t* counts) {
+    uint32_t n_new = 0;
+    const uint64_t stride = (uint64_t)gridDim.x * KS_THREADS;
+    for (uint64_t i = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x; i < old_slots; i += stride) {
+        const uint64_t key = old_table[i];
+        if (key == KSET_EMPTY) continue;
+        if (COUNT) {
+            uint64_t at;
+            n_new += ks_insert<true>(table, slots, key, ctr, &at);
+            if (at != KSET_EMPTY) counts[at] = old_counts[i];
+        } else {
+            n_new += ks_insert(table, slots, key, ctr);
+        }
+    }
     ks_wave_add(ctr, n_new);
 }
 
 __global__ void __launch_bounds__(KS_THREADS) kset_rehash_kernel(const uint64_t* __restrict__ old_table, uint64_t old_slots,
                                                                   uint64_t* table, uint64_t slots, unsigned long long* ctr) {
-    uint32_t n_new = 0;
-    const uint64_t stride = (uint64_t)gridDim.x * KS_THREADS;
-    for (uint64_t i = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x; i < old_slots; i += stride) {
-        const uint64_t key = old_table[i];
-        if (key != KSET_EMPTY) n_new += ks_insert(table, slots, key, ctr);
-    }
-    ks_wave_add(ctr, n_new);
+    ks_rehash_body<false>(old_table, old_slots, table, slots, ctr, nullptr, nullptr);
 }
 
-// The body of kset_query_kernel, and with TRACK of kset_track_flags_kernel (further down), which also keeps what the lane knows
-// anyway: the missing bits of the 32 windows that start in its stretch, and which of its 32 bytes begin a sequence.
-template <bool TRACK>
+__global__ void __launch_bounds__(KS_THREADS) kset_rehash_count_kernel(const uint64_t* __restrict__ old_table, uint64_t old_slots,
+                                                                        uint64_t* table, uint64_t slots, unsigned long long* ctr,
+                                                                        const uint8_t* __restrict__ old_counts, uint8_t* counts) {
+    ks_rehash_body<true>(old_table, old_slots, table, slots, ctr, old_counts, counts);
+}
+
+// The body of kset_query_kernel; as KS_TRACK of kset_track_flags_kernel (further down), which also keeps what the lane knows
+// anyway: the missing bits of the 32 windows that start in its stretch, and which of its 32 bytes begin a sequence; as KS_MARK of
+// kset_mark_kernel (hypo --qv-spectra): the probe hands back the slot, a window whose key is in the set adds one to that slot's byte
+// of `marks` (the copy bytes of one text), and the windows and misses of all sequences go to total[0] / missing[0], per wave.
+enum { KS_QUERY = 0, KS_TRACK = 1, KS_MARK = 2 };
+template <int MODE>
 __device__ __forceinline__ void ks_query_body(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n_seqs, uint64_t n,
                                               uint32_t k, const uint64_t* __restrict__ table, uint64_t slots, unsigned long long* total,
                                               unsigned long long* missing, const uint8_t* __restrict__ want, uint32_t* __restrict__ miss_bits,
-                                              uint32_t* __restrict__ begin_bits) {
+                                              uint32_t* __restrict__ begin_bits, uint32_t* marks) {
+    constexpr bool TRACK = MODE == KS_TRACK, MARK = MODE == KS_MARK;
     __shared__ __attribute__((aligned(16))) uint8_t sb[KR_BLOCK_BYTES + KR_HALO];
     const uint64_t b0 = (uint64_t)blockIdx.x * KR_BLOCK_BYTES;
     kmer_stage(sb, bytes, b0, n);
@@ -130,13 +215,21 @@ __device__ __forceinline__ void ks_query_body(const uint8_t* __restrict__ bytes,
             const uint64_t g = b0 + (uint64_t)p;
             if (g >= n) break;
             if (g == seq_end) {                                  // the next sequence starts here (g < n: there is one that holds g)
-                if (tot) { atomicAdd(total + seq, tot); if (mis) atomicAdd(missing + seq, mis); }
-                tot = mis = 0; roll.reset();
+                if (!MARK) {
+                    if (tot) { atomicAdd(total + seq, tot); if (mis) atomicAdd(missing + seq, mis); }
+                    tot = mis = 0;
+                }
+                roll.reset();
                 do { ++seq; seq_end = off[seq + 1]; } while (seq_end == g);
                 if (TRACK) { if (p < s0 + KR_STRETCH) bbits |= 1u << (p - s0); wanted = !want || want[seq]; }
             }
             if (!roll.push(sb[p])) continue;
             ++tot;
+            if (MARK) {
+                const uint64_t at = ks_find(table, slots, roll.canon());
+                if (at != KSET_EMPTY) ks_byte_inc(marks, at); else ++mis;
+                continue;
+            }
             if (!ks_contains(table, slots, roll.canon())) {
                 ++mis;
                 if (TRACK && wanted) mbits |= 1u << (p - ((int)k - 1) - s0);   // the window's start: s0 <= p - k + 1 < s0 + KR_STRETCH
@@ -148,8 +241,9 @@ __device__ __forceinline__ void ks_query_body(const uint8_t* __restrict__ bytes,
         miss_bits[w] = mbits; begin_bits[w] = bbits;
     }
     // per wave: the lanes that ended in the sequence of the wave's first lane are summed and added once, the others add their own
-    const uint32_t lead = __shfl(seq, 0);
-    const bool same = seq == lead;
+    // (MARK: one sum for all sequences, so every lane is with the first)
+    const uint32_t lead = MARK ? 0u : __shfl(seq, 0);
+    const bool same = MARK || seq == lead;
     unsigned long long t = same ? tot : 0, m = same ? mis : 0;
     for (int o = 32; o > 0; o >>= 1) { t += __shfl_xor(t, o); m += __shfl_xor(m, o); }
     if ((threadIdx.x & 63) == 0 && t) { atomicAdd(total + lead, t); if (m) atomicAdd(missing + lead, m); }
@@ -159,7 +253,42 @@ __device__ __forceinline__ void ks_query_body(const uint8_t* __restrict__ bytes,
 __global__ void __launch_bounds__(KS_THREADS) kset_query_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off,
                                                                  uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* __restrict__ table,
                                                                  uint64_t slots, unsigned long long* total, unsigned long long* missing) {
-    ks_query_body<false>(bytes, off, n_seqs, n, k, table, slots, total, missing, nullptr, nullptr, nullptr);
+    ks_query_body<KS_QUERY>(bytes, off, n_seqs, n, k, table, slots, total, missing, nullptr, nullptr, nullptr, nullptr);
+}
+
+// ---- read counts and copy numbers (hypo --qv-spectra; DESIGN.md "k-mer spectra") ------------------------------------------------------
+// Beside the table lie 1 + n_texts planes of one byte per slot, ks_plane_words(slots) 32-bit words each: plane 0 counts the
+// windows of the reads per key (kset_insert_count_kernel, moved by kset_rehash_count_kernel), plane 1 + t the windows of text t
+// (kset_mark_kernel).  Both stop at 255 (ks_byte_inc).  A key is in the table from its first window on, and that window counts:
+// a slot's count byte is 0 exactly when the slot is free, so kset_spectrum_kernel reads the two planes and never the keys.
+//   * kset_spectrum_kernel: grid-stride over the words of the count plane; every workgroup keeps the 256 x 5 bins (count, copy
+//     number capped at 4) as 32-bit counters in LDS and adds the bins it used to hist[] with 64-bit adds.  Integers only: the
+//     result does not depend on the order.  A workgroup sees at most 4 * ceil(words / lanes of the grid) slots, below 2^32 for any
+//     table that fits a device.  Bounds: words below n_words of both planes, bins below KSET_HIST_BINS (a byte times 5 + at most 4).
+__global__ void __launch_bounds__(KS_THREADS) kset_mark_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n_seqs,
+                                                                uint64_t n, uint32_t k, const uint64_t* __restrict__ table, uint64_t slots,
+                                                                uint32_t* marks, unsigned long long* sums) {
+    ks_query_body<KS_MARK>(bytes, off, n_seqs, n, k, table, slots, sums, sums + 1, nullptr, nullptr, nullptr, marks);
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_spectrum_kernel(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ copies,
+                                                                    uint64_t n_words, unsigned long long* hist) {
+    __shared__ uint32_t bins[KSET_HIST_BINS];
+    for (uint32_t b = threadIdx.x; b < KSET_HIST_BINS; b += KS_THREADS) bins[b] = 0;
+    __syncthreads();
+    const uint64_t stride = (uint64_t)gridDim.x * KS_THREADS;
+    for (uint64_t w = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x; w < n_words; w += stride) {
+        const uint32_t c4 = counts[w];
+        if (!c4) continue;                                      // four free slots
+        const uint32_t m4 = copies[w];
+        for (uint32_t j = 0; j < 32; j += 8) {
+            const uint32_t c = (c4 >> j) & 0xffu, m = (m4 >> j) & 0xffu;
+            if (c) atomicAdd(&bins[c * KSET_HIST_COLS + (m < KSET_HIST_COLS - 1 ? m : KSET_HIST_COLS - 1)], 1u);
+        }
+    }
+    __syncthreads();
+    for (uint32_t b = threadIdx.x; b < KSET_HIST_BINS; b += KS_THREADS)
+        if (bins[b]) atomicAdd(hist + b, (unsigned long long)bins[b]);
 }
 
 // ---- where the missing windows are (hypo --qv-bed; DESIGN.md "k-mer QV track") -------------------------------------------------------
@@ -193,7 +322,7 @@ __global__ void __launch_bounds__(KS_THREADS) kset_track_flags_kernel(const uint
                                                                        uint64_t slots, unsigned long long* total, unsigned long long* missing,
                                                                        const uint8_t* __restrict__ want, uint32_t* __restrict__ miss_bits,
                                                                        uint32_t* __restrict__ begin_bits) {
-    ks_query_body<true>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits);
+    ks_query_body<KS_TRACK>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits, nullptr);
 }
 
 // the start and end bits of a word from the missing bits of the word before it and its own, and its begin bits
@@ -535,6 +664,42 @@ hipError_t kset_rehash_run(const uint64_t* old_table, uint64_t old_slots, uint64
     uint64_t blocks = (old_slots + KS_THREADS - 1) / KS_THREADS;
     if (blocks > 16384) blocks = 16384;
     kset_rehash_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(old_table, old_slots, table, slots, ctr);
+    return hipGetLastError();
+}
+
+uint64_t ks_plane_words(uint64_t slots) { return ((slots + 255) / 256) * 64; }
+
+hipError_t kset_insert_count_run(const uint8_t* bytes, uint64_t n, uint32_t k, uint64_t* table, uint64_t slots, unsigned long long* ctr,
+                                 uint32_t* planes, hipStream_t st) {
+    if (!n) return hipSuccess;
+    const uint64_t blocks = (n + KR_BLOCK_BYTES - 1) / KR_BLOCK_BYTES;
+    kset_insert_count_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, n, k, table, slots, ctr, planes);
+    return hipGetLastError();
+}
+
+hipError_t kset_rehash_count_run(const uint64_t* old_table, uint64_t old_slots, const uint32_t* old_planes, uint64_t* table, uint64_t slots,
+                                 uint32_t* planes, unsigned long long* ctr, hipStream_t st) {
+    if (!old_slots) return hipSuccess;
+    uint64_t blocks = (old_slots + KS_THREADS - 1) / KS_THREADS;
+    if (blocks > 16384) blocks = 16384;
+    kset_rehash_count_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(old_table, old_slots, table, slots, ctr, (const uint8_t*)old_planes,
+                                                                                  (uint8_t*)planes);
+    return hipGetLastError();
+}
+
+hipError_t kset_mark_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table, uint64_t slots,
+                         uint32_t* planes, uint32_t text, unsigned long long* sums, hipStream_t st) {
+    if (!n || !n_seqs) return hipSuccess;
+    const uint64_t blocks = (n + KR_BLOCK_BYTES - 1) / KR_BLOCK_BYTES;
+    kset_mark_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, planes + (1 + (uint64_t)text) * ks_plane_words(slots), sums);
+    return hipGetLastError();
+}
+
+hipError_t kset_spectrum_run(const uint32_t* planes, uint64_t slots, uint32_t text, unsigned long long* hist, hipStream_t st) {
+    const uint64_t n_words = ks_plane_words(slots);
+    uint64_t blocks = (n_words + KS_THREADS - 1) / KS_THREADS;
+    if (blocks > 4096) blocks = 4096;
+    kset_spectrum_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(planes, planes + (1 + (uint64_t)text) * n_words, n_words, hist);
     return hipGetLastError();
 }
 

@@ -19,6 +19,24 @@ constexpr uint64_t KSET_MIN_SLOTS = 1024;
 hipError_t kset_insert_run(const uint8_t* bytes, uint64_t n, uint32_t k, uint64_t* table, uint64_t slots, unsigned long long* ctr, hipStream_t st);
 // every key of `old_table` into `table` (which must not hold any of them yet); ctr[0] += keys moved
 hipError_t kset_rehash_run(const uint64_t* old_table, uint64_t old_slots, uint64_t* table, uint64_t slots, unsigned long long* ctr, hipStream_t st);
+// Read counts and copy numbers (hypo --qv-spectra; DESIGN.md "k-mer spectra").  planes: (1 + n_texts) * ks_plane_words(slots) 32-bit
+// words beside a table of `slots` slots, zero when fresh; byte s of plane 0 is the count of the key in slot s (the windows of the
+// reads, stopping at 255), byte s of plane 1 + t the windows of text t (likewise).  A plane is padded to whole 256-slot blocks.
+constexpr uint32_t KSET_MAX_TEXTS = 4;
+constexpr uint32_t KSET_HIST_COLS = 5, KSET_HIST_BINS = 256 * KSET_HIST_COLS;      // hist[count * 5 + min(copy number, 4)]
+uint64_t ks_plane_words(uint64_t slots);
+// kset_insert_run, and every window adds one to its key's count byte: a window handed in twice is counted twice
+hipError_t kset_insert_count_run(const uint8_t* bytes, uint64_t n, uint32_t k, uint64_t* table, uint64_t slots, unsigned long long* ctr,
+                                 uint32_t* planes, hipStream_t st);
+// kset_rehash_run, and every key's count byte goes with it (the copy bytes must still be zero: they stay behind)
+hipError_t kset_rehash_count_run(const uint64_t* old_table, uint64_t old_slots, const uint32_t* old_planes, uint64_t* table, uint64_t slots,
+                                 uint32_t* planes, unsigned long long* ctr, hipStream_t st);
+// the sequences of kset_query_run: a window whose key is in the table adds one to the key's byte of text `text`; sums[0] += all
+// windows, sums[1] += those whose key is not in the table (zeroed by the caller)
+hipError_t kset_mark_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table, uint64_t slots,
+                         uint32_t* planes, uint32_t text, unsigned long long* sums, hipStream_t st);
+// hist[c * 5 + j] += the keys with count byte c and min(copy byte of `text`, 4) == j; KSET_HIST_BINS values, zeroed by the caller
+hipError_t kset_spectrum_run(const uint32_t* planes, uint64_t slots, uint32_t text, unsigned long long* hist, hipStream_t st);
 // n_seqs byte strings back to back in bytes[0, off[n_seqs]) (off[0] = 0): total[s] += length-k windows of sequence s made of
 // ACGTacgt only, missing[s] += those whose canonical k-mer is not in the table.  total / missing must be zeroed by the caller.
 hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table,

@@ -467,6 +467,31 @@ int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n
     uint64_t* total, uint64_t* missing, uint64_t* iv_off /* n_seqs + 1 */,
     uint64_t* iv_start, uint64_t* iv_end, uint64_t* iv_missing, uint64_t iv_cap);
 
+/* Read k-mer counts and copy numbers on the set (hypo --qv-spectra; DESIGN.md "k-mer spectra").  Additive to ABI 11: callers bind
+ * the three by name.  Presence, and with it every answer of the query entry points above, is what it is without them.
+ *  - hypo_gpu_kset_counts_enable(n_texts), n_texts in 1..HYPO_KSET_MAX_TEXTS: after hypo_gpu_kset_begin, while the set is empty.
+ *    Every slot gets one count byte and n_texts copy bytes; max_bytes of _begin now caps 9 + n_texts bytes a slot (the empty table
+ *    is replaced, by a smaller one when the cap asks for it), and hypo_gpu_kset_size reports all resident bytes.  From here on
+ *    hypo_gpu_kset_add also counts: every length-k window of the bytes adds 1 to the count of its canonical k-mer, which stops at
+ *    255.  A window handed in by two calls is counted twice, so consecutive chunks of one stream of reads must overlap by EXACTLY
+ *    k - 1 bytes.  Growth keeps the counts; a call refused with HYPO_E_CAPACITY leaves keys and counts as they were.
+ *  - hypo_gpu_kset_mark(text, bytes, off, n_seqs, n_windows, n_unmarked), text < n_texts: the sequences and the byte rules of
+ *    hypo_gpu_kset_query.  Every window whose k-mer is in the set adds 1 to that k-mer's copy byte of `text`, which stops at 255;
+ *    the other windows are counted in *n_unmarked (it equals the sum of hypo_gpu_kset_query's missing[]), all windows in
+ *    *n_windows (either pointer may be NULL).  Calls add up.  An accepted call closes the set: hypo_gpu_kset_add answers
+ *    HYPO_E_INVALID from then on.
+ *  - hypo_gpu_kset_spectrum(text, hist): hist[c * 5 + j], c = 0..255, j = 0..4, = the k-mers of the set with count c and
+ *    min(copy byte of `text`, 4) == j; HYPO_KSET_SPECTRUM_BINS values.  Row 0 is all zero, row 255 means 255 or more, column 4
+ *    means 4 or more.
+ * HYPO_E_INVALID: no set, _enable on a set that holds k-mers or counts already, n_texts out of range, _mark / _spectrum without
+ * _enable or with text >= n_texts, off[] decreasing, a NULL required pointer; a refused call changes nothing.  Synchronous, on the
+ * calling thread's context. */
+#define HYPO_KSET_MAX_TEXTS 4
+#define HYPO_KSET_SPECTRUM_BINS 1280
+int hypo_gpu_kset_counts_enable(uint32_t n_texts);
+int hypo_gpu_kset_mark(uint32_t text, const char* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t* n_windows, uint64_t* n_unmarked);
+int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist);
+
 /* Kernel timing with HIP events on the stream the kernels run on ----------------------------------
  * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each records
  * events around its kernels.  hypo_gpu_profile_read(call, ms, n) synchronises that call's last event

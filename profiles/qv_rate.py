@@ -3,9 +3,12 @@
 256 MiB calls (the file's bytes as they are: header lines end runs like any other non-base byte), then the first bytes of the
 file queried as one sequence.  Writes profiles/qv_rate.json and prints it: per set the k-mers/s inside the add calls, the
 growths and the time they took (HYPO_KSET_STATS line of the library), the query rate in bases/s, the final table size and load.
-    python profiles/qv_rate.py [--sets 5m,100m] [--k 21] [--dir /tmp/qv_rate] [--kernel-trace] [--poly]
+    python profiles/qv_rate.py [--sets 5m,100m] [--k 21] [--dir /tmp/qv_rate] [--kernel-trace] [--poly] [--counts]
 --kernel-trace: every set once more, alone, under `rocprofv3 --kernel-trace --stats`; the kernels' own totals are added.
---poly: 150 MB of poly-A and of one read repeated, against 150 MB of the 5m set (what same-slot contention costs)."""
+--poly: 150 MB of poly-A and of one read repeated, against 150 MB of the 5m set (what same-slot contention costs).
+--counts: the set of `hypo --qv-spectra`.  Every set is inserted twice in one process, without counts and then with
+hypo_gpu_kset_counts_enable(2) (same bytes, same calls), the queried bytes are also marked as text 0 (hypo_gpu_kset_mark) and the
+spectrum is fetched (hypo_gpu_kset_spectrum); writes profiles/spectra_rate.json instead."""
 import argparse
 import csv
 import glob
@@ -52,7 +55,7 @@ def insert_all(gpu, data, k):
         at += PIECE - (k - 1)
 
 
-def one(path, k, expected):
+def one(path, k, expected, counts=False):
     from hypo_amd import capi
     gpu = capi.HypoGpu(0)
     data = np.fromfile(path, dtype=np.uint8)
@@ -65,10 +68,32 @@ def one(path, k, expected):
     total, missing = gpu.kset_query([q])
     t_q = time.perf_counter() - t0
     gpu.kset_end()
-    return {"k": k, "file_GB": round(data.size / 1e9, 3), "add_calls_s": round(t_add, 4), "windows": windows,
-            "insert_kmers_per_s": round(windows / t_add), "distinct": n, "table_GiB": round(table_bytes / 2 ** 30, 3),
-            "load": round(n * 8 / table_bytes, 3), "query_bytes": len(q), "query_s": round(t_q, 4), "query_bases_per_s": round(len(q) / t_q),
-            "query_total": int(total[0]), "query_missing": int(missing[0])}
+    row = {"k": k, "file_GB": round(data.size / 1e9, 3), "add_calls_s": round(t_add, 4), "windows": windows,
+           "insert_kmers_per_s": round(windows / t_add), "distinct": n, "table_GiB": round(table_bytes / 2 ** 30, 3),
+           "load": round(n * 8 / table_bytes, 3), "query_bytes": len(q), "query_s": round(t_q, 4), "query_bases_per_s": round(len(q) / t_q),
+           "query_total": int(total[0]), "query_missing": int(missing[0])}
+    if counts:
+        # the same bytes in the same calls into a set that counts; then a mark of the queried bytes and the spectrum
+        gpu.kset_begin(k, expected)
+        gpu.kset_counts_enable(2)
+        t_cadd, _ = insert_all(gpu, data, k)
+        nc, bytes_c = gpu.kset_size()
+        assert nc == n
+        t0 = time.perf_counter()
+        n_win, n_un = gpu.kset_mark(0, [q])
+        t_m = time.perf_counter() - t0
+        assert (n_win, n_un) == (int(total[0]), int(missing[0]))
+        gpu.kset_spectrum(0)                                               # (first use of the kernel)
+        t0 = time.perf_counter()
+        hist = gpu.kset_spectrum(0)
+        t_s = time.perf_counter() - t0
+        assert int(hist.sum()) == n
+        gpu.kset_end()
+        row.update({"counts_add_calls_s": round(t_cadd, 4), "counts_insert_kmers_per_s": round(windows / t_cadd),
+                    "counts_over_plain": round(t_cadd / t_add, 3), "counts_resident_GiB": round(bytes_c / 2 ** 30, 3),
+                    "mark_s": round(t_m, 4), "mark_bases_per_s": round(len(q) / t_m), "spectrum_call_s": round(t_s, 5),
+                    "saturated_kmers": int(hist[255].sum())})
+    return row
 
 
 def poly(path, k):
@@ -103,7 +128,8 @@ def kernel_stats(args, out_dir, tag):
             name = " ".join(str(v) for v in row.values())
             calls = next((row[c] for c in row if c.lower() == "calls"), "0")
             total = next((row[c] for c in row if c.lower().startswith("totalduration")), "0")
-            for short in ("kset_insert_kernel", "kset_rehash_kernel", "kset_query_kernel"):
+            for short in ("kset_insert_kernel", "kset_rehash_kernel", "kset_query_kernel", "kset_insert_count_kernel", "kset_rehash_count_kernel",
+                          "kset_mark_kernel", "kset_spectrum_kernel"):
                 if short in name:
                     out[short] = {"calls": int(calls), "total_ms": round(float(total) / 1e6, 3)}
     return out
@@ -116,20 +142,22 @@ def main():
     ap.add_argument("--dir", default="/tmp/qv_rate")
     ap.add_argument("--kernel-trace", action="store_true")
     ap.add_argument("--poly", action="store_true")
-    ap.add_argument("--out", default=os.path.join(HERE, "qv_rate.json"))
+    ap.add_argument("--counts", action="store_true")
+    ap.add_argument("--out")
     ap.add_argument("--one", help=argparse.SUPPRESS)
     ap.add_argument("--poly-one", help=argparse.SUPPRESS)
     a = ap.parse_args()
     if a.one:
         path, size = a.one.rsplit(":", 1)
-        print(json.dumps(one(path, a.k, int(size))))
+        print(json.dumps(one(path, a.k, int(size), a.counts)))
         return
     if a.poly_one:
         print(json.dumps(poly(a.poly_one, a.k)))
         return
     os.makedirs(a.dir, exist_ok=True)
+    a.out = a.out or os.path.join(HERE, "spectra_rate.json" if a.counts else "qv_rate.json")
     env = dict(os.environ, HYPO_KSET_STATS="1")
-    res = {"what": f"exact {a.k}-mer set from 30x 150-bp reads (hypo --qv)", "sets": {}}
+    res = {"what": f"exact {a.k}-mer set from 30x 150-bp reads (hypo --qv" + ("-spectra: without and with counts)" if a.counts else ")"), "sets": {}}
 
     def child(args):
         p = subprocess.run([sys.executable, os.path.abspath(__file__), "--k", str(a.k)] + args, capture_output=True, text=True, timeout=1800, env=env)
@@ -138,11 +166,13 @@ def main():
         return json.loads(p.stdout.strip().splitlines()[-1]), p.stderr
     for size in a.sets.split(","):
         path = reads_for(a.dir, size)
-        args = ["--one", f"{path}:{parse_size(size)}"]
+        args = ["--one", f"{path}:{parse_size(size)}"] + (["--counts"] if a.counts else [])
         row, err = child(args)
         m = re.findall(r"\[kset\] k \d+, \d+ keys, \d+ slots \(peak (\d+)\), (\d+) growths in ([0-9.]+) s", err)
-        if m:
-            row["peak_table_GiB"], row["growths"], row["growth_s"] = round(int(m[-1][0]) * 8 / 2 ** 30, 3), int(m[-1][1]), float(m[-1][2])
+        if m:                                            # (--counts: the first line is the set without counts, the second the one with)
+            row["peak_table_GiB"], row["growths"], row["growth_s"] = round(int(m[0][0]) * 8 / 2 ** 30, 3), int(m[0][1]), float(m[0][2])
+            if a.counts and len(m) > 1:
+                row["counts_growths"], row["counts_growth_s"] = int(m[1][1]), float(m[1][2])
         if a.kernel_trace:
             row["kernels"] = kernel_stats(["--k", str(a.k)] + args, a.dir, size)
         res["sets"][size] = row
