@@ -31,7 +31,7 @@ EXPORTS = [
     "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts",
     "hypo_gpu_kset_begin", "hypo_gpu_kset_add", "hypo_gpu_kset_size", "hypo_gpu_kset_query", "hypo_gpu_kset_end",
     "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants", "hypo_gpu_kset_query_track",
-    "hypo_gpu_kset_counts_enable", "hypo_gpu_kset_mark", "hypo_gpu_kset_spectrum",
+    "hypo_gpu_kset_counts_enable", "hypo_gpu_kset_mark", "hypo_gpu_kset_spectrum", "hypo_gpu_kset_min_count",
 ]
 KSET_SPAN_PIECE = 2048        # windows per piece of a long span (kset_kernel.hpp)
 KSET_MAX_EDITS = 12           # edits of a site of hypo_gpu_kset_query_variants (HYPO_KSET_MAX_EDITS)
@@ -406,6 +406,14 @@ class HypoGpu:
         rc, hist = self.kset_spectrum_rc(text)
         self._check(rc)
         return hist
+
+    def kset_min_count_rc(self, t: int) -> int:
+        return int(self.lib.hypo_gpu_kset_min_count(C.c_uint32(t)))
+
+    def kset_min_count(self, t: int):
+        """on a set that counts: from the next call on the four queries answer against the k-mers the reads have at least t times
+        (1..255; 1 = the set itself)"""
+        self._check(self.kset_min_count_rc(t))
 
     def kset_end(self):
         self._check(self.lib.hypo_gpu_kset_end())

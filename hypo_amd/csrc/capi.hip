@@ -166,6 +166,7 @@ struct Ctx {
         uint64_t* table = nullptr; uint64_t slots = 0, max_slots = 0, count = 0; uint32_t k = 0; DevBuf in, off, res, ctr;
         uint32_t growths = 0; double grow_s = 0; uint64_t peak_slots = 0;
         uint64_t max_bytes = 0; uint32_t n_texts = 0; uint32_t* planes = nullptr; bool marked = false;
+        uint32_t min_count = 1;                            // hypo_gpu_kset_min_count: the queries answer against the keys counted at least this often
         uint64_t plane_bytes(uint64_t n_slots) const { return n_texts ? (1 + (uint64_t)n_texts) * hypo::ks_plane_words(n_slots) * 4 : 0; }
         double slot_bytes() const { return n_texts ? 9.0 + n_texts : 8.0; }      // what max_bytes caps, per slot
     };
@@ -1256,7 +1257,7 @@ int hypo_gpu_kset_begin(uint32_t k, uint64_t expected_distinct, uint64_t max_byt
     if (ks.table) { (void)hipFree(ks.table); ks.table = nullptr; }
     if (ks.planes) { (void)hipFree(ks.planes); ks.planes = nullptr; }
     ks.k = 0; ks.slots = 0; ks.count = 0; ks.growths = 0; ks.grow_s = 0; ks.peak_slots = 0;
-    ks.n_texts = 0; ks.marked = false;
+    ks.n_texts = 0; ks.marked = false; ks.min_count = 1;
     ks.max_slots = max_slots; ks.max_bytes = max_bytes;
     HIP_TRY(ks.ctr.alloc(16));
     uint64_t slots = ks_slots_for(expected_distinct < ((uint64_t)1 << 62) ? expected_distinct : ((uint64_t)1 << 62));
@@ -1329,7 +1330,7 @@ int hypo_gpu_kset_query(const char* bytes, const uint64_t* off, uint32_t n_seqs,
     if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
     hipStream_t st = g_ctx.stream;
     const int rc = ks_query_seqs(ks, bytes + off[0], rel, n_seqs, rel.size() * 8, total, missing, [&](char* d_off, unsigned long long* d_tot, unsigned long long* d_mis) {
-        return hypo::kset_query_run((const uint8_t*)ks.in.p, (const uint64_t*)d_off, n_seqs, rel[n_seqs], ks.k, ks.table, ks.slots, d_tot, d_mis, st);
+        return hypo::kset_query_run((const uint8_t*)ks.in.p, (const uint64_t*)d_off, n_seqs, rel[n_seqs], ks.k, ks.table, ks.slots, d_tot, d_mis, ks.planes, ks.min_count, st);
     });
     if (rc != HYPO_OK) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -1362,7 +1363,7 @@ int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n
         if (want) { const hipError_t e = hipMemcpyAsync(d + at_want, want, n_seqs, hipMemcpyHostToDevice, st); if (e != hipSuccess) return e; }
         return hypo::kset_track_count_run((const uint8_t*)ks.in.p, (const uint64_t*)d, n_seqs, n, ks.k, ks.table, ks.slots, d_tot, d_mis,
                                           want ? (const uint8_t*)(d + at_want) : nullptr, (uint32_t*)(d + at_miss), (uint32_t*)(d + at_begin),
-                                          (uint64_t*)(d + at_sums), (uint64_t*)(d + at_pre), st);
+                                          (uint64_t*)(d + at_sums), (uint64_t*)(d + at_pre), ks.planes, ks.min_count, st);
     });
     if (rc != HYPO_OK) return rc;
     char* const d_off = (char*)ks.off.p;
@@ -1423,7 +1424,7 @@ int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_
     HIP_TRY(h2d(ks.off.p, item_lo.data(), (size_t)n_items * 8, st));
     HIP_TRY(h2d((char*)ks.off.p + lo_bytes, item_len.data(), (size_t)n_items * 4, st));
     HIP_TRY(hypo::kset_spans_run((const uint8_t*)ks.in.p, (const uint64_t*)ks.off.p, (const uint32_t*)((const char*)ks.off.p + lo_bytes), (uint32_t)n_items, k,
-                                 ks.table, ks.slots, (uint2*)ks.res.p, ks_group(), st));
+                                 ks.table, ks.slots, (uint2*)ks.res.p, ks_group(), ks.planes, ks.min_count, st));
     std::vector<uint2> res((size_t)n_items);
     HIP_TRY(d2h(res.data(), ks.res.p, (size_t)n_items * 8, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1519,7 +1520,7 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
                                     (const uint4*)(d_off + o_items), (uint32_t)n_items, (const uint32_t*)(d_off + o_sitem), (const uint32_t*)(d_off + o_voff), n_sites, k,
                                     ks.table, ks.slots, (uint2*)(d_res + r_item), (uint32_t*)(d_res + r_mask), (unsigned long long*)(d_res + r_bt),
                                     (unsigned long long*)(d_res + r_bm), want_vars ? (unsigned long long*)(d_res + r_vt) : nullptr,
-                                    want_vars ? (unsigned long long*)(d_res + r_vm) : nullptr, ks_group(), st));
+                                    want_vars ? (unsigned long long*)(d_res + r_vm) : nullptr, ks_group(), ks.planes, ks.min_count, st));
     HIP_TRY(d2h(best_mask, d_res + r_mask, (size_t)n_sites * 4, st));
     HIP_TRY(d2h(best_total, d_res + r_bt, (size_t)n_sites * 8, st));
     HIP_TRY(d2h(best_missing, d_res + r_bm, (size_t)n_sites * 8, st));
@@ -1592,6 +1593,15 @@ int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist) {
     HIP_TRY(hypo::kset_spectrum_run(ks.planes, ks.slots, text, (unsigned long long*)ks.res.p, st));
     HIP_TRY(hipMemcpyAsync(hist, ks.res.p, kBytes, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
+    return HYPO_OK;
+}
+
+// ---- a least count for the queries (hypo --qv-min-count) --------------------------------------------------------------------------
+int hypo_gpu_kset_min_count(uint32_t t) {
+    HYPO_KSET_ENTRY();
+    if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)");
+    if (t < 1 || t > 255) return fail(HYPO_E_INVALID, "t = %u out of range 1..255 (the k-mer set counts up to 255)", t);
+    ks.min_count = t;                                                  // read when a query launches: the counts are those of that moment
     return HYPO_OK;
 }
 

@@ -24,6 +24,8 @@ struct Extras {
     KmerGuard guard;
     SpectraReport spectra;
     bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false;
+    uint32_t min_given = 1;                                // --qv-min-count: 1 = off, 0 = the valley
+    bool min_on() const { return min_given != 1; }
     bool ask_on = false;                                   // --qv or --qv-bed: every contig's texts are put to the set
     bool text_on = false;                                  // ... or --qv-spectra: every contig's texts are needed as strings
     bool set_on = false;                                   // ... or --kmer-guard: the set is built
@@ -46,6 +48,12 @@ struct Extras {
     }
     void qv_reads_done(const SolidBuildStats& st, bool shared_pass) {
         if (qv.read_size() != HYPO_OK) qv_fail("hypo_gpu_kset_size");
+        // --qv-min-count: the last read is in and nothing has been asked yet; from here on the set answers for the reliable k-mers
+        if (min_on()) {
+            if (qv.set_min_count(min_given) != HYPO_OK) qv_fail("hypo_gpu_kset_spectrum / hypo_gpu_kset_min_count");
+            std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer min count (k = %u): >= %u (%s), %llu of %llu read k-mers reliable\n", qv.k(), qv.min_count(),
+                         min_given ? "given" : "valley", (unsigned long long)qv.n_reliable(), (unsigned long long)qv.n_distinct());
+        }
         std::fprintf(stderr, "[Hypo::QV] Info: k-mer set of the reads (k = %u): %llu distinct k-mers, %.3f s in the insert calls of %.3f GB%s\n", qv.k(),
                      (unsigned long long)qv.n_distinct(), st.sink_s, st.seq_bytes / 1e9, shared_pass ? " (the parse pass of the solid k-mers)" : " (reads parsed for the QV alone)");
     }
@@ -151,6 +159,13 @@ void Hypo::polish() {
 
 // ---- once per run, before the batches ----------------------------------------------------------------------------------------
 void Hypo::bind_extras(Extras& ex) {
+    // --qv-min-count: counts on the set and the threshold of its queries, bound by name and only under the flag (1 is the run
+    // without it).  Checked first: its error names them.
+    ex.min_given = _cFlags.qv_min_count;
+    if (ex.min_on() && !(ex.qv.bind_min_count() && ex.qv.bind())) {
+        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv-min-count needs hypo_gpu_kset_counts_enable, hypo_gpu_kset_spectrum and hypo_gpu_kset_min_count, and hypo_gpu_kset_begin / _add / _size / _end, which the device library does not provide\n");
+        std::exit(1);
+    }
     // --qv-spectra: counts on the set, bound by name and only under the flag.  Checked first: its error names them.
     ex.spectra_on = !_cFlags.qv_spectra_filename.empty();
     if (ex.spectra_on && !(ex.spectra.bind() && ex.qv.bind())) {
@@ -205,6 +220,11 @@ void Hypo::bind_extras(Extras& ex) {
         // --qv-spectra: the set counts from its first k-mer on, and the reads reach it window by window, each once
         if (ex.spectra_on) {
             if (ex.spectra.enable() != HYPO_OK) ex.qv_fail("the k-mer set could not be made to count");
+            ex.qv_sink.exact = true;
+        }
+        // --qv-min-count: likewise, with one plane less when no text is going to be marked
+        if (ex.min_on()) {
+            if (!ex.spectra_on && ex.qv.enable_counts() != HYPO_OK) ex.qv_fail("the k-mer set could not be made to count");
             ex.qv_sink.exact = true;
         }
     }

@@ -1,5 +1,6 @@
 // QvReport.cpp — see QvReport.hpp.
 #include "QvReport.hpp"
+#include "SpectraReport.hpp"
 #include <dlfcn.h>
 #include <cmath>
 #include <cstdio>
@@ -27,6 +28,29 @@ bool QvReport::bind() {
 bool QvReport::bind_track() {
     _track = (decltype(_track))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_query_track");
     return _track != nullptr;
+}
+
+bool QvReport::bind_min_count() {
+    _counts_enable = (decltype(_counts_enable))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_counts_enable");
+    _spectrum = (decltype(_spectrum))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_spectrum");
+    _set_min_count = (decltype(_set_min_count))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_min_count");
+    return _counts_enable && _spectrum && _set_min_count;
+}
+
+int QvReport::enable_counts() { return _counts_enable(1); }
+
+int QvReport::set_min_count(uint32_t given) {
+    // no text has been marked yet: every key of the set is in column 0 of its count's row
+    std::vector<uint64_t> hist((size_t)SpectraReport::kRows * SpectraReport::kCols);
+    int rc = _spectrum(0, hist.data());
+    if (rc != HYPO_OK) return rc;
+    uint64_t h[SpectraReport::kRows];
+    for (uint32_t c = 0; c < SpectraReport::kRows; ++c) { h[c] = 0; for (uint32_t j = 0; j < SpectraReport::kCols; ++j) h[c] += hist[(size_t)c * SpectraReport::kCols + j]; }
+    const uint32_t t = given ? given : SpectraReport::valley(h);
+    if ((rc = _set_min_count(t)) != HYPO_OK) return rc;
+    _min_count = t; _n_reliable = 0;
+    for (uint32_t c = t; c < SpectraReport::kRows; ++c) _n_reliable += h[c];
+    return HYPO_OK;
 }
 
 int QvReport::begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes, size_t n_contigs) {

@@ -23,6 +23,15 @@ public:
     bool bind_track();
     // the set on the calling thread's context; max_bytes 0 = the library's default cap
     int begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes, size_t n_contigs);
+    // --qv-min-count: binds hypo_gpu_kset_counts_enable, _spectrum and _min_count by name (false: the library lacks one).  The
+    // set counts (enable_counts right after begin, unless --qv-spectra has enabled its counts already), and after the reads
+    // set_min_count reads the histogram of the read counts, takes t = `given` or, for 0, its valley, and from then on every query of
+    // the set, the guard's included, is answered against the k-mers seen at least t times (DESIGN.md "k-mer min count").
+    bool bind_min_count();
+    int enable_counts();
+    int set_min_count(uint32_t given);
+    uint32_t min_count() const { return _min_count; }
+    uint64_t n_reliable() const { return _n_reliable; }      // distinct read k-mers seen at least min_count() times
     ReadSink sink();
     int read_size();                                         // after the reads: fetches the number of distinct k-mers
     uint64_t n_distinct() const { return _n_distinct; }
@@ -50,6 +59,11 @@ private:
     int (*_track)(const char*, const uint64_t*, uint32_t, const uint8_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t) = nullptr;
     struct Interval { uint64_t start, end, missing; };
     std::vector<std::vector<Interval>> _intervals;           // per contig, of its polished text
+    int (*_counts_enable)(uint32_t) = nullptr;
+    int (*_spectrum)(uint32_t, uint64_t*) = nullptr;
+    int (*_set_min_count)(uint32_t) = nullptr;
+    uint32_t _min_count = 1;
+    uint64_t _n_reliable = 0;
     bool _open = false;
     uint32_t _k = 0;
     uint64_t _n_distinct = 0;

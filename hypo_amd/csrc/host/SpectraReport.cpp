@@ -48,12 +48,16 @@ int SpectraReport::fetch(uint32_t k, uint64_t reads_distinct, uint32_t reliable_
     _given = reliable_min != 0;
     _t = reliable_min;
     if (!_given) {
-        // the valley of the read histogram: the smallest c in 2..254 at which it stops falling; 2 when it never does
-        auto h = [&](uint32_t c) { uint64_t s = 0; for (uint32_t j = 0; j < kCols; ++j) s += at(DRAFT, c, j); return s; };
-        _t = 2;
-        for (uint32_t c = 2; c < kRows - 1; ++c) if (h(c) <= h(c + 1)) { _t = c; break; }
+        uint64_t h[kRows];
+        for (uint32_t c = 0; c < kRows; ++c) { h[c] = 0; for (uint32_t j = 0; j < kCols; ++j) h[c] += at(DRAFT, c, j); }
+        _t = valley(h);
     }
     return HYPO_OK;
+}
+
+uint32_t SpectraReport::valley(const uint64_t* h) {
+    for (uint32_t c = 2; c < kRows - 1; ++c) if (h[c] <= h[c + 1]) return c;
+    return 2;
 }
 
 void SpectraReport::sums(Text t, uint64_t& reliable, uint64_t& found) const {

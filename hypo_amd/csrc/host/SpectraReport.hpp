@@ -15,6 +15,9 @@ class SpectraReport {
 public:
     static constexpr uint32_t kRows = 256, kCols = 5;        // hist[c * 5 + min(copy number, 4)], c = 0..255
     enum Text { DRAFT = 0, POLISHED = 1, N_TEXTS = 2 };
+    // the valley of a read histogram h[0 .. kRows): the smallest c in 2..254 at which it stops falling, h[c] <= h[c + 1]; 2 when it
+    // never does (the default of --qv-reliable-min, and `valley` of --qv-min-count)
+    static uint32_t valley(const uint64_t* h);
     // binds the three entry points by name: only runs with --qv-spectra need them (false: the device library lacks one)
     bool bind();
     int enable();                                            // the set of the calling thread's context counts from here on

@@ -20,6 +20,9 @@
 //   * counts (hypo --qv-spectra; further down, with comments of their own): a count byte and up to four copy bytes per slot in planes
 //     beside the table, a saturating byte add that serves both, and the counted variants of the insert and rehash kernels, the mark
 //     kernel (the query body with a probe that returns the slot) and the spectrum kernel.
+//   * a least count (hypo --qv-min-count; further down, with comments of their own): the query, track-flags, spans and variants
+//     kernels once more as kset_*_min_kernel, whose probe also loads the hit slot's count byte and answers "seen at least t times".
+//     They are instances of the same bodies with a compile-time switch; the kernels above do not know of t.
 // Forward progress: every probe loop runs at most `slots` steps.  A lane of the insert or rehash kernel that finds neither its key
 // nor a free slot sets the overflow flag and leaves; lanes in a long probe look at the flag every 64 steps and leave too.  The host
 // keeps the table at most half full, so the flag says "internal error", but no input can make a kernel spin.
@@ -79,6 +82,21 @@ __device__ __forceinline__ bool ks_contains(const uint64_t* __restrict__ table, 
     for (uint64_t probe = 0; probe < slots; ++probe) {
         const uint64_t cur = table[s];
         if (cur == key) return true;
+        if (cur == KSET_EMPTY) return false;
+        if (++s == slots) s = 0;
+    }
+    return false;
+}
+
+// ks_contains against R_t = { keys whose count byte is at least t } (hypo --qv-min-count): the same walk, and a hit loads the slot's byte
+// of the count plane (byte s of `counts` belongs to slot s; a key's byte is at least 1 from its first window on).  One more
+// dependent load per hit, none per miss.  Bounds: s < slots, and the plane has ks_plane_words(slots) * 4 >= slots bytes.
+__device__ __forceinline__ bool ks_contains_min(const uint64_t* __restrict__ table, uint64_t slots, const uint8_t* __restrict__ counts, uint64_t key,
+                                                uint32_t t) {
+    uint64_t s = ks_home(key, slots);
+    for (uint64_t probe = 0; probe < slots; ++probe) {
+        const uint64_t cur = table[s];
+        if (cur == key) return counts[s] >= t;
         if (cur == KSET_EMPTY) return false;
         if (++s == slots) s = 0;
     }
@@ -187,14 +205,17 @@ __global__ void __launch_bounds__(KS_THREADS) kset_rehash_count_kernel(const uin
 // The body of kset_query_kernel; as KS_TRACK of kset_track_flags_kernel (further down), which also keeps what the lane knows
 // anyway: the missing bits of the 32 windows that start in its stretch, and which of its 32 bytes begin a sequence; as KS_MARK of
 // kset_mark_kernel (hypo --qv-spectra): the probe hands back the slot, a window whose key is in the set adds one to that slot's byte
-// of `marks` (the copy bytes of one text), and the windows and misses of all sequences go to total[0] / missing[0], per wave.
-enum { KS_QUERY = 0, KS_TRACK = 1, KS_MARK = 2 };
+// of `marks` (the copy bytes of one text), and the windows and misses of all sequences go to total[0] / missing[0], per wave;
+// as KS_QUERY_MIN / KS_TRACK_MIN (hypo --qv-min-count) of kset_query_min_kernel / kset_track_flags_min_kernel: KS_QUERY / KS_TRACK
+// with ks_contains_min as the probe, so a window whose key the reads have fewer than min_count times is missing.
+enum { KS_QUERY = 0, KS_TRACK = 1, KS_MARK = 2, KS_QUERY_MIN = 3, KS_TRACK_MIN = 4 };
 template <int MODE>
 __device__ __forceinline__ void ks_query_body(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off, uint32_t n_seqs, uint64_t n,
                                               uint32_t k, const uint64_t* __restrict__ table, uint64_t slots, unsigned long long* total,
                                               unsigned long long* missing, const uint8_t* __restrict__ want, uint32_t* __restrict__ miss_bits,
-                                              uint32_t* __restrict__ begin_bits, uint32_t* marks) {
-    constexpr bool TRACK = MODE == KS_TRACK, MARK = MODE == KS_MARK;
+                                              uint32_t* __restrict__ begin_bits, uint32_t* marks, const uint8_t* __restrict__ counts = nullptr,
+                                              uint32_t min_count = 1) {
+    constexpr bool TRACK = MODE == KS_TRACK || MODE == KS_TRACK_MIN, MARK = MODE == KS_MARK, MIN = MODE == KS_QUERY_MIN || MODE == KS_TRACK_MIN;
     __shared__ __attribute__((aligned(16))) uint8_t sb[KR_BLOCK_BYTES + KR_HALO];
     const uint64_t b0 = (uint64_t)blockIdx.x * KR_BLOCK_BYTES;
     kmer_stage(sb, bytes, b0, n);
@@ -230,7 +251,7 @@ __device__ __forceinline__ void ks_query_body(const uint8_t* __restrict__ bytes,
                 if (at != KSET_EMPTY) ks_byte_inc(marks, at); else ++mis;
                 continue;
             }
-            if (!ks_contains(table, slots, roll.canon())) {
+            if (MIN ? !ks_contains_min(table, slots, counts, roll.canon(), min_count) : !ks_contains(table, slots, roll.canon())) {
                 ++mis;
                 if (TRACK && wanted) mbits |= 1u << (p - ((int)k - 1) - s0);   // the window's start: s0 <= p - k + 1 < s0 + KR_STRETCH
             }
@@ -323,6 +344,27 @@ __global__ void __launch_bounds__(KS_THREADS) kset_track_flags_kernel(const uint
                                                                        const uint8_t* __restrict__ want, uint32_t* __restrict__ miss_bits,
                                                                        uint32_t* __restrict__ begin_bits) {
     ks_query_body<KS_TRACK>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits, nullptr);
+}
+
+// ---- a least count (hypo --qv-min-count; DESIGN.md "k-mer min count") ---------------------------------------------------------------
+// R_t = the keys the reads have at least t times, t = 2..255 (t = 1 is the set itself, and the host then launches the kernels
+// above).  A set that counts answers its four queries against R_t with the kernels below: the bodies above with ks_contains_min
+// as the probe, `counts` = plane 0 as bytes, `t` wave-uniform.  Everything behind the flag words of the track (count, scan, emit,
+// offsets, finish) and kset_variants_reduce_kernel take their input as it is.  Bounds: those of the kernels they restate, and the
+// count byte of a slot < slots.
+__global__ void __launch_bounds__(KS_THREADS) kset_query_min_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off,
+                                                                     uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* __restrict__ table,
+                                                                     uint64_t slots, unsigned long long* total, unsigned long long* missing,
+                                                                     const uint8_t* __restrict__ counts, uint32_t t) {
+    ks_query_body<KS_QUERY_MIN>(bytes, off, n_seqs, n, k, table, slots, total, missing, nullptr, nullptr, nullptr, nullptr, counts, t);
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_track_flags_min_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off,
+                                                                           uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* __restrict__ table,
+                                                                           uint64_t slots, unsigned long long* total, unsigned long long* missing,
+                                                                           const uint8_t* __restrict__ want, uint32_t* __restrict__ miss_bits,
+                                                                           uint32_t* __restrict__ begin_bits, const uint8_t* __restrict__ counts, uint32_t t) {
+    ks_query_body<KS_TRACK_MIN>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits, nullptr, counts, t);
 }
 
 // the start and end bits of a word from the missing bits of the word before it and its own, and its begin bits
@@ -445,9 +487,13 @@ uint32_t kset_track_blocks(uint64_t n) { return (uint32_t)(n / KR_BLOCK_BYTES + 
 
 hipError_t kset_track_count_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table, uint64_t slots,
                                 unsigned long long* total, unsigned long long* missing, const uint8_t* want, uint32_t* miss_bits, uint32_t* begin_bits,
-                                uint64_t* sums, uint64_t* pre, hipStream_t st) {
+                                uint64_t* sums, uint64_t* pre, const uint32_t* planes, uint32_t min_count, hipStream_t st) {
     const uint32_t blocks = kset_track_blocks(n);
-    kset_track_flags_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits);
+    if (min_count > 1)
+        kset_track_flags_min_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits,
+                                                                               (const uint8_t*)planes, min_count);
+    else
+        kset_track_flags_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
     kset_track_count_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(miss_bits, begin_bits, k, sums);
@@ -500,9 +546,11 @@ template <int G> __device__ __forceinline__ uint32_t ks_window_bits(uint64_t lo,
 }
 
 // The item of the calling lane's group goes through the set: `fetch(x)` is byte x < len of the item, out[item] = (windows, misses).
-template <int G, class Fetch>
+// MIN (hypo --qv-min-count): the probe is ks_contains_min with `counts` and `t`.
+template <int G, bool MIN, class Fetch>
 __device__ __forceinline__ void ks_group_scan(Fetch fetch, bool have, uint32_t len, uint32_t k, const uint64_t* __restrict__ table,
-                                              uint64_t slots, uint2* __restrict__ out, uint64_t item) {
+                                              uint64_t slots, uint2* __restrict__ out, uint64_t item, const uint8_t* __restrict__ counts = nullptr,
+                                              uint32_t t = 1) {
     static_assert(G == 32 || G == 64, "a half-wave or a wave");
     const uint32_t lane = threadIdx.x & 63, l = lane & (G - 1), half = G == 64 ? 0 : lane >> 5;
     const uint32_t n_win = len >= k ? len - k + 1 : 0;
@@ -527,7 +575,8 @@ __device__ __forceinline__ void ks_group_scan(Fetch fetch, bool have, uint32_t l
             const uint32_t h0 = ks_window_bits<G>(c0, n0, l) & kmask, h1 = ks_window_bits<G>(c1, n1, l) & kmask;
             const uint64_t fwd = (ks_spread(__brev(h1) >> (32 - k)) << 1) | ks_spread(__brev(h0) >> (32 - k));
             const uint64_t rc = (ks_spread(~h1 & kmask) << 1) | ks_spread(~h0 & kmask);
-            miss = !ks_contains(table, slots, fwd < rc ? fwd : rc);
+            const uint64_t key = fwd < rc ? fwd : rc;
+            miss = MIN ? !ks_contains_min(table, slots, counts, key, t) : !ks_contains(table, slots, key);
         }
         tot += (uint32_t)__popcll(ks_group_part<G>(__ballot(ok), half));
         mis += (uint32_t)__popcll(ks_group_part<G>(__ballot(miss), half));
@@ -545,14 +594,32 @@ __global__ void __launch_bounds__(KS_THREADS) kset_spans_kernel(const uint8_t* _
     const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
     const bool have = item < n_items;
     const uint64_t lo = have ? item_lo[item] : 0;
-    ks_group_scan<G>([&](uint32_t x) { return (uint32_t)bytes[lo + x]; }, have, have ? item_len[item] : 0, k, table, slots, out, item);
+    ks_group_scan<G, false>([&](uint32_t x) { return (uint32_t)bytes[lo + x]; }, have, have ? item_len[item] : 0, k, table, slots, out, item);
+}
+
+// kset_spans_kernel against R_t (hypo --qv-min-count; the section "a least count" above)
+template <int G>
+__global__ void __launch_bounds__(KS_THREADS) kset_spans_min_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ item_lo,
+                                                                     const uint32_t* __restrict__ item_len, uint32_t n_items, uint32_t k,
+                                                                     const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out,
+                                                                     const uint8_t* __restrict__ counts, uint32_t t) {
+    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
+    const bool have = item < n_items;
+    const uint64_t lo = have ? item_lo[item] : 0;
+    ks_group_scan<G, true>([&](uint32_t x) { return (uint32_t)bytes[lo + x]; }, have, have ? item_len[item] : 0, k, table, slots, out, item, counts, t);
 }
 
 hipError_t kset_spans_run(const uint8_t* bytes, const uint64_t* item_lo, const uint32_t* item_len, uint32_t n_items, uint32_t k,
-                          const uint64_t* table, uint64_t slots, uint2* out, int group, hipStream_t st) {
+                          const uint64_t* table, uint64_t slots, uint2* out, int group, const uint32_t* planes, uint32_t min_count, hipStream_t st) {
     if (!n_items) return hipSuccess;
     const uint32_t per_block = (uint32_t)KS_THREADS / (uint32_t)group;
     const uint32_t blocks = (n_items + per_block - 1) / per_block;
+    if (min_count > 1) {
+        const uint8_t* counts = (const uint8_t*)planes;
+        if (group == 32) kset_spans_min_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out, counts, min_count);
+        else kset_spans_min_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out, counts, min_count);
+        return hipGetLastError();
+    }
     if (group == 32) kset_spans_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out);
     else kset_spans_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out);
     return hipGetLastError();
@@ -606,7 +673,25 @@ __global__ void __launch_bounds__(KS_THREADS) kset_variants_kernel(const uint8_t
     const uint4 it = have ? items[item] : make_uint4(0, 0, 0, 0);
     const uint64_t lo = have ? site_lo[it.x] : 0;
     const uint32_t e0 = have ? edit_off[it.x] : 0, e1 = have ? edit_off[it.x + 1] : 0;
-    ks_group_scan<G>([&](uint32_t x) { return ks_variant_byte(bytes, alts, lo, e0, e1, eb, ee, ao, al, it.y, it.z + x); }, have, it.w, k, table, slots, out, item);
+    ks_group_scan<G, false>([&](uint32_t x) { return ks_variant_byte(bytes, alts, lo, e0, e1, eb, ee, ao, al, it.y, it.z + x); }, have, it.w, k, table, slots, out, item);
+}
+
+// kset_variants_kernel against R_t (hypo --qv-min-count; the section "a least count" above)
+template <int G>
+__global__ void __launch_bounds__(KS_THREADS) kset_variants_min_kernel(const uint8_t* __restrict__ bytes, const uint8_t* __restrict__ alts,
+                                                                        const uint64_t* __restrict__ site_lo, const uint32_t* __restrict__ edit_off,
+                                                                        const uint64_t* __restrict__ eb, const uint64_t* __restrict__ ee,
+                                                                        const uint64_t* __restrict__ ao, const uint32_t* __restrict__ al,
+                                                                        const uint4* __restrict__ items, uint32_t n_items, uint32_t k,
+                                                                        const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out,
+                                                                        const uint8_t* __restrict__ counts, uint32_t t) {
+    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
+    const bool have = item < n_items;
+    const uint4 it = have ? items[item] : make_uint4(0, 0, 0, 0);
+    const uint64_t lo = have ? site_lo[it.x] : 0;
+    const uint32_t e0 = have ? edit_off[it.x] : 0, e1 = have ? edit_off[it.x + 1] : 0;
+    ks_group_scan<G, true>([&](uint32_t x) { return ks_variant_byte(bytes, alts, lo, e0, e1, eb, ee, ao, al, it.y, it.z + x); }, have, it.w, k, table, slots, out, item,
+                           counts, t);
 }
 
 // One lane per site: the pieces of every variant are added up (the site's items are in mask order, a variant's pieces next to each
@@ -639,11 +724,17 @@ hipError_t kset_variants_run(const uint8_t* bytes, const uint8_t* alts, const ui
                              const uint64_t* ee, const uint64_t* ao, const uint32_t* al, const uint4* items, uint32_t n_items,
                              const uint32_t* site_item, const uint32_t* var_off, uint32_t n_sites, uint32_t k, const uint64_t* table, uint64_t slots,
                              uint2* item_res, uint32_t* best_mask, unsigned long long* best_total, unsigned long long* best_missing,
-                             unsigned long long* var_total, unsigned long long* var_missing, int group, hipStream_t st) {
+                             unsigned long long* var_total, unsigned long long* var_missing, int group, const uint32_t* planes, uint32_t min_count,
+                             hipStream_t st) {
     if (!n_sites || !n_items) return hipSuccess;
     const uint32_t per_block = (uint32_t)KS_THREADS / (uint32_t)group;
     const uint32_t blocks = (n_items + per_block - 1) / per_block;
-    if (group == 32) kset_variants_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res);
+    const uint8_t* counts = (const uint8_t*)planes;
+    if (min_count > 1 && group == 32)
+        kset_variants_min_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res, counts, min_count);
+    else if (min_count > 1)
+        kset_variants_min_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res, counts, min_count);
+    else if (group == 32) kset_variants_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res);
     else kset_variants_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
@@ -704,10 +795,12 @@ hipError_t kset_spectrum_run(const uint32_t* planes, uint64_t slots, uint32_t te
 }
 
 hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table,
-                          uint64_t slots, unsigned long long* total, unsigned long long* missing, hipStream_t st) {
+                          uint64_t slots, unsigned long long* total, unsigned long long* missing, const uint32_t* planes, uint32_t min_count, hipStream_t st) {
     if (!n || !n_seqs) return hipSuccess;
     const uint64_t blocks = (n + KR_BLOCK_BYTES - 1) / KR_BLOCK_BYTES;
-    kset_query_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing);
+    if (min_count > 1)
+        kset_query_min_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing, (const uint8_t*)planes, min_count);
+    else kset_query_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing);
     return hipGetLastError();
 }
 

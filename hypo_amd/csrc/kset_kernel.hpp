@@ -37,10 +37,13 @@ hipError_t kset_mark_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_s
                          uint32_t* planes, uint32_t text, unsigned long long* sums, hipStream_t st);
 // hist[c * 5 + j] += the keys with count byte c and min(copy byte of `text`, 4) == j; KSET_HIST_BINS values, zeroed by the caller
 hipError_t kset_spectrum_run(const uint32_t* planes, uint64_t slots, uint32_t text, unsigned long long* hist, hipStream_t st);
+// A least count (hypo --qv-min-count; DESIGN.md "k-mer min count"): the four queries below take the planes of a set that counts and
+// min_count = t.  With t >= 2 they answer against R_t, the keys whose count byte is at least t, with kernels of their own
+// (kset_*_min_kernel); with t <= 1 they launch the kernels they always launched and `planes` is not looked at (it may be NULL).
 // n_seqs byte strings back to back in bytes[0, off[n_seqs]) (off[0] = 0): total[s] += length-k windows of sequence s made of
 // ACGTacgt only, missing[s] += those whose canonical k-mer is not in the table.  total / missing must be zeroed by the caller.
 hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table,
-                          uint64_t slots, unsigned long long* total, unsigned long long* missing, hipStream_t st);
+                          uint64_t slots, unsigned long long* total, unsigned long long* missing, const uint32_t* planes, uint32_t min_count, hipStream_t st);
 // The same query, and where the missing windows are (hypo --qv-bed; DESIGN.md "k-mer QV track"), in two steps with the caller
 // reading pre[3 blocks .. 3 blocks + 3) = (intervals, intervals, missing windows of wanted sequences) in between, blocks =
 // kset_track_blocks(n).  want: NULL or n_seqs bytes, 0 = no intervals for that sequence.  Work space: miss_bits / begin_bits of
@@ -51,7 +54,7 @@ hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_
 uint32_t kset_track_blocks(uint64_t n);
 hipError_t kset_track_count_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table, uint64_t slots,
                                 unsigned long long* total, unsigned long long* missing, const uint8_t* want, uint32_t* miss_bits, uint32_t* begin_bits,
-                                uint64_t* sums, uint64_t* pre, hipStream_t st);
+                                uint64_t* sums, uint64_t* pre, const uint32_t* planes, uint32_t min_count, hipStream_t st);
 hipError_t kset_track_emit_run(const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint32_t* miss_bits, const uint32_t* begin_bits,
                                const uint64_t* pre, uint64_t n_iv, uint64_t* iv_off, uint64_t* iv_start, uint64_t* iv_end, uint64_t* cnt_lo,
                                uint64_t* cnt_hi, hipStream_t st);
@@ -61,7 +64,7 @@ hipError_t kset_track_emit_run(const uint64_t* off, uint32_t n_seqs, uint64_t n,
 constexpr uint32_t KSET_SPAN_PIECE = 2048;
 constexpr int KSET_SPAN_GROUP = 32;                // the default geometry (DESIGN.md "k-mer guard": measured against 64)
 hipError_t kset_spans_run(const uint8_t* bytes, const uint64_t* item_lo, const uint32_t* item_len, uint32_t n_items, uint32_t k,
-                          const uint64_t* table, uint64_t slots, uint2* out, int group, hipStream_t st);
+                          const uint64_t* table, uint64_t slots, uint2* out, int group, const uint32_t* planes, uint32_t min_count, hipStream_t st);
 
 // Every subset of the edits of n_sites sites (hypo --guard-records): site s is bytes[site_lo[s], ..) with the edits
 // [edit_off[s], edit_off[s + 1]) (at most KSET_MAX_EDITS, ascending and disjoint; edit e replaces bytes[eb[e], ee[e]) by
@@ -76,6 +79,7 @@ hipError_t kset_variants_run(const uint8_t* bytes, const uint8_t* alts, const ui
                              const uint64_t* ee, const uint64_t* ao, const uint32_t* al, const uint4* items, uint32_t n_items,
                              const uint32_t* site_item, const uint32_t* var_off, uint32_t n_sites, uint32_t k, const uint64_t* table, uint64_t slots,
                              uint2* item_res, uint32_t* best_mask, unsigned long long* best_total, unsigned long long* best_missing,
-                             unsigned long long* var_total, unsigned long long* var_missing, int group, hipStream_t st);
+                             unsigned long long* var_total, unsigned long long* var_missing, int group, const uint32_t* planes, uint32_t min_count,
+                             hipStream_t st);
 
 }  // namespace hypo

@@ -491,6 +491,16 @@ int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n
 int hypo_gpu_kset_counts_enable(uint32_t n_texts);
 int hypo_gpu_kset_mark(uint32_t text, const char* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t* n_windows, uint64_t* n_unmarked);
 int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist);
+/* A least count for the queries (hypo --qv-min-count; DESIGN.md "k-mer min count").  Additive to ABI 11: callers bind it by name.
+ * R_t = the k-mers of the set whose count (hypo_gpu_kset_counts_enable) is at least t; R_1 is the set.  From the next call on
+ * hypo_gpu_kset_query, _query_spans, _query_variants and _query_track answer against R_t: a window whose k-mer the reads contain
+ * fewer than t times is missing, and everything those entry points derive from "missing" (intervals, best masks) follows.  The
+ * threshold is applied when a query runs, to the counts of that moment: it may be set any number of times, before or after adds
+ * and marks, it does not close the set, and hypo_gpu_kset_add, _size, _mark and _spectrum do not know of it.  hypo_gpu_kset_begin
+ * starts at t = 1, and with t = 1 the queries run the kernels they run on a set that does not count.  A count stops at 255, so
+ * R_255 holds the k-mers seen 255 times or more.  HYPO_E_INVALID: no set, a set without counts, t outside 1..255; a refused call
+ * changes nothing.  On the calling thread's context. */
+int hypo_gpu_kset_min_count(uint32_t t);
 
 /* Kernel timing with HIP events on the stream the kernels run on ----------------------------------
  * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each records

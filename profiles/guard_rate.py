@@ -16,6 +16,9 @@ spans and the sites of a real run's records, and what the guard adds to the wall
          (--parent-bin: hypo of a build of the parent, beside its two libraries), --qv, --qv --kmer-guard,
          --kmer-guard, --guard-records.
     python profiles/guard_rate.py --spans-only spans_c3.npz --reads reads.fa      # (the child of steps 2 and 3)
+    --min-count (either form): the child's set counts, and after the calls above (t = 1: the presence kernels) it makes them again at
+    t = 2 and at the valley of the read histogram (hypo --qv-min-count: kset_spans_min_kernel, kset_variants_min_kernel), in the same
+    process on the same spans and sites; the rocprofv3 pass of step 3 then lists the counted kernels next to the presence ones.
 """
 import argparse
 import csv
@@ -39,13 +42,15 @@ REPS = 5
 N_MAX = 8                     # --guard-records-max's default
 
 
-def spans_calls(path, reads):
+def spans_calls(path, reads, min_count=False):
     from hypo_amd import capi
     z = np.load(path)
     text, lo, hi = z["text"], z["lo"], z["hi"]
     gpu = capi.HypoGpu(0)
     data = np.fromfile(reads, dtype=np.uint8)
     gpu.kset_begin(K, int(z["genome"]))
+    if min_count:
+        gpu.kset_counts_enable(1)                           # (t stays 1 for the first round: the presence kernels, on the same set)
     t0 = time.perf_counter()
     for at in range(0, data.size, PIECE - (K - 1)):
         gpu.kset_add(data[at:at + PIECE])
@@ -54,42 +59,55 @@ def spans_calls(path, reads):
     windows = int(np.maximum(hi.astype(np.int64) - lo.astype(np.int64) - K + 1, 0).sum())
     out = {"spans": int(lo.size), "text_bytes": int(text.size), "windows": windows, "span_bytes_mean": round(float((hi - lo).mean()), 1),
            "set_build_s": round(t_set, 3), "distinct": gpu.kset_size()[0], "groups": {}}
-    answers = []
-    for group in (32, 64):
-        os.environ["HYPO_KSET_SPAN_GROUP"] = str(group)
-        gpu.kset_query_spans(text, lo, hi)                  # warm-up: arenas grown, code loaded
-        ts = []
-        for _ in range(REPS):
-            t0 = time.perf_counter()
-            total, missing = gpu.kset_query_spans(text, lo, hi)
-            ts.append(time.perf_counter() - t0)
-        answers.append((total, missing))
-        out["groups"][str(group)] = {"call_s": [round(t, 4) for t in ts], "best_s": round(min(ts), 4), "spans_per_s": round(lo.size / min(ts)),
-                                     "windows_per_s": round(windows / min(ts))}
-    assert all(np.array_equal(a, b) for a, b in zip(*answers)), "the two geometries disagree"
-    out["missing_windows"] = int(answers[0][1].sum())
-    if "v_lo" in z:                                          # the sites of --guard-records over the drafts alone
-        args = (z["v_text"], z["v_alts"], z["v_lo"], z["v_hi"], z["v_eoff"], z["v_eb"], z["v_ee"], z["v_ao"], z["v_al"])
-        n_edits = np.diff(z["v_eoff"].astype(np.int64))
-        v = {"sites": int(z["v_lo"].size), "edits": int(n_edits.sum()), "variants": int((1 << n_edits).sum()), "text_bytes": int(z["v_text"].size),
-             "alt_bytes": int(z["v_alts"].size), "cluster_sizes": json.loads(str(z["v_hist"])), "groups": {}}
-        masks = []
+
+    def measure(out):
+        """both calls, both geometries, against the set as it answers now"""
+        answers = []
         for group in (32, 64):
             os.environ["HYPO_KSET_SPAN_GROUP"] = str(group)
-            gpu.kset_query_variants(*args, variants=False)
+            gpu.kset_query_spans(text, lo, hi)                  # warm-up: arenas grown, code loaded
             ts = []
             for _ in range(REPS):
                 t0 = time.perf_counter()
-                best = gpu.kset_query_variants(*args, variants=False)
+                total, missing = gpu.kset_query_spans(text, lo, hi)
                 ts.append(time.perf_counter() - t0)
-            masks.append(best[0])
-            v["groups"][str(group)] = {"call_s": [round(t, 4) for t in ts], "best_s": round(min(ts), 4), "variants_per_s": round(v["variants"] / min(ts))}
-        assert np.array_equal(*masks), "the two geometries disagree"
-        full = (1 << n_edits) - 1
-        whole = z["v_whole"].astype(bool)                    # sites of clusters beyond the limit: one edit, decided whole
-        v["rejected_whole"] = int((masks[0] == 0).sum())
-        v["accepted_in_part"] = int(((masks[0] != 0) & (masks[0] != full) & ~whole).sum())
-        out["variants"] = v
+            answers.append((total, missing))
+            out["groups"][str(group)] = {"call_s": [round(t, 4) for t in ts], "best_s": round(min(ts), 4), "spans_per_s": round(lo.size / min(ts)),
+                                         "windows_per_s": round(windows / min(ts))}
+        assert all(np.array_equal(a, b) for a, b in zip(*answers)), "the two geometries disagree"
+        out["missing_windows"] = int(answers[0][1].sum())
+        if "v_lo" in z:                                          # the sites of --guard-records over the drafts alone
+            args = (z["v_text"], z["v_alts"], z["v_lo"], z["v_hi"], z["v_eoff"], z["v_eb"], z["v_ee"], z["v_ao"], z["v_al"])
+            n_edits = np.diff(z["v_eoff"].astype(np.int64))
+            v = {"sites": int(z["v_lo"].size), "edits": int(n_edits.sum()), "variants": int((1 << n_edits).sum()), "text_bytes": int(z["v_text"].size),
+                 "alt_bytes": int(z["v_alts"].size), "cluster_sizes": json.loads(str(z["v_hist"])), "groups": {}}
+            masks = []
+            for group in (32, 64):
+                os.environ["HYPO_KSET_SPAN_GROUP"] = str(group)
+                gpu.kset_query_variants(*args, variants=False)
+                ts = []
+                for _ in range(REPS):
+                    t0 = time.perf_counter()
+                    best = gpu.kset_query_variants(*args, variants=False)
+                    ts.append(time.perf_counter() - t0)
+                masks.append(best[0])
+                v["groups"][str(group)] = {"call_s": [round(t, 4) for t in ts], "best_s": round(min(ts), 4), "variants_per_s": round(v["variants"] / min(ts))}
+            assert np.array_equal(*masks), "the two geometries disagree"
+            full = (1 << n_edits) - 1
+            whole = z["v_whole"].astype(bool)                    # sites of clusters beyond the limit: one edit, decided whole
+            v["rejected_whole"] = int((masks[0] == 0).sum())
+            v["accepted_in_part"] = int(((masks[0] != 0) & (masks[0] != full) & ~whole).sum())
+            out["variants"] = v
+
+    measure(out)
+    if min_count:                                            # --min-count: the same calls once more at t = 2 and at the valley, the kset_*_min_kernel variants
+        h = gpu.kset_spectrum(0).sum(axis=1)
+        valley = next((c for c in range(2, 255) if h[c] <= h[c + 1]), 2)
+        out["min_count"] = {"valley": int(valley)}
+        for t in (2, int(valley)):
+            gpu.kset_min_count(t)
+            out["min_count"][str(t)] = {"groups": {}}
+            measure(out["min_count"][str(t)])
     gpu.kset_end()
     return out
 
@@ -164,12 +182,13 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--spans-only")
     ap.add_argument("--reads")
+    ap.add_argument("--min-count", action="store_true", help="the set counts, and both calls are timed at t = 1, t = 2 and the valley (hypo --qv-min-count)")
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--wall-runs", type=int, default=10)
     ap.add_argument("--parent-bin", help="hypo of a build of the parent commit (flag-off comparison)")
     args = ap.parse_args()
     if args.spans_only:
-        print(json.dumps(spans_calls(args.spans_only, args.reads)))
+        print(json.dumps(spans_calls(args.spans_only, args.reads, args.min_count)))
         return
     out = os.path.abspath(args.out)
     os.makedirs(out, exist_ok=True)
@@ -180,7 +199,7 @@ def main():
         json.dump(res, open(os.path.join(out, "guard_rate.json"), "w"), indent=1)
     path, d, argv, reads, res["run"] = prepare(work, args.threads)
     print(json.dumps(res["run"]), flush=True)
-    child = [sys.executable, os.path.abspath(__file__), "--spans-only", path, "--reads", reads]
+    child = [sys.executable, os.path.abspath(__file__), "--spans-only", path, "--reads", reads] + (["--min-count"] if args.min_count else [])
     p = subprocess.run(["timeout", "-k", "10", "600"] + child, capture_output=True, text=True)
     if p.returncode != 0:                                  # (nothing more on the GPU after a failed child)
         print(p.stderr[-1500:], flush=True)
