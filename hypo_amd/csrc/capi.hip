@@ -109,7 +109,7 @@ struct DevBuf {
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
 
-// HIP-event recorder for the next calls (hypo_gpu_profile_*)
+// recorder for the next calls (hypo_gpu_profile_*): HIP events bound to the kernels' dispatches, no marker on a stream
 struct ProfCall { int kind = 0; hypo::KernelEvents ke; };      // kind 1 = POA, 2 = scan
 struct Prof { std::vector<ProfCall> calls; int used = 0; };
 
@@ -270,7 +270,7 @@ hipError_t d2h(void* dst, const void* src, size_t bytes, hipStream_t st) {
 ProfCall* prof_next(int kind) {
     if (g_prof.used >= (int)g_prof.calls.size()) return nullptr;
     ProfCall* c = &g_prof.calls[g_prof.used++];
-    c->kind = kind; c->ke.n = 0;
+    c->kind = kind; c->ke.n = 0; c->ke.bound = 0;
     return c;
 }
 
@@ -563,7 +563,8 @@ int hypo_gpu_profile_begin(int max_calls) {
     for (auto& c : g_prof.calls) for (auto& e : c.ke.ev) if (e) (void)hipEventDestroy(e);
     g_prof.calls.assign((size_t)max_calls, ProfCall());
     g_prof.used = 0;
-    for (auto& c : g_prof.calls) for (auto& e : c.ke.ev) HIP_TRY(hipEventCreate(&e));
+    // (the events only carry times: no system-scope release at the end of the kernel one is bound to)
+    for (auto& c : g_prof.calls) for (auto& e : c.ke.ev) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableSystemFence));
     return HYPO_OK;
 }
 int hypo_gpu_profile_calls(void) { return g_prof.used; }
@@ -572,23 +573,25 @@ int hypo_gpu_profile_read(int call, float* ms, int n) {
     if (call < 0 || call >= g_prof.used || !ms) return fail(HYPO_E_INVALID, "no such profiled call");
     ProfCall& c = g_prof.calls[(size_t)call];
     if (c.ke.n < 2) return 0;
-    HIP_TRY(hipEventSynchronize(c.ke.ev[c.ke.n - 1]));
+    HIP_TRY(hipEventSynchronize(c.ke.ev[c.kind == 1 ? c.ke.n - 1 : 1]));
     int out = 0;
     float t = 0.f;
-    if (c.kind == 1) {          // POA: [plan, class 0..4, whole call]; event pairs may sit on different streams
+    if (c.kind == 1) {          // POA: [plan, class 0..5, whole call]; the kernels of the pairs may sit on different streams
         const int pairs = (c.ke.n - 1) / 2;
         for (int i = 0; i < pairs && out < n; ++i) {
-            HIP_TRY(hipEventSynchronize(c.ke.ev[2 * i + 1]));
-            HIP_TRY(hipEventElapsedTime(&t, c.ke.ev[2 * i], c.ke.ev[2 * i + 1]));
+            t = 0.f;                                           // (a class without a timed launch in this call: KernelEvents::bound)
+            if (i == 0 || (c.ke.bound >> (2 * i)) & 1u) {
+                HIP_TRY(hipEventSynchronize(c.ke.ev[2 * i + 1]));
+                HIP_TRY(hipEventElapsedTime(&t, c.ke.ev[2 * i], c.ke.ev[2 * i + 1]));
+            }
             ms[out++] = t;
         }
         if (out < n) { HIP_TRY(hipEventElapsedTime(&t, c.ke.ev[0], c.ke.ev[c.ke.n - 1])); ms[out++] = t; }
         return out;
     }
-    for (int i = 0; i + 1 < c.ke.n && out < n; ++i) {
-        HIP_TRY(hipEventElapsedTime(&t, c.ke.ev[i], c.ke.ev[i + 1]));
-        ms[out++] = t;
-    }
+    // scan: [the scan kernel, 0, 0] (the two zeros keep the record's length: they timed nothing but event records since round 5)
+    HIP_TRY(hipEventElapsedTime(&t, c.ke.ev[0], c.ke.ev[1]));
+    for (int i = 0; i + 1 < c.ke.n && out < n; ++i) ms[out++] = i == 0 ? t : 0.f;
     return out;
 }
 
@@ -943,7 +946,7 @@ int hypo_gpu_solid_scan_device(const uint8_t* packed4, uint64_t n_bases, uint32_
         return fail(HYPO_E_WORKSPACE, "workspace %zu < required %zu", workspace_bytes, hypo::scan_workspace_bytes(n_bases));
     hipStream_t st = (hipStream_t)hip_stream;                  // NULL is the HIP null stream itself (what torch calls its default stream)
     ProfCall* pc = prof_next(2);
-    if (pc) pc->ke.n = 4;
+    if (pc) pc->ke.n = n_bases ? 4 : 0;                        // (an empty scan launches nothing: an empty record)
     HIP_TRY(hypo::scan_run(packed4, n_bases, k, bits, solid_pos_words, kids, kids_cap, word_rank, n_solid,
                            workspace, workspace_bytes, st, pc ? pc->ke.ev : nullptr));
     return HYPO_OK;

@@ -33,6 +33,7 @@ constexpr size_t kPoaHdrCursor = 6144;
 constexpr size_t kPoaHdrPlanned = 7680;
 constexpr size_t kPoaHdrHead2 = 7744;
 constexpr size_t kPoaHdrDone = 7808;        // done[8]
+constexpr size_t kPoaHdrPlanTicket = 7840;  // workgroups of poa_plan_count_kernel that have flushed their histogram
 constexpr size_t kPoaHdrSpillUsed = 7872;
 constexpr size_t kPoaHdrWork = 7936;        // work[8] (u64)
 static_assert(kPoaHdrWork + 8 * sizeof(uint64_t) <= kPoaHeaderBytes && kPoaHdrStats + sizeof(HypoPoaStats) <= kPoaHdrPhase, "workspace header");
@@ -63,9 +64,11 @@ struct PoaQueues {
     PoaPinned* host;        // PoaAux::pinned (page-locked host memory the kernels write their counts to: no copy commands on the stream)
 };
 
-// optional event recorder: ev[0]/ev[1] around the plan kernels, ev[2+2c]/ev[3+2c] around size-class kernel c
-// (recorded on the stream that kernel runs on), ev[2+2*classes] after everything has joined the caller's stream
-struct KernelEvents { hipEvent_t ev[16]; int n; };
+// optional event recorder.  The events are bound to the dispatches themselves (hipExtLaunchKernelGGL: the kernel's own start and
+// end time, no marker packet on any stream): ev[0] = start of poa_plan_count_kernel, ev[1] = end of poa_plan_scatter_kernel,
+// ev[2+2c] / ev[3+2c] = start / end of the launch of size class c that poa_run times (bit 2+2c of `bound` is set when there was
+// one), ev[2+2*classes] = end of poa_giant_kernel, the last kernel of the call.
+struct KernelEvents { hipEvent_t ev[16]; int n; uint32_t bound; };
 
 // Streams, events and the pinned readback buffer poa_run() needs beyond the caller's stream.  Owned by the library context
 // (capi.hip): created on first use on the current device, released by poa_release() at shutdown / device change.

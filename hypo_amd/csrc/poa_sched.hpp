@@ -82,7 +82,7 @@ struct PoaKnobs {
 // ------------------------------------------------------------------------------------------------
 // history: what the kernels leave in page-locked host memory, and what a call reads out of it
 // ------------------------------------------------------------------------------------------------
-// PoaAux::pinned.  poa_plan_scan_kernel writes `plan`, poa_giant_kernel (the last launch of a call) `final_count` and `work`: no
+// PoaAux::pinned.  poa_plan_count_kernel (its last workgroup) writes `plan`, poa_giant_kernel (the last launch of a call) `final_count` and `work`: no
 // copy commands on the stream, and whoever reads gets the last finished call.
 struct PoaPinned {
     uint32_t plan[8];            // planned counts per class of the call in flight

@@ -18,6 +18,7 @@
 // The 4^k-bit set is NOT staged through LDS for the survey's configurations: k=11 needs 512 KiB,
 // more than the 160 KiB of a CU, while it fits every XCD's 4 MiB L2.
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include "scan_kernel.hpp"
 
 namespace hypo {
@@ -250,12 +251,16 @@ hipError_t scan_run(const uint8_t* packed4, uint64_t n_bases, uint32_t k, const 
         if (n_solid) return hipMemsetAsync(n_solid, 0, 8, stream);
         return hipSuccess;
     }
-    if (prof_ev) (void)hipEventRecord(prof_ev[0], stream);
     if ((e = hipMemsetAsync(ws, 0, 256 + status_bytes, stream)) != hipSuccess) return e;
-    hipLaunchKernelGGL(scan_fused_kernel, dim3((unsigned)n_tiles), dim3(SCAN_THREADS), 0, stream,
-                       packed4, n_bases, k, bits, words, word_rank, (kids && kids_cap) ? kids : nullptr, kids_cap, n_words, n_tiles, hdr, status, n_solid,
-                       kids_cap ? kids32 : nullptr, kids_cap ? spos : nullptr);
-    if (prof_ev) { (void)hipEventRecord(prof_ev[1], stream); (void)hipEventRecord(prof_ev[2], stream); (void)hipEventRecord(prof_ev[3], stream); }
+    // a profiled call binds prof_ev[0] / prof_ev[1] to the dispatch (the kernel's own start and end time, no marker on the stream)
+    if (prof_ev)
+        hipExtLaunchKernelGGL(scan_fused_kernel, dim3((unsigned)n_tiles), dim3(SCAN_THREADS), 0, stream, prof_ev[0], prof_ev[1], 0,
+                              packed4, n_bases, k, bits, words, word_rank, (kids && kids_cap) ? kids : nullptr, kids_cap, n_words, n_tiles, hdr, status, n_solid,
+                              kids_cap ? kids32 : nullptr, kids_cap ? spos : nullptr);
+    else
+        hipLaunchKernelGGL(scan_fused_kernel, dim3((unsigned)n_tiles), dim3(SCAN_THREADS), 0, stream,
+                           packed4, n_bases, k, bits, words, word_rank, (kids && kids_cap) ? kids : nullptr, kids_cap, n_words, n_tiles, hdr, status, n_solid,
+                           kids_cap ? kids32 : nullptr, kids_cap ? spos : nullptr);
     return hipGetLastError();
 }
 

@@ -502,13 +502,15 @@ int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist);
  * changes nothing.  On the calling thread's context. */
 int hypo_gpu_kset_min_count(uint32_t t);
 
-/* Kernel timing with HIP events on the stream the kernels run on ----------------------------------
- * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each records
- * events around its kernels.  hypo_gpu_profile_read(call, ms, n) synchronises that call's last event
- * and returns up to n elapsed times in milliseconds:
- *   POA call : ms[0] = plan kernels, ms[1 + c] = size-class kernel c (6 classes; the LDS classes overlap in time),
- *              ms[7] = the whole call on the caller's stream (HYPO_PROFILE_POA_SLOTS values)
- *   scan call: ms[0] = mark, ms[1] = rank (3 kernels), ms[2] = kids (HYPO_PROFILE_SCAN_SLOTS values)
+/* Kernel timing: each kernel's own start and end time --------------------------------------------
+ * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each binds HIP
+ * events to the dispatches of its kernels (no marker packet on any stream: what a profiled call puts
+ * between its kernels is what an unprofiled one does).  hypo_gpu_profile_read(call, ms, n) waits for
+ * that call's last kernel and returns up to n elapsed times in milliseconds:
+ *   POA call : ms[0] = plan kernels (start of the first to end of the last), ms[1 + c] = the timed launch of size
+ *              class c, start to end (6 classes; the LDS classes overlap in time; 0.0 when the call had no such launch),
+ *              ms[7] = start of the plan to the end of the call's last kernel (HYPO_PROFILE_POA_SLOTS values)
+ *   scan call: ms[0] = the scan kernel, start to end, ms[1] = ms[2] = 0.0 (HYPO_PROFILE_SCAN_SLOTS values)
  * Returns the number of values written, or <0. */
 #define HYPO_PROFILE_POA_SLOTS 8
 #define HYPO_PROFILE_SCAN_SLOTS 3
