@@ -72,6 +72,7 @@ public:
     std::string polished_text() const;                      // the sequence line operator<< writes (hypo --qv asks the k-mer set about it)
     friend class Alignment;
     friend class DeviceArms;
+    friend struct VoteTables;                               // host_capi.cpp: fills the tables of the vote loops from flat arrays (tests)
 
     // scan results (Contig::_solid_pos / _kmerinfo[i]->kid)
     uint64_t get_num_solid() const { return _n_solid; }

@@ -12,6 +12,43 @@
 
 using namespace hypo;
 
+// What Alignment::update_solidkmers_support / update_minimisers_support read of a Contig, put there from the flat arrays the
+// C-ABI of the device votes takes (include/hypo_gpu.h) instead of by a scan and prepare_for_division.
+namespace hypo {
+struct VoteTables {
+    static void set_solid(Contig& c, uint64_t n_solid, const uint32_t* spos, const uint64_t* kids) {
+        for (uint64_t i = 0; i < n_solid; ++i) c._solid_pos.set(spos[i]);
+        c._solid_pos.init_support();
+        c._kids.assign(kids, kids + n_solid);
+        c._n_solid = n_solid;
+        c._kcov.assign(n_solid, 0); c._ksup.assign(n_solid, 0);
+    }
+    static void get_solid(const Contig& c, uint32_t* cov, uint32_t* sup) {
+        std::memcpy(cov, c._kcov.data(), c._kcov.size() * 4); std::memcpy(sup, c._ksup.data(), c._ksup.size() * 4);
+    }
+    // borders [n_borders]: the set bits of _reg_pos; entries of MWMinimiserInfo x of the contig: [off[x], off[x + 1]) of rel_pos / minimisers
+    static void set_mega(Contig& c, const uint32_t* borders, uint32_t n_borders, bool even, uint32_t n_info, const uint32_t* off, const uint32_t* rel_pos, const uint32_t* minimisers) {
+        for (uint32_t i = 0; i < n_borders; ++i) c._reg_pos.set(borders[i]);
+        c._reg_pos.init_support();
+        c._is_win_even = even;
+        c._minimserinfo.assign(n_info, MWMinimiserInfo());
+        for (uint32_t x = 0; x < n_info; ++x) {
+            MWMinimiserInfo& mi = c._minimserinfo[x];
+            mi.rel_pos.assign(rel_pos + off[x], rel_pos + off[x + 1]);
+            mi.minimisers.assign(minimisers + off[x], minimisers + off[x + 1]);
+            mi.coverage.assign(mi.rel_pos.size(), 0); mi.support.assign(mi.rel_pos.size(), 0);
+        }
+    }
+    static void get_mega(const Contig& c, uint32_t n_info, const uint32_t* off, uint32_t* cov, uint32_t* sup) {
+        for (uint32_t x = 0; x < n_info; ++x) {
+            const MWMinimiserInfo& mi = c._minimserinfo[x];
+            if (mi.coverage.empty()) continue;
+            std::memcpy(cov + off[x], mi.coverage.data(), mi.coverage.size() * 4); std::memcpy(sup + off[x], mi.support.data(), mi.support.size() * 4);
+        }
+    }
+};
+}  // namespace hypo
+
 extern "C" {
 
 int hypo_host_set_scores(const int8_t sc[6]) {
@@ -140,6 +177,58 @@ int hypo_host_plan_contexts(uint32_t initial_cid, uint32_t final_cid, int n_ctx,
                             int split_batch, int allow_pieces, uint32_t* out) {
     const std::vector<hypo::CtxWork> work = hypo::plan_contexts(initial_cid, final_cid, n_ctx, n_reads, contig_len, split_batch != 0, allow_pieces != 0);
     for (const hypo::CtxWork& w : work) { *out++ = w.c0; *out++ = w.c1; *out++ = w.piece ? 1 : 0; *out++ = w.own0; *out++ = w.own1; }
+    return 0;
+}
+
+// Alignment::update_solidkmers_support of every read over one coordinate space of total_len bases whose solid k-mers are given
+// as hypo_gpu_support_kmers takes them (spos ascending, kids); the reads as hypo_gpu_reads_upload takes them.  OUT coverage /
+// support [n_solid].  -1: a table or a read does not fit the coordinate space.
+int hypo_host_kmer_votes(uint32_t k, uint64_t total_len, uint64_t n_solid, const uint32_t* spos, const uint64_t* kids, uint32_t n_reads, const uint32_t* rb,
+                         const uint32_t* re, const uint32_t* qae, const uint64_t* seq_off, const uint8_t* reads2, uint32_t* coverage, uint32_t* support) {
+    for (uint64_t i = 0; i < n_solid; ++i) if (spos[i] >= total_len || (i && spos[i - 1] >= spos[i])) return -1;
+    for (uint32_t a = 0; a < n_reads; ++a) if (re[a] <= rb[a] || re[a] > total_len) return -1;
+    Contig c(0, "votes", std::string((size_t)total_len, 'A'));
+    VoteTables::set_solid(c, n_solid, spos, kids);
+    for (uint32_t a = 0; a < n_reads; ++a) {
+        Alignment al(rb[a], re[a], qae[a], reads2 + seq_off[a], nullptr, 0);
+        al.update_solidkmers_support(k, c);
+    }
+    VoteTables::get_solid(c, coverage, support);
+    return 0;
+}
+
+// Alignment::update_minimisers_support of every read, one Contig per contig of the tables (the arrays of HypoMegaWindows; a contig's
+// length is its last border); rb / re are in the batch's coordinate space, read_contig names the contig.  OUT coverage / support
+// [mw_off[n_info]].  -1: a read does not lie inside its contig.
+int hypo_host_minimizer_votes(uint32_t n_contigs, const uint32_t* contig_base, const uint32_t* reg_base, const uint8_t* win_even, const uint32_t* info_base,
+                              const uint32_t* start, uint32_t n_info, const uint32_t* mw_off, const uint32_t* rel_pos, const uint32_t* minimisers,
+                              uint32_t n_reads, const uint32_t* rb, const uint32_t* re, const uint32_t* qae, const uint64_t* seq_off, const uint8_t* reads2,
+                              const uint32_t* read_contig, uint32_t* coverage, uint32_t* support) {
+    std::vector<std::unique_ptr<Contig>> ctg;
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        const uint32_t nb = reg_base[c + 1] - reg_base[c];
+        const uint32_t len = nb ? start[reg_base[c + 1] - 1] : 0;
+        const uint32_t x0 = info_base[c], x1 = c + 1 < n_contigs ? info_base[c + 1] : n_info;
+        ctg.emplace_back(new Contig(c, "votes", std::string((size_t)len, 'A')));
+        // (entry x of the contig is entry x0 + x of the tables: the offsets are taken relative to the contig's first entry)
+        std::vector<uint32_t> off(mw_off + x0, mw_off + x1 + 1);
+        const uint32_t e0 = off[0];
+        for (uint32_t& o : off) o -= e0;
+        VoteTables::set_mega(*ctg.back(), start + reg_base[c], nb, win_even[c] != 0, x1 - x0, off.data(), rel_pos + e0, minimisers + e0);
+    }
+    for (uint32_t a = 0; a < n_reads; ++a) {
+        const uint32_t c = read_contig[a];
+        if (c >= n_contigs || rb[a] < contig_base[c] || re[a] <= rb[a] || re[a] - contig_base[c] > ctg[c]->get_len()) return -1;
+        Alignment al(rb[a] - contig_base[c], re[a] - contig_base[c], qae[a], reads2 + seq_off[a], nullptr, 0);
+        al.update_minimisers_support(*ctg[c]);
+    }
+    for (uint32_t c = 0; c < n_contigs; ++c) {
+        const uint32_t x0 = info_base[c], x1 = c + 1 < n_contigs ? info_base[c + 1] : n_info;
+        std::vector<uint32_t> off(mw_off + x0, mw_off + x1 + 1);
+        const uint32_t e0 = off[0];
+        for (uint32_t& o : off) o -= e0;
+        VoteTables::get_mega(*ctg[c], x1 - x0, off.data(), coverage + e0, support + e0);
+    }
     return 0;
 }
 

@@ -41,8 +41,9 @@ __device__ __forceinline__ uint32_t count_less_equal(const uint32_t* a, uint32_t
 // sorted), so the solid k-mers they can see are one short stretch of the arrays: the block copies that stretch (positions, ids) into
 // LDS once and every lane's walk reads LDS; coverage becomes a +1 / -1 pair per read on a difference array in LDS, support an LDS
 // counter, and one global atomic per touched k-mer and block goes out at the end (120 global atomics per read before).  The read's
-// bases come in 16 at a time.  A block whose stretch does not fit (sparse reads) takes the same walk over global memory.  Which
-// (k-mer, read) pairs vote, and in which order within a read, is unchanged.
+// bases come in 16 at a time.  A block whose stretch does not fit (sparse reads, long reads) walks it tile by tile: every lane pauses
+// where its window reaches the end of the tile and goes on in the next one (WalkState below).  Which (k-mer, read) pairs vote, and in
+// which order within a read, is unchanged.
 namespace {
 constexpr uint32_t KCAP = 2048;                           // solid k-mers of a block's tile held in LDS
 constexpr uint32_t kLongReadSpan = 1000;                  // mean reference span above which a block takes 64 reads instead of 256

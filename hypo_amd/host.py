@@ -89,3 +89,35 @@ class HostMirror:
         self.lib.hypo_host_plan_contexts(C.c_uint32(initial_cid), C.c_uint32(final_cid), C.c_int(n_ctx), p(nr), p(cl),
                                          C.c_int(1 if split_batch else 0), C.c_int(1 if allow_pieces else 0), p(out))
         return [(int(r[0]), int(r[1]), bool(r[2]), int(r[3]), int(r[4])) for r in out.reshape(n_ctx, 5)]
+
+    def kmer_votes(self, k, total_len, spos, kids, rb, re, qae, seq_off, reads2):
+        """(coverage, support) of Alignment::update_solidkmers_support over every read: the host loop on the flat arrays
+        hypo_gpu_reads_upload / hypo_gpu_support_kmers take (include/hypo_gpu.h)"""
+        spos = np.ascontiguousarray(spos, dtype=np.uint32); kids = np.ascontiguousarray(kids, dtype=np.uint64)
+        rb, re, qae = (np.ascontiguousarray(x, dtype=np.uint32) for x in (rb, re, qae))
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64); reads2 = np.ascontiguousarray(reads2, dtype=np.uint8)
+        cov = np.zeros(max(spos.size, 1), dtype=np.uint32); sup = np.zeros(max(spos.size, 1), dtype=np.uint32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = self.lib.hypo_host_kmer_votes(C.c_uint32(k), C.c_uint64(total_len), C.c_uint64(spos.size), p(spos), p(kids), C.c_uint32(rb.size),
+                                           p(rb), p(re), p(qae), p(seq_off), p(reads2), p(cov), p(sup))
+        if rc != 0:
+            raise RuntimeError(f"hypo_host_kmer_votes rc={rc}")
+        return cov[:spos.size], sup[:spos.size]
+
+    def minimizer_votes(self, tables, rb, re, qae, seq_off, reads2, read_contig):
+        """(coverage, support) of Alignment::update_minimisers_support over every read; tables: the arrays of HypoMegaWindows by
+        name (contig_base, reg_base, win_even, info_base, start, n_info, mw_off, rel_pos, minimisers)"""
+        u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)
+        T = tables
+        cb, rbase, ib, start, off, rel, mins = (u32(x) for x in (T.contig_base, T.reg_base, T.info_base, T.start, T.mw_off, T.rel_pos, T.minimisers))
+        even = np.ascontiguousarray(T.win_even, dtype=np.uint8)
+        rb, re, qae, ctg = (u32(x) for x in (rb, re, qae, read_contig))
+        seq_off = np.ascontiguousarray(seq_off, dtype=np.uint64); reads2 = np.ascontiguousarray(reads2, dtype=np.uint8)
+        n_ent = int(off[T.n_info])
+        cov = np.zeros(max(n_ent, 1), dtype=np.uint32); sup = np.zeros(max(n_ent, 1), dtype=np.uint32)
+        p = lambda a: a.ctypes.data_as(C.c_void_p)
+        rc = self.lib.hypo_host_minimizer_votes(C.c_uint32(cb.size), p(cb), p(rbase), p(even), p(ib), p(start), C.c_uint32(T.n_info), p(off), p(rel), p(mins),
+                                                C.c_uint32(rb.size), p(rb), p(re), p(qae), p(seq_off), p(reads2), p(ctg), p(cov), p(sup))
+        if rc != 0:
+            raise RuntimeError(f"hypo_host_minimizer_votes rc={rc}")
+        return cov[:n_ent], sup[:n_ent]

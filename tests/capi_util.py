@@ -1,4 +1,4 @@
-"""What the tests that call the C-ABI through ctypes share: the HypoArmsReads struct and a small set of exact-copy reads."""
+"""What the tests that call the C-ABI through ctypes share: the HypoArmsReads and HypoMegaWindows structs and a small set of exact-copy reads."""
 import ctypes as C
 
 import numpy as np
@@ -7,6 +7,11 @@ import numpy as np
 class ArmsReads(C.Structure):                      # HypoArmsReads, include/hypo_gpu.h
     _fields_ = [("n_alignments", C.c_uint32), ("rb", C.c_void_p), ("re", C.c_void_p), ("qae", C.c_void_p), ("seq_off", C.c_void_p),
                 ("reads2", C.c_void_p), ("reads2_bytes", C.c_uint64), ("cigar_off", C.c_void_p), ("cigar", C.c_void_p), ("file_rank", C.c_void_p)]
+
+
+class MegaWindows(C.Structure):                   # HypoMegaWindows, include/hypo_gpu.h
+    _fields_ = [("n_contigs", C.c_uint32), ("contig_base", C.c_void_p), ("reg_base", C.c_void_p), ("win_even", C.c_void_p), ("info_base", C.c_void_p),
+                ("start", C.c_void_p), ("n_info", C.c_uint32), ("mw_off", C.c_void_p), ("rel_pos", C.c_void_p), ("minimisers", C.c_void_p)]
 
 
 def ptr(a):

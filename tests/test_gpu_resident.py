@@ -6,6 +6,7 @@ import ctypes as C
 import numpy as np
 import pytest
 
+import votes_checker
 from hypo_amd import abi, capi, sim
 from capi_util import ArmsReads, exact_reads as _reads, ptr as _p
 
@@ -42,7 +43,10 @@ def test_kept_scan_and_kept_votes_equal_the_plain_entry_points(n_bases, k):
     assert lib.hypo_gpu_reads_upload(C.byref(A), _p(ctg), C.c_uint64(total)) == abi.HYPO_OK, lib.hypo_gpu_last_error()
     cov = np.zeros(ns, dtype=np.uint32); sup = np.zeros(ns, dtype=np.uint32)
     assert lib.hypo_gpu_support_kmers(C.c_uint32(k), C.c_uint64(ns), _p(spos), _p(kids), _p(cov), _p(sup)) == abi.HYPO_OK, lib.hypo_gpu_last_error()
-    assert cov.sum() > 0 and sup.sum() > 0
+    # ... and they are the votes of the reference's loop (tests/votes_checker.py), element for element
+    want_cov, want_sup = votes_checker.kmer_votes(k, spos, kids, rb, re, qae, seq_off, reads2)
+    assert want_cov.sum() > 0 and want_sup.sum() > 0
+    assert (cov == want_cov).all() and (sup == want_sup).all()
     # the same votes against the kept scan, results into page-locked memory
     ptr = C.c_void_p()
     assert lib.hypo_gpu_host_alloc(C.c_size_t(ns * 8), C.byref(ptr)) == abi.HYPO_OK and ptr.value
