@@ -19,6 +19,13 @@ HYPO_E_UNSUPPORTED = -7
 # hypo_gpu_kset_query_track: what hypo_amd.capi puts into the interval arrays before a call (no position or count is that large)
 TRACK_UNTOUCHED = 0xFFFFFFFFFFFFFFFF
 
+# hypo_gpu_kset_query_fixes (HYPO_KSET_MAX_FIX_REGION, HYPO_KSET_MAX_FIX_SPAN); hypo_amd.capi fills the outputs with the sentinels
+# before a call (no count and no candidate index is that large)
+KSET_MAX_FIX_REGION = 31
+KSET_MAX_FIX_SPAN = 2048
+FIXES_UNTOUCHED64 = 0xFFFFFFFFFFFFFFFF
+FIXES_UNTOUCHED32 = 0xFFFFFFFF
+
 # hypo_gpu_kset_counts_enable / _mark / _spectrum (HYPO_KSET_MAX_TEXTS, HYPO_KSET_SPECTRUM_BINS): hist[count * 5 + min(copies, 4)]
 KSET_MAX_TEXTS = 4
 KSET_SPECTRUM_ROWS, KSET_SPECTRUM_COLS = 256, 5

@@ -30,7 +30,7 @@ EXPORTS = [
     "hypo_gpu_kmer_count_begin", "hypo_gpu_kmer_count_add", "hypo_gpu_kmer_histogram", "hypo_gpu_solid_set_build",
     "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts",
     "hypo_gpu_kset_begin", "hypo_gpu_kset_add", "hypo_gpu_kset_size", "hypo_gpu_kset_query", "hypo_gpu_kset_end",
-    "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants", "hypo_gpu_kset_query_track",
+    "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants", "hypo_gpu_kset_query_track", "hypo_gpu_kset_query_fixes",
     "hypo_gpu_kset_counts_enable", "hypo_gpu_kset_mark", "hypo_gpu_kset_spectrum", "hypo_gpu_kset_min_count",
 ]
 KSET_SPAN_PIECE = 2048        # windows per piece of a long span (kset_kernel.hpp)
@@ -371,6 +371,35 @@ class HypoGpu:
         out = self.kset_query_track_rc(seqs_or_text, off, want, 0)
         if out[0] == abi.HYPO_E_WORKSPACE:
             out = self.kset_query_track_rc(seqs_or_text, off, want, int(out[3][-1]))
+        self._check(out[0])
+        return out[1:]
+
+    def kset_query_fixes_rc(self, data, lo, hi, c0, c1, cands=True):
+        """(return code, none_total u64[n], none_missing u64[n], best_cand u32[n], best_total u64[n], best_missing u64[n], zeros u32[n],
+        cand_total, cand_missing) of hypo_gpu_kset_query_fixes; nothing is checked here.  cand_*: u64[sum of 9 (c1 - c0) - 3] as far as
+        the regions are sane, None without `cands`.  Every output is filled with abi.FIXES_UNTOUCHED64 / 32 before the call."""
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        lo, hi, c0, c1 = (np.ascontiguousarray(x, dtype=np.uint64) for x in (lo, hi, c0, c1))
+        n = lo.size
+        assert hi.size == n and c0.size == n and c1.size == n
+        pad = lambda x, t: np.concatenate([x, np.zeros(1, t)])          # (an empty array still has an address)
+        w = c1.astype(np.int64) - c0.astype(np.int64)
+        n_cands = int(sum(9 * int(x) - 3 for x in w if 1 <= x <= abi.KSET_MAX_FIX_REGION))
+        u64 = lambda m: np.full(m + 1, abi.FIXES_UNTOUCHED64, np.uint64)
+        u32 = lambda m: np.full(m + 1, abi.FIXES_UNTOUCHED32, np.uint32)
+        nt, nm, bc, bt, bm, z = u64(n), u64(n), u32(n), u64(n), u64(n), u32(n)
+        ct, cm = (u64(n_cands), u64(n_cands)) if cands else (None, None)
+        rc = int(self.lib.hypo_gpu_kset_query_fixes(
+            _p(pad(a, np.uint8)), C.c_uint64(a.size), _p(pad(lo, np.uint64)), _p(pad(hi, np.uint64)), _p(pad(c0, np.uint64)), _p(pad(c1, np.uint64)), C.c_uint32(n),
+            _p(nt), _p(nm), _p(bc), _p(bt), _p(bm), _p(z), _p(ct) if cands else None, _p(cm) if cands else None))
+        return rc, nt[:n], nm[:n], bc[:n], bt[:n], bm[:n], z[:n], (ct[:n_cands] if cands else None), (cm[:n_cands] if cands else None)
+
+    def kset_query_fixes(self, data, lo, hi, c0, c1, cands=True):
+        """site s = data[lo[s]:hi[s]] with the region [c0[s], c1[s]) of w bytes; its 9 w - 3 candidates are the span as it is, then
+        every substitution, deletion and insertion of one base in the region (include/hypo_gpu.h has the order).  (none_total,
+        none_missing, best_cand, best_total, best_missing, zeros, cand_total, cand_missing): the unedited span's pair, the canonical
+        candidate with the fewest missing windows, how many canonical candidates miss nothing, and every candidate's pair."""
+        out = self.kset_query_fixes_rc(data, lo, hi, c0, c1, cands)
         self._check(out[0])
         return out[1:]
 

@@ -1533,6 +1533,69 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
     return HYPO_OK;
 }
 
+int hypo_gpu_kset_query_fixes(const char* bytes, uint64_t n_bytes, const uint64_t* lo, const uint64_t* hi, const uint64_t* c0, const uint64_t* c1, uint32_t n_sites,
+                              uint64_t* none_total, uint64_t* none_missing, uint32_t* best_cand, uint64_t* best_total, uint64_t* best_missing, uint32_t* zeros,
+                              uint64_t* cand_total, uint64_t* cand_missing) {
+    HYPO_KSET_ENTRY();
+    if (!n_sites) return HYPO_OK;
+    if (!bytes || !lo || !hi || !c0 || !c1 || !none_total || !none_missing || !best_cand || !best_total || !best_missing || !zeros) return fail(HYPO_E_INVALID, "NULL buffer");
+    if (!cand_total != !cand_missing) return fail(HYPO_E_INVALID, "cand_total and cand_missing are both given or both NULL");
+    static_assert(hypo::KSET_MAX_FIX_REGION == HYPO_KSET_MAX_FIX_REGION && hypo::KSET_MAX_FIX_SPAN == HYPO_KSET_MAX_FIX_SPAN, "the header's limits");
+    // everything is checked before a buffer is touched: the kernels trust what they are given
+    std::vector<uint32_t> len(n_sites), rc0(n_sites), w(n_sites), item_off((size_t)n_sites + 1);
+    uint64_t n_items = 0;
+    for (uint32_t s = 0; s < n_sites; ++s) {
+        if (!(lo[s] <= c0[s] && c0[s] < c1[s] && c1[s] <= hi[s] && hi[s] <= n_bytes))
+            return fail(HYPO_E_INVALID, "site %u: lo <= c0 < c1 <= hi <= n_bytes does not hold for [%llu, %llu) with the region [%llu, %llu) of %llu bytes", s,
+                        (unsigned long long)lo[s], (unsigned long long)hi[s], (unsigned long long)c0[s], (unsigned long long)c1[s], (unsigned long long)n_bytes);
+        if (c1[s] - c0[s] > hypo::KSET_MAX_FIX_REGION) return fail(HYPO_E_INVALID, "site %u: a region of %llu bytes, at most %u (HYPO_KSET_MAX_FIX_REGION)", s, (unsigned long long)(c1[s] - c0[s]), hypo::KSET_MAX_FIX_REGION);
+        if (hi[s] - lo[s] > hypo::KSET_MAX_FIX_SPAN) return fail(HYPO_E_INVALID, "site %u: a span of %llu bytes, at most %u (HYPO_KSET_MAX_FIX_SPAN)", s, (unsigned long long)(hi[s] - lo[s]), hypo::KSET_MAX_FIX_SPAN);
+        len[s] = (uint32_t)(hi[s] - lo[s]); rc0[s] = (uint32_t)(c0[s] - lo[s]); w[s] = (uint32_t)(c1[s] - c0[s]);
+        item_off[s] = (uint32_t)n_items;
+        n_items += 9ull * w[s] - 3;
+        if (n_items >= (1ull << 31)) return fail(HYPO_E_CAPACITY, "%llu candidates in one call (site %u): split the call", (unsigned long long)n_items, s);
+    }
+    item_off[n_sites] = (uint32_t)n_items;
+    const bool want_cands = cand_total != nullptr;
+    hipStream_t st = g_ctx.stream;
+    // ks.in: bytes.  ks.off: site_lo | site_len | site_c0 | site_w | item_off.  ks.res: item pairs | none_total | none_missing |
+    // best_total | best_missing | cand_total | cand_missing | best_cand | zeros.  Every section starts at a multiple of 256 bytes.
+    Carver co, cr;
+    const size_t o_lo = co.take((size_t)n_sites * 8), o_len = co.take((size_t)n_sites * 4), o_c0 = co.take((size_t)n_sites * 4), o_w = co.take((size_t)n_sites * 4),
+                 o_ioff = co.take(((size_t)n_sites + 1) * 4);
+    const size_t r_item = cr.take((size_t)n_items * 8), r_nt = cr.take((size_t)n_sites * 8), r_nm = cr.take((size_t)n_sites * 8), r_bt = cr.take((size_t)n_sites * 8),
+                 r_bm = cr.take((size_t)n_sites * 8), r_ct = cr.take(want_cands ? (size_t)n_items * 8 : 0), r_cm = cr.take(want_cands ? (size_t)n_items * 8 : 0),
+                 r_bc = cr.take((size_t)n_sites * 4), r_z = cr.take((size_t)n_sites * 4);
+    HIP_TRY(ks.in.alloc(n_bytes));
+    HIP_TRY(ks.off.alloc(co.at));
+    HIP_TRY(ks.res.alloc(cr.at));
+    char* d_off = (char*)ks.off.p; char* d_res = (char*)ks.res.p;
+    HIP_TRY(h2d(ks.in.p, bytes, n_bytes, st));
+    HIP_TRY(h2d(d_off + o_lo, lo, (size_t)n_sites * 8, st));
+    HIP_TRY(h2d(d_off + o_len, len.data(), (size_t)n_sites * 4, st));
+    HIP_TRY(h2d(d_off + o_c0, rc0.data(), (size_t)n_sites * 4, st));
+    HIP_TRY(h2d(d_off + o_w, w.data(), (size_t)n_sites * 4, st));
+    HIP_TRY(h2d(d_off + o_ioff, item_off.data(), item_off.size() * 4, st));
+    HIP_TRY(hypo::kset_fixes_run((const uint8_t*)ks.in.p, (const uint64_t*)(d_off + o_lo), (const uint32_t*)(d_off + o_len), (const uint32_t*)(d_off + o_c0),
+                                 (const uint32_t*)(d_off + o_w), (const uint32_t*)(d_off + o_ioff), n_sites, (uint32_t)n_items, ks.k, ks.table, ks.slots,
+                                 (uint2*)(d_res + r_item), (unsigned long long*)(d_res + r_nt), (unsigned long long*)(d_res + r_nm), (uint32_t*)(d_res + r_bc),
+                                 (unsigned long long*)(d_res + r_bt), (unsigned long long*)(d_res + r_bm), (uint32_t*)(d_res + r_z),
+                                 want_cands ? (unsigned long long*)(d_res + r_ct) : nullptr, want_cands ? (unsigned long long*)(d_res + r_cm) : nullptr, ks_group(),
+                                 ks.planes, ks.min_count, st));
+    HIP_TRY(d2h(none_total, d_res + r_nt, (size_t)n_sites * 8, st));
+    HIP_TRY(d2h(none_missing, d_res + r_nm, (size_t)n_sites * 8, st));
+    HIP_TRY(d2h(best_cand, d_res + r_bc, (size_t)n_sites * 4, st));
+    HIP_TRY(d2h(best_total, d_res + r_bt, (size_t)n_sites * 8, st));
+    HIP_TRY(d2h(best_missing, d_res + r_bm, (size_t)n_sites * 8, st));
+    HIP_TRY(d2h(zeros, d_res + r_z, (size_t)n_sites * 4, st));
+    if (want_cands) {
+        HIP_TRY(d2h(cand_total, d_res + r_ct, (size_t)n_items * 8, st));
+        HIP_TRY(d2h(cand_missing, d_res + r_cm, (size_t)n_items * 8, st));
+    }
+    HIP_TRY(hipStreamSynchronize(st));
+    return HYPO_OK;
+}
+
 // ---- read counts, copy numbers and the spectrum (hypo --qv-spectra) ---------------------------------------------------------------
 int hypo_gpu_kset_counts_enable(uint32_t n_texts) {
     HYPO_KSET_ENTRY();

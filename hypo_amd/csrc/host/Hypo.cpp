@@ -4,6 +4,7 @@
 #include "SolidBuild.hpp"
 #include "EditVcf.hpp"
 #include "KmerGuard.hpp"
+#include "KmerFix.hpp"
 #include "QvReport.hpp"
 #include "SpectraReport.hpp"
 #include <ctime>
@@ -17,18 +18,19 @@
 namespace hypo {
 extern std::atomic<uint64_t> g_stage_counters[5];      // host/Contig.cpp
 
-// --vcf, --qv, --qv-bed, --qv-spectra, --kmer-guard: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
+// --vcf, --qv, --qv-bed, --qv-spectra, --kmer-guard, --kmer-fix: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
 struct Extras {
     EditScriptsFn edit_fn = nullptr, guard_edit_fn = nullptr;
     QvReport qv;
     KmerGuard guard;
     SpectraReport spectra;
-    bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false;
+    KmerFix fix;
+    bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false, fix_on = false;
     uint32_t min_given = 1;                                // --qv-min-count: 1 = off, 0 = the valley
     bool min_on() const { return min_given != 1; }
     bool ask_on = false;                                   // --qv or --qv-bed: every contig's texts are put to the set
     bool text_on = false;                                  // ... or --qv-spectra: every contig's texts are needed as strings
-    bool set_on = false;                                   // ... or --kmer-guard: the set is built
+    bool set_on = false;                                   // ... or --kmer-guard or --kmer-fix: the set is built
     ReadSink qv_sink;                                      // (holds a pointer to qv: an Extras stays where it is)
     VcfStats vstats;
     Extras() = default; Extras(const Extras&) = delete;
@@ -159,6 +161,18 @@ void Hypo::polish() {
 
 // ---- once per run, before the batches ----------------------------------------------------------------------------------------
 void Hypo::bind_extras(Extras& ex) {
+    // --kmer-fix: the fixes query and the track query, bound by name and only under the flag, and the set they ask.  Checked
+    // first: its error names what is lacking.
+    ex.fix_on = !_cFlags.kmer_fix_filename.empty();
+    if (ex.fix_on) {
+        ex.fix.set_k(_cFlags.qv_k);
+        const bool have_all = ex.fix.bind(), have_set = QvReport().bind();
+        if (!have_all || !have_set) {
+            std::fprintf(stderr, "[Hypo::Hypo] Error: --kmer-fix needs%s%s%s, which the device library does not provide\n", ex.fix.have_fixes() ? "" : " hypo_gpu_kset_query_fixes",
+                         ex.fix.have_track() ? "" : " hypo_gpu_kset_query_track", have_set ? "" : " hypo_gpu_kset_begin / _add / _size / _end");
+            std::exit(1);
+        }
+    }
     // --qv-min-count: counts on the set and the threshold of its queries, bound by name and only under the flag (1 is the run
     // without it).  Checked first: its error names them.
     ex.min_given = _cFlags.qv_min_count;
@@ -210,8 +224,8 @@ void Hypo::bind_extras(Extras& ex) {
     }
     ex.ask_on = ex.qv_on || ex.bed_on;
     ex.text_on = ex.ask_on || ex.spectra_on;
-    ex.set_on = ex.text_on || ex.guard_on;
-    if (ex.guard_on && !ex.ask_on) (void)ex.qv.bind();   // (the guard's check above found the entry points)
+    ex.set_on = ex.text_on || ex.guard_on || ex.fix_on;
+    if ((ex.guard_on || ex.fix_on) && !ex.ask_on) (void)ex.qv.bind();   // (the guard's or the fix's check above found the entry points)
     if (ex.set_on) {
         // (sized for one k-mer per genome position; what the read errors add makes it grow)
         const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
@@ -736,9 +750,28 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
             writer_fatal("edit scripts");
     }
     // --qv: the draft and the polished text of every contig of the batch go to the k-mer set in one query on context 0
-    int qrc = ex.text_on ? hypo_gpu_use_device(0) : HYPO_OK;
+    int qrc = ex.text_on || ex.fix_on ? hypo_gpu_use_device(0) : HYPO_OK;
+    // --kmer-fix: every contig's text goes through the fixes first; what comes back is written and handed on in its place
+    const KmerFix::Emit write_fixed = [&](uint32_t c, const std::string& draft, const std::string& text) {
+        ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;
+        return ex.texts(c, draft, text);
+    };
     // --kmer-guard: the batch's records are made first, their clusters judged by the set, and every contig is written as
     // its draft with the accepted records applied
+    if (ex.guard_on && ex.fix_on) {
+        VcfStats unused;
+        int grc = ex.guard.run_batch(_contigs, initial_cid, final_cid, *edits, ex.edit_fn ? ex.vstats : unused,
+            [&](uint32_t c, const std::string& draft, const std::string& text, const VcfContigRecords& recs, const std::vector<uint8_t>& rejected) {
+                if (ex.edit_fn) vcf_write_records(vfile, *_contigs[c], recs, &rejected);
+                const std::string name = _contigs[c]->get_name();
+                _contigs[c]->release_after_output();
+                return ex.fix.push(c, name, ex.text_on ? draft : std::string(), text, write_fixed);
+            });
+        if (grc == HYPO_OK) grc = ex.fix.flush(write_fixed);
+        if (grc == HYPO_OK) qrc = ex.texts_flush();
+        if (grc != HYPO_OK || qrc != HYPO_OK) writer_fatal(grc != HYPO_OK ? "k-mer guard / k-mer fix" : "k-mer set query");
+        return;
+    }
     if (ex.guard_on) {
         VcfStats unused;
         const int grc = ex.guard.run_batch(_contigs, initial_cid, final_cid, *edits, ex.edit_fn ? ex.vstats : unused,
@@ -750,6 +783,20 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
             });
         if (grc == HYPO_OK) qrc = ex.texts_flush();
         if (grc != HYPO_OK || qrc != HYPO_OK) writer_fatal(grc != HYPO_OK ? "k-mer guard" : "k-mer set query");
+        return;
+    }
+    if (ex.fix_on) {
+        for (uint32_t c = initial_cid; c < final_cid && qrc == HYPO_OK; ++c) {
+            std::string text = _contigs[c]->polished_text();
+            std::string draft = ex.text_on ? _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()) : std::string();
+            if (edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, ex.vstats);
+            const std::string name = _contigs[c]->get_name();
+            _contigs[c]->release_after_output();
+            qrc = ex.fix.push(c, name, std::move(draft), std::move(text), write_fixed);
+        }
+        if (qrc == HYPO_OK) qrc = ex.fix.flush(write_fixed);
+        if (qrc == HYPO_OK) qrc = ex.texts_flush();
+        if (qrc != HYPO_OK) writer_fatal("k-mer fix / k-mer set query");
         return;
     }
     for (uint32_t c = initial_cid; c < final_cid; ++c) {
@@ -776,6 +823,7 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         if (hypo_gpu_use_device(0) != HYPO_OK || ex.spectra.fetch(ex.qv.k(), ex.qv.n_distinct(), _cFlags.qv_reliable_min) != HYPO_OK) ex.qv_fail("hypo_gpu_kset_spectrum");
         ex.spectra.write(out.open_spectra(_cFlags.qv_spectra_filename));
     }
+    if (ex.fix_on) ex.fix.write(out.open_fixes(_cFlags.kmer_fix_filename));
     // --qv: the table is formatted once, closed and checked like the others; the set has answered its last query
     if (ex.set_on) ex.qv.end();
     if (ex.qv_on) {
@@ -812,6 +860,12 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         if (w == RunOutputs::SPECTRA)
             std::fprintf(stdout, "[Hypo::Hypo] Info: spectra %s (k = %u, reliable >= %u): completeness draft %s, polished %s\n", _cFlags.qv_spectra_filename.c_str(), ex.spectra.k(),
                          ex.spectra.threshold(), ex.spectra.completeness(SpectraReport::DRAFT).c_str(), ex.spectra.completeness(SpectraReport::POLISHED).c_str());
+        if (w == RunOutputs::FIXES) {
+            const KmerFix::Stats& fs = ex.fix.stats();
+            std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer fix %s (k = %u): %llu intervals, %llu sites, %llu fixed (%llu sub, %llu del, %llu ins), %llu ambiguous, %llu missing k-mers removed\n",
+                         _cFlags.kmer_fix_filename.c_str(), ex.fix.k(), (unsigned long long)fs.intervals, (unsigned long long)fs.sites, (unsigned long long)fs.fixed,
+                         (unsigned long long)fs.sub, (unsigned long long)fs.del, (unsigned long long)fs.ins, (unsigned long long)fs.ambiguous, (unsigned long long)fs.removed);
+        }
         if (w == RunOutputs::BED) {
             const QvReport::TrackSums ts = ex.qv.track_sums();
             std::fprintf(stdout, "[Hypo::Hypo] Info: QV track %s (k = %u): %llu intervals covering %llu bases, %llu missing k-mers\n", _cFlags.qv_bed_filename.c_str(), ex.qv.k(),

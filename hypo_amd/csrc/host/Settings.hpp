@@ -35,6 +35,7 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     std::string qv_spectra_filename;       // new, opt-in: --qv-spectra <file> (copy-number spectrum and k-mer completeness of the draft and the polished text)
     uint32_t qv_reliable_min = 0;          // new, opt-in: --qv-reliable-min (1..255: the least read count of a reliable k-mer; 0 = the valley of the read histogram)
     uint32_t qv_min_count = 1;             // new, opt-in: --qv-min-count (1..255, 0 = valley: a read k-mer counts for --qv, --qv-bed and the guards when the reads have it this often; 1 = presence, the run without the flag)
+    std::string kmer_fix_filename;         // new, opt-in: --kmer-fix <file> (one pass of single-base fixes the read k-mers pin down, listed in the file)
     uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
 };
 

@@ -33,7 +33,8 @@ const struct option long_options[] = {
     {"qv-mem", required_argument, nullptr, 1010}, {"kmer-guard", no_argument, nullptr, 1011},
     {"guard-records", no_argument, nullptr, 1012}, {"guard-records-max", required_argument, nullptr, 1013},
     {"qv-bed", required_argument, nullptr, 1014}, {"qv-spectra", required_argument, nullptr, 1015},
-    {"qv-reliable-min", required_argument, nullptr, 1016}, {"qv-min-count", required_argument, nullptr, 1017}, {nullptr, 0, nullptr, 0}};
+    {"qv-reliable-min", required_argument, nullptr, 1016}, {"qv-min-count", required_argument, nullptr, 1017},
+    {"kmer-fix", required_argument, nullptr, 1018}, {nullptr, 0, nullptr, 0}};
 
 // Same layout as the reference's usage() (src/main.cpp:363-430): "Usage: hypo <args>", the mandatory block, the optional
 // block, every flag as "-x, --long <type>" followed by what it does and its default.  The wording is this build's own.
@@ -78,6 +79,7 @@ void usage() {
         {"    --qv-spectra <str>", "[MI355X build] Also write the copy-number spectrum and the k-mer completeness of the draft and of the polished text (with --kmer-guard the guarded text) as a tab-separated file: the k-mer set of --qv also counts how often the short reads contain every k-mer, and per read multiplicity 1 to 255 the file tells how many distinct read k-mers the text contains 0, 1, 2, 3 and 4 or more times (Merqury's spectra-cn: a collapsed or duplicated stretch moves k-mers between the columns). Completeness is the share of the reliable read k-mers (seen at least --qv-reliable-min times) that the text contains; asm_only_windows are the text's k-mers no read contains, polished_missing of --qv. Uses --qv-k and --qv-mem, with or without --qv, --qv-bed, --vcf and --kmer-guard; counted and compared on the device.", "no spectra"},
         {"    --qv-reliable-min <int>", "[MI355X build] Least number of times the short reads must contain a k-mer for it to count as reliable in the completeness of --qv-spectra, 1 to 255.", "the valley of the read k-mer histogram: the smallest multiplicity from 2 on at which it stops falling"},
         {"    --qv-min-count <int|valley>", "[MI355X build] Count a read k-mer only when the short reads contain it at least this often, 1 to 255, or `valley`: the valley of the read k-mer histogram, the default of --qv-reliable-min. A k-mer seen fewer times is mostly a sequencing error and then counts as missing wherever the reads are asked: in the missing columns and QVs of --qv, the intervals of --qv-bed, and the decisions of --kmer-guard and --guard-records. Needs at least one of those four; 1 is the run without the flag. The k-mer set then counts as for --qv-spectra (one more byte a slot under --qv-mem), whose file does not change.", "1: a k-mer seen once is present"},
+        {"    --kmer-fix <str>", "[MI355X build] Make one pass of single-base fixes over the text that would otherwise be written (with --kmer-guard the guarded text), where the k-mers of the short reads pin an isolated error down: a stretch of at most 2k - 1 bases in which every k-mer is one no read contains, at least k - 1 bases from the next such stretch and not at a contig end, is tried with every substitution, deletion and insertion of one base at the positions all its k-mers share, and fixed when exactly one of the edited texts lacks no k-mer of the reads; two such texts (a heterozygous base, a read error) leave it alone. The file lists the fixes, tab-separated: contig, pos (0-based, in the text before the fixes), kind (sub, del, ins), ref, alt, and the missing k-mers the fix removes. --qv, --qv-bed and --qv-spectra then describe the fixed text; --vcf still describes the text before the fixes. Uses the k-mer set of --qv (--qv-k, --qv-mem, --qv-min-count) with or without the other flags; the edits are tried on the device.", "no fixes"},
         {"-h, --help", "Print the usage.", nullptr}};
     std::printf("\n Usage: hypo <args>\n\n ** Mandatory args:\n");
     for (const auto& e : mandatory) std::printf("\t%s\n\t%s\n\n", e.flag, e.what);
@@ -214,6 +216,7 @@ int main(int argc, char** argv) {
                 if (!valley && (end == optarg || *end || v < 1 || v > 255)) { std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-min-count must be between 1 and 255 (the k-mer set counts up to 255) or `valley` %s!\n", optarg); std::exit(1); }
                 flags.qv_min_count = valley ? 0 : (uint32_t)v; break;                // (0: the valley, found when the reads are in)
             }
+            case 1018: flags.kmer_fix_filename = optarg; break;
             case 1002: {
                 flags.devices.clear();
                 for (const char* c = optarg; *c;) { flags.devices.push_back(std::atoi(c)); while (*c && *c != ',') ++c; if (*c == ',') ++c; }
@@ -222,8 +225,8 @@ int main(int argc, char** argv) {
             default: usage(); return 0;                                    // -h and unknown options alike (src/main.cpp:302-304)
         }
     }
-    if (flags.qv_min_count != 1 && flags.qv_filename.empty() && flags.qv_bed_filename.empty() && !flags.kmer_guard) {   // (1 is the run without the flag)
-        std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-min-count changes what --qv, --qv-bed, --kmer-guard and --guard-records ask the reads: it needs at least one of them!\n");
+    if (flags.qv_min_count != 1 && flags.qv_filename.empty() && flags.qv_bed_filename.empty() && !flags.kmer_guard && flags.kmer_fix_filename.empty()) {   // (1 is the run without the flag)
+        std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-min-count changes what --qv, --qv-bed, --kmer-guard, --guard-records and --kmer-fix ask the reads: it needs at least one of them!\n");
         std::exit(1);
     }
     if (!(is_sr && is_draft && is_size && is_bamsr && is_cov)) {

@@ -17,6 +17,8 @@
 //   * kset_spans_kernel / kset_variants_kernel (below, with comments of their own): many short spans, and every subset of a few
 //     edits of many short sites, a group of 32 or 64 lanes per item; read-only probes, no LDS, no atomics.  Both are ks_group_scan
 //     with another source of bytes.
+//   * kset_fixes_kernel / kset_fixes_reduce_kernel (below, with comments of their own; hypo --kmer-fix): every one-base edit of many
+//     short regions, a group per candidate, ks_group_scan once more, and a lane per site that picks the best candidate.
 //   * counts (hypo --qv-spectra; further down, with comments of their own): a count byte and up to four copy bytes per slot in planes
 //     beside the table, a saturating byte add that serves both, and the counted variants of the insert and rehash kernels, the mark
 //     kernel (the query body with a probe that returns the slot) and the spectrum kernel.
@@ -740,6 +742,141 @@ hipError_t kset_variants_run(const uint8_t* bytes, const uint8_t* alts, const ui
     if (e != hipSuccess) return e;
     kset_variants_reduce_kernel<<<dim3((n_sites + KS_THREADS - 1) / KS_THREADS), dim3(KS_THREADS), 0, st>>>(items, item_res, site_item, var_off, n_sites, best_mask, best_total,
                                                                                                               best_missing, var_total, var_missing);
+    return hipGetLastError();
+}
+
+// ---- every one-base edit of a short region (hypo --kmer-fix; DESIGN.md "k-mer fix") -----------------------------------------------------
+// An item is ONE candidate of a site: item i belongs to the site s with item_off[s] <= i < item_off[s + 1] (a binary search; a site
+// with a region of w bytes has 9 w - 3 candidates) and j = i - item_off[s] names its edit by arithmetic, in the order of
+// ks_fix_edit.  The candidate's text exists nowhere: byte x of it is the edit's base where x is the edit's position p, and else
+// byte x of the span, one further on from p for a deletion, one back behind p for an insertion.  A lane loads one such byte a
+// pass; the rest is ks_group_scan, as for the spans.  No LDS, no atomics, no scratch; item i's pair goes to out[i].
+// Bounds: the caller checked lo <= c0 < c1 <= hi <= n_bytes, hi - lo <= KSET_MAX_FIX_SPAN and c1 - c0 <= KSET_MAX_FIX_REGION for
+// every site.  With L = hi - lo and p in [c0 - lo, c1 - lo): a substitution has L bytes and reads lo + x, x < L; a deletion has
+// L - 1 and reads lo + x + 1 <= lo + L - 1; an insertion has L + 1 and reads lo + x - 1 <= lo + L - 1 behind p, lo + x < lo + p
+// in front of it.  So every read is inside [lo, hi).  A text has at most 2049 bytes: at most 2049 / G + 1 passes.  items / out
+// are indexed below n_items = item_off[n_sites], sites below n_sites (the search), the probe is ks_contains.
+enum { KS_FIX_NONE = 0, KS_FIX_SUB = 1, KS_FIX_DEL = 2, KS_FIX_INS = 3 };
+__device__ __forceinline__ uint32_t ks_base_char(uint32_t base) { return (0x54474341u >> (8 * base)) & 0xffu; }   // 'A' 'C' 'G' 'T'
+// candidate j < 9 w - 3 of a region of w bytes: its kind, its position relative to the region's first byte, its base (0..3)
+__device__ __forceinline__ void ks_fix_edit(uint32_t j, uint32_t w, uint32_t& kind, uint32_t& at, uint32_t& base) {
+    kind = KS_FIX_NONE; at = 0; base = 0;
+    if (!j) return;
+    --j;
+    if (j < 4 * w) { kind = KS_FIX_SUB; at = j >> 2; base = j & 3u; return; }
+    j -= 4 * w;
+    if (j < w) { kind = KS_FIX_DEL; at = j; return; }
+    j -= w;
+    kind = KS_FIX_INS; at = 1 + (j >> 2); base = j & 3u;
+}
+
+template <int G, bool MIN>
+__device__ __forceinline__ void ks_fixes_body(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ site_lo, const uint32_t* __restrict__ site_len,
+                                              const uint32_t* __restrict__ site_c0, const uint32_t* __restrict__ site_w,
+                                              const uint32_t* __restrict__ item_off, uint32_t n_sites, uint32_t n_items, uint32_t k,
+                                              const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out,
+                                              const uint8_t* __restrict__ counts, uint32_t t) {
+    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
+    const bool have = item < n_items;
+    uint64_t lo = 0;
+    uint32_t len = 0, p = 0xffffffffu, ch = 0, kind = KS_FIX_NONE;
+    if (have) {
+        uint32_t a = 0, b = n_sites;                            // the last site with item_off[site] <= item (item < item_off[n_sites])
+        while (b - a > 1) { const uint32_t mid = a + (b - a) / 2; if (item_off[mid] <= (uint32_t)item) a = mid; else b = mid; }
+        uint32_t at, base;
+        ks_fix_edit((uint32_t)item - item_off[a], site_w[a], kind, at, base);
+        lo = site_lo[a];
+        len = site_len[a] + (kind == KS_FIX_INS ? 1u : 0u) - (kind == KS_FIX_DEL ? 1u : 0u);
+        if (kind != KS_FIX_NONE) p = site_c0[a] + at;
+        ch = ks_base_char(base);
+    }
+    const bool put = kind == KS_FIX_SUB || kind == KS_FIX_INS;  // the byte at p is the edit's base
+    const uint32_t skip = kind == KS_FIX_DEL ? 1u : kind == KS_FIX_INS ? 0xffffffffu : 0u;   // from p on: + 1, - 1 or nothing
+    ks_group_scan<G, MIN>([&](uint32_t x) { return put && x == p ? ch : (uint32_t)bytes[lo + (uint32_t)(x + (x >= p ? skip : 0u))]; }, have, len, k, table, slots, out, item,
+                          counts, t);
+}
+
+template <int G>
+__global__ void __launch_bounds__(KS_THREADS) kset_fixes_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ site_lo,
+                                                                 const uint32_t* __restrict__ site_len, const uint32_t* __restrict__ site_c0,
+                                                                 const uint32_t* __restrict__ site_w, const uint32_t* __restrict__ item_off,
+                                                                 uint32_t n_sites, uint32_t n_items, uint32_t k, const uint64_t* __restrict__ table,
+                                                                 uint64_t slots, uint2* __restrict__ out) {
+    ks_fixes_body<G, false>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, out, nullptr, 1);
+}
+
+// kset_fixes_kernel against R_t (hypo --qv-min-count; the section "a least count" above)
+template <int G>
+__global__ void __launch_bounds__(KS_THREADS) kset_fixes_min_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ site_lo,
+                                                                     const uint32_t* __restrict__ site_len, const uint32_t* __restrict__ site_c0,
+                                                                     const uint32_t* __restrict__ site_w, const uint32_t* __restrict__ item_off,
+                                                                     uint32_t n_sites, uint32_t n_items, uint32_t k, const uint64_t* __restrict__ table,
+                                                                     uint64_t slots, uint2* __restrict__ out, const uint8_t* __restrict__ counts, uint32_t t) {
+    ks_fixes_body<G, true>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, out, counts, t);
+}
+
+__device__ __forceinline__ uint32_t ks_upper(uint32_t c) { return c >= 'a' && c <= 'z' ? c - 32u : c; }
+
+// One lane per site walks the site's candidates in order.  A candidate is CANONICAL when no earlier one and not the unedited span
+// spells the same text, which the region's own bytes decide: a substitution that changes the base, a deletion of the first base of
+// a run (or at the region's start), an insertion that does not repeat the base in front of it (or right behind the region's
+// start).  best_*: the canonical candidate with the fewest missing windows, the first among equals; zeros: the canonical
+// candidates with none missing.  cand_total / cand_missing (NULL or both): every candidate's pair at item_off[site] + j.
+// Bounds: res / cand_* below item_off[n_sites] = n_items, the six per-site arrays below n_sites, bytes at [c0, c1) of the site only
+// (the byte in front of position q is read for q > c0 alone).
+__global__ void __launch_bounds__(KS_THREADS) kset_fixes_reduce_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ site_lo,
+                                                                        const uint32_t* __restrict__ site_c0, const uint32_t* __restrict__ site_w,
+                                                                        const uint32_t* __restrict__ item_off, const uint2* __restrict__ res,
+                                                                        uint32_t n_sites, unsigned long long* __restrict__ none_total,
+                                                                        unsigned long long* __restrict__ none_missing, uint32_t* __restrict__ best_cand,
+                                                                        unsigned long long* __restrict__ best_total, unsigned long long* __restrict__ best_missing,
+                                                                        uint32_t* __restrict__ zeros, unsigned long long* __restrict__ cand_total,
+                                                                        unsigned long long* __restrict__ cand_missing) {
+    const uint64_t s = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x;
+    if (s >= n_sites) return;
+    const uint32_t i0 = item_off[s], w = site_w[s], n = 9 * w - 3;
+    const uint8_t* reg = bytes + site_lo[s] + site_c0[s];       // the region's w bytes
+    uint32_t bc = 0, nz = 0;
+    unsigned long long bt = 0, bm = 0;
+    bool first = true;
+    for (uint32_t j = 0; j < n; ++j) {
+        const uint2 r = res[i0 + j];
+        if (cand_total) { cand_total[(uint64_t)i0 + j] = r.x; cand_missing[(uint64_t)i0 + j] = r.y; }
+        if (!j) { none_total[s] = r.x; none_missing[s] = r.y; continue; }
+        uint32_t kind, at, base;
+        ks_fix_edit(j, w, kind, at, base);
+        const uint32_t b = ks_base_char(base);
+        bool canon;
+        if (kind == KS_FIX_SUB) canon = ks_upper(reg[at]) != b;
+        else if (kind == KS_FIX_DEL) canon = at == 0 || ks_upper(reg[at - 1]) != ks_upper(reg[at]);
+        else canon = at == 1 || ks_upper(reg[at - 1]) != b;
+        if (!canon) continue;
+        if (!r.y) ++nz;
+        if (first || r.y < bm) { bc = j; bt = r.x; bm = r.y; first = false; }
+    }
+    best_cand[s] = bc; best_total[s] = bt; best_missing[s] = bm; zeros[s] = nz;
+}
+
+hipError_t kset_fixes_run(const uint8_t* bytes, const uint64_t* site_lo, const uint32_t* site_len, const uint32_t* site_c0, const uint32_t* site_w,
+                          const uint32_t* item_off, uint32_t n_sites, uint32_t n_items, uint32_t k, const uint64_t* table, uint64_t slots, uint2* item_res,
+                          unsigned long long* none_total, unsigned long long* none_missing, uint32_t* best_cand, unsigned long long* best_total,
+                          unsigned long long* best_missing, uint32_t* zeros, unsigned long long* cand_total, unsigned long long* cand_missing, int group,
+                          const uint32_t* planes, uint32_t min_count, hipStream_t st) {
+    if (!n_sites || !n_items) return hipSuccess;
+    const uint32_t per_block = (uint32_t)KS_THREADS / (uint32_t)group;
+    const uint32_t blocks = (n_items + per_block - 1) / per_block;
+    const uint8_t* counts = (const uint8_t*)planes;
+    if (min_count > 1 && group == 32)
+        kset_fixes_min_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, item_res, counts, min_count);
+    else if (min_count > 1)
+        kset_fixes_min_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, item_res, counts, min_count);
+    else if (group == 32) kset_fixes_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, item_res);
+    else kset_fixes_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, item_res);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    kset_fixes_reduce_kernel<<<dim3((n_sites + KS_THREADS - 1) / KS_THREADS), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_c0, site_w, item_off, item_res, n_sites, none_total,
+                                                                                                           none_missing, best_cand, best_total, best_missing, zeros,
+                                                                                                           cand_total, cand_missing);
     return hipGetLastError();
 }
 

@@ -82,4 +82,20 @@ hipError_t kset_variants_run(const uint8_t* bytes, const uint8_t* alts, const ui
                              unsigned long long* var_total, unsigned long long* var_missing, int group, const uint32_t* planes, uint32_t min_count,
                              hipStream_t st);
 
+// Every one-base edit of n_sites short regions (hypo --kmer-fix; DESIGN.md "k-mer fix"): site s is the span bytes[site_lo[s],
+// site_lo[s] + site_len[s]) with the region of site_w[s] bytes that starts site_c0[s] bytes into it.  Its 9 w - 3 candidates, in
+// this order: the span as it is; sub(p, b), p ascending over the region, b in ACGT order; del(p), p ascending; ins(p, b), b put in
+// front of p, p ascending from the region's second byte.  item_off[s] = the candidates of the sites before s (n_sites + 1 entries,
+// n_items = item_off[n_sites]); item_res: n_items pairs of work space.  none_*: the unedited span's pair; best_*: the canonical
+// candidate (see the reduce kernel) with the fewest missing windows, the first among equals; zeros: the canonical candidates with
+// none missing; cand_total / cand_missing (both or neither): every candidate's pair at item_off[s] + j.  The caller has checked every
+// range (see the bounds comment of the kernels).
+constexpr uint32_t KSET_MAX_FIX_REGION = 31;
+constexpr uint32_t KSET_MAX_FIX_SPAN = 2048;
+hipError_t kset_fixes_run(const uint8_t* bytes, const uint64_t* site_lo, const uint32_t* site_len, const uint32_t* site_c0, const uint32_t* site_w,
+                          const uint32_t* item_off, uint32_t n_sites, uint32_t n_items, uint32_t k, const uint64_t* table, uint64_t slots, uint2* item_res,
+                          unsigned long long* none_total, unsigned long long* none_missing, uint32_t* best_cand, unsigned long long* best_total,
+                          unsigned long long* best_missing, uint32_t* zeros, unsigned long long* cand_total, unsigned long long* cand_missing, int group,
+                          const uint32_t* planes, uint32_t min_count, hipStream_t st);
+
 }  // namespace hypo

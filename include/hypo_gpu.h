@@ -466,6 +466,30 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
 int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n_seqs, const uint8_t* want /* may be NULL */,
     uint64_t* total, uint64_t* missing, uint64_t* iv_off /* n_seqs + 1 */,
     uint64_t* iv_start, uint64_t* iv_end, uint64_t* iv_missing, uint64_t iv_cap);
+/* Every one-base edit of many short regions against the set (hypo --kmer-fix; DESIGN.md "k-mer fix").  Additive to ABI 11: callers
+ * bind it by name.  Site s is the span bytes[lo[s], hi[s]) with the region [c0[s], c1[s]) inside it, w = c1 - c0 bytes wide.  It has
+ * 9 w - 3 candidates, in this order: index 0 the span as it is; then sub(p, b), p ascending over the region, b in ACGT order (4 w);
+ * then del(p), p ascending over the region (w); then ins(p, b), b put in front of p, p ascending over (c0, c1), b in ACGT order
+ * (4 (w - 1)).  Substituted and inserted bytes are upper case.  A candidate's total / missing are those of hypo_gpu_kset_query for
+ * the span with that one edit (no window crosses the span's ends; a window holding a non-base byte is no window); the texts are
+ * never built.  Different candidates can spell one text; with bases compared case-blind a candidate is CANONICAL when it is
+ * sub(p, b) and upper(bytes[p]) != b, or del(p) and p == c0 or upper(bytes[p - 1]) != upper(bytes[p]), or ins(p, b) and p == c0 + 1
+ * or upper(bytes[p - 1]) != b; index 0 is not.  Distinct canonical candidates have distinct texts, and every other candidate's text
+ * is that of index 0 or of a canonical one.  none_total[s] / none_missing[s]: the pair of index 0.  best_cand[s]: the index of the
+ * canonical candidate with the fewest missing windows, the first in order among equals; best_total[s] / best_missing[s]: its pair.
+ * zeros[s]: the canonical candidates with no missing window.  cand_total / cand_missing (both given or both NULL) receive every
+ * candidate's pair, site s at the sum of 9 w - 3 over the sites before it.  Sites may overlap, repeat and come in any order; the
+ * answers depend on the input and the set alone.  HYPO_E_INVALID: lo <= c0 < c1 <= hi <= n_bytes violated, c1 - c0 above
+ * HYPO_KSET_MAX_FIX_REGION, hi - lo above HYPO_KSET_MAX_FIX_SPAN, a NULL required pointer with n_sites > 0, one of cand_* without
+ * the other, no set (as hypo_gpu_kset_query); a refused call changes nothing.  n_sites == 0 touches nothing.  Synchronous, on the
+ * calling thread's context. */
+#define HYPO_KSET_MAX_FIX_REGION 31
+#define HYPO_KSET_MAX_FIX_SPAN 2048
+int hypo_gpu_kset_query_fixes(const char* bytes, uint64_t n_bytes, const uint64_t* lo, const uint64_t* hi,
+                              const uint64_t* c0, const uint64_t* c1, uint32_t n_sites,
+                              uint64_t* none_total, uint64_t* none_missing, uint32_t* best_cand, uint64_t* best_total,
+                              uint64_t* best_missing, uint32_t* zeros,
+                              uint64_t* cand_total /* may be NULL */, uint64_t* cand_missing /* may be NULL */);
 
 /* Read k-mer counts and copy numbers on the set (hypo --qv-spectra; DESIGN.md "k-mer spectra").  Additive to ABI 11: callers bind
  * the three by name.  Presence, and with it every answer of the query entry points above, is what it is without them.
@@ -493,7 +517,7 @@ int hypo_gpu_kset_mark(uint32_t text, const char* bytes, const uint64_t* off, ui
 int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist);
 /* A least count for the queries (hypo --qv-min-count; DESIGN.md "k-mer min count").  Additive to ABI 11: callers bind it by name.
  * R_t = the k-mers of the set whose count (hypo_gpu_kset_counts_enable) is at least t; R_1 is the set.  From the next call on
- * hypo_gpu_kset_query, _query_spans, _query_variants and _query_track answer against R_t: a window whose k-mer the reads contain
+ * hypo_gpu_kset_query, _query_spans, _query_variants, _query_track and _query_fixes answer against R_t: a window whose k-mer the reads contain
  * fewer than t times is missing, and everything those entry points derive from "missing" (intervals, best masks) follows.  The
  * threshold is applied when a query runs, to the counts of that moment: it may be set any number of times, before or after adds
  * and marks, it does not close the set, and hypo_gpu_kset_add, _size, _mark and _spectrum do not know of it.  hypo_gpu_kset_begin
