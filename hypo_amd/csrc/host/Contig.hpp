@@ -73,6 +73,7 @@ public:
     friend class Alignment;
     friend class DeviceArms;
     friend struct VoteTables;                               // host_capi.cpp: fills the tables of the vote loops from flat arrays (tests)
+    friend struct ArmTables;                                // host_capi.cpp: the same for the tables of arm selection
 
     // scan results (Contig::_solid_pos / _kmerinfo[i]->kid)
     uint64_t get_num_solid() const { return _n_solid; }

@@ -1,5 +1,6 @@
 // host_capi.cpp — C entry points over the C++ host mirror so that tests can drive it like the reference's
 // own classes (same call sequence as oracle/ref_harness.cpp uses on the real reference).
+#include <cstdio>
 #include <cstring>
 #include <memory>
 #include <string>
@@ -47,9 +48,103 @@ struct VoteTables {
         }
     }
 };
+
+// What Alignment::find_short_arms / find_long_arms and Contig::fill_short_windows / fill_long_windows read of a Contig, put there from
+// the flat arrays of HypoArmsRegions (include/hypo_gpu.h) instead of by divide_into_regions / prepare_long_windows.
+struct ArmTables {
+    // SHORT: _reg_pos / _reg_type / _reg_info / _anchor_kmers and a SHORT Window per region that is neither SR nor MSR
+    static void set_short(Contig& c, uint32_t nr, const uint32_t* start, const uint8_t* type, const uint32_t* info, uint64_t n_anchor, const uint64_t* anchors) {
+        for (uint32_t i = 0; i <= nr; ++i) c._reg_pos.set(start[i]);
+        c._reg_pos.init_support();
+        c._reg_type.clear();
+        for (uint32_t i = 0; i <= nr; ++i) c._reg_type.push_back((RegionType)type[i]);
+        c._reg_info.assign(info, info + nr + 1);
+        c._anchor_kmers.assign(anchors, anchors + n_anchor);
+        c._pwindows.clear(); c._pwindows.resize((size_t)nr + 1);
+        for (uint32_t i = 0; i < nr; ++i)
+            if (c._reg_type[i] != RegionType::SR && c._reg_type[i] != RegionType::MSR) c._pwindows[i].reset(new Window(c._pseq, start[i], start[i + 1], WindowType::SHORT));
+    }
+    // LONG: the pseudo tables with the identity as _true_reg_id and a LONG Window per LONG region
+    static void set_long(Contig& c, uint32_t nr, const uint32_t* start, const uint8_t* type) {
+        c._pseudo_reg_pos = BitVec((uint64_t)c._len + 1);
+        for (uint32_t i = 0; i <= nr; ++i) c._pseudo_reg_pos.set(start[i]);
+        c._pseudo_reg_pos.init_support();
+        c._pseudo_reg_type.clear(); c._true_reg_id.clear(); c._reg_type.clear();
+        for (uint32_t i = 0; i <= nr; ++i) { c._pseudo_reg_type.push_back((RegionType)type[i]); c._reg_type.push_back((RegionType)type[i]); c._true_reg_id.push_back(i); }
+        c._pwindows.clear(); c._pwindows.resize((size_t)nr + 1);
+        for (uint32_t i = 0; i < nr; ++i)
+            if (c._pseudo_reg_type[i] == RegionType::LONG) c._pwindows[i].reset(new Window(c._pseq, start[i], start[i + 1], WindowType::LONG));
+    }
+};
 }  // namespace hypo
 
+// the arms both exports return: per region whether a window remains, internal / prefix / suffix / empty, and Window::dump_text()
+// ("draft|I:arm..|P:arm..|S:arm..") of the remaining windows, one per line in region order.  The number of bytes, -2: text too small
+static long arms_report(const Contig& c, uint32_t nr, uint8_t* valid, uint32_t* counts, char* text, long cap) {
+    long at = 0;
+    for (uint32_t i = 0; i < nr; ++i) {
+        valid[i] = c.is_valid_window(i) ? 1 : 0;
+        counts[4 * i] = counts[4 * i + 1] = counts[4 * i + 2] = counts[4 * i + 3] = 0;
+        if (!valid[i]) continue;
+        const Window& w = *c.window(i);
+        unsigned n[4] = {0, 0, 0, 0};
+        std::sscanf(w.dump_counts().c_str(), "%u\t%u\t%u\t%u", &n[0], &n[1], &n[2], &n[3]);
+        for (int j = 0; j < 4; ++j) counts[4 * i + j] = n[j];
+        const std::string t = w.dump_text();
+        if (at + (long)t.size() + 1 > cap) return -2;
+        std::memcpy(text + at, t.data(), t.size()); at += (long)t.size(); text[at++] = '\n';
+    }
+    return at;
+}
+// an Alignment per record, in file order (file_rank NULL: the order given)
+static bool arms_alignments(uint64_t total_len, uint32_t n, const uint32_t* rb, const uint32_t* re, const uint32_t* qae, const uint64_t* seq_off, const uint8_t* reads2,
+                            const uint32_t* cigar_off, const uint32_t* cigar, const uint32_t* file_rank, std::vector<std::unique_ptr<Alignment>>& out) {
+    out.clear(); out.resize(n);
+    for (uint32_t a = 0; a < n; ++a) {
+        const uint32_t at = file_rank ? file_rank[a] : a;
+        if (re[a] <= rb[a] || re[a] > total_len || at >= n || out[at]) return false;
+        out[at].reset(new Alignment(rb[a], re[a], qae[a], reads2 + seq_off[a], cigar + cigar_off[a], cigar_off[a + 1] - cigar_off[a]));
+    }
+    return true;
+}
+// the contig as text from its PackedSeq<4> bytes
+static std::string arms_contig_text(const uint8_t* contig4, uint64_t total_len) {
+    std::string s((size_t)total_len, 'N');
+    for (uint64_t p = 0; p < total_len; ++p) { const unsigned c = (contig4[p >> 1] >> (4 - 4 * (p & 1))) & 15u; s[(size_t)p] = "ACGTN"[c < 4 ? c : 4]; }
+    return s;
+}
+
 extern "C" {
+
+// Alignment::find_short_arms of every record in file order, then Contig::fill_short_windows, over the flat tables hypo_gpu_arms_build
+// takes (include/hypo_gpu.h; the tables must be consistent: tests/arms_cases.py check_tables).  OUT valid [n_regions], counts
+// [4 * n_regions], text (see arms_report).  The number of text bytes; -1: a record does not fit; -2: text too small
+long hypo_host_short_arms(uint32_t n_regions, const uint32_t* start, const uint8_t* type, const uint32_t* info, uint64_t n_anchor, const uint64_t* anchors, uint32_t k,
+                          const uint8_t* contig4, uint32_t n_reads, const uint32_t* rb, const uint32_t* re, const uint32_t* qae, const uint64_t* seq_off, const uint8_t* reads2,
+                          const uint32_t* cigar_off, const uint32_t* cigar, const uint32_t* file_rank, uint8_t* valid, uint32_t* counts, char* text, long cap) {
+    const uint64_t total_len = start[n_regions];
+    Contig c(0, "arms", arms_contig_text(contig4, total_len));
+    ArmTables::set_short(c, n_regions, start, type, info, n_anchor, anchors);
+    std::vector<std::unique_ptr<Alignment>> al;
+    if (!arms_alignments(total_len, n_reads, rb, re, qae, seq_off, reads2, cigar_off, cigar, file_rank, al)) return -1;
+    for (auto& a : al) a->find_short_arms(k, c);
+    c.fill_short_windows(al);
+    return arms_report(c, n_regions, valid, counts, text, cap);
+}
+
+// Alignment::find_long_arms of every record in file order, then Contig::fill_long_windows, over the pseudo regions hypo_gpu_arms_build_long takes
+long hypo_host_long_arms(uint32_t n_regions, const uint32_t* start, const uint8_t* type, const uint8_t* contig4, uint32_t n_reads, const uint32_t* rb, const uint32_t* re,
+                         const uint32_t* qae, const uint64_t* seq_off, const uint8_t* reads2, const uint32_t* cigar_off, const uint32_t* cigar, const uint32_t* file_rank,
+                         uint8_t* valid, uint32_t* counts, char* text, long cap) {
+    const uint64_t total_len = start[n_regions];
+    Contig c(0, "arms", arms_contig_text(contig4, total_len));
+    ArmTables::set_long(c, n_regions, start, type);
+    std::vector<std::unique_ptr<Alignment>> al;
+    if (!arms_alignments(total_len, n_reads, rb, re, qae, seq_off, reads2, cigar_off, cigar, file_rank, al)) return -1;
+    for (auto& a : al) a->find_long_arms(c);
+    c.fill_long_windows(al);
+    return arms_report(c, n_regions, valid, counts, text, cap);
+}
 
 int hypo_host_set_scores(const int8_t sc[6]) {
     ScoreParams sp{sc[0], sc[1], sc[2], sc[3], sc[4], sc[5]};

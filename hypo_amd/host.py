@@ -121,3 +121,38 @@ class HostMirror:
         if rc != 0:
             raise RuntimeError(f"hypo_host_minimizer_votes rc={rc}")
         return cov[:n_ent], sup[:n_ent]
+
+    def _arms(self, long_mode, regions, reads):
+        u32 = lambda a: np.ascontiguousarray(a, dtype=np.uint32)
+        p = lambda a: None if a is None else a.ctypes.data_as(C.c_void_p)
+        nr = int(regions.n_regions)
+        start, rtype, contig4 = u32(regions.start), np.ascontiguousarray(regions.type, dtype=np.uint8), np.ascontiguousarray(regions.contig4, dtype=np.uint8)
+        rb, re, qae, cigar_off, cigar = (u32(x) for x in (reads.rb, reads.re, reads.qae, reads.cigar_off, reads.cigar))
+        seq_off = np.ascontiguousarray(reads.seq_off, dtype=np.uint64); reads2 = np.ascontiguousarray(reads.reads2, dtype=np.uint8)
+        rank = None if getattr(reads, "file_rank", None) is None else u32(reads.file_rank)
+        valid = np.zeros(nr, dtype=np.uint8); counts = np.zeros(4 * nr, dtype=np.uint32)
+        cap = int(start[nr]) + 2 * int(qae.sum()) + 8 * int(rb.size) + nr + 1024
+        text = C.create_string_buffer(cap)
+        tail = (C.c_uint32(rb.size), p(rb), p(re), p(qae), p(seq_off), p(reads2), p(cigar_off), p(cigar), p(rank), p(valid), p(counts), text, C.c_long(cap))
+        if long_mode:
+            f = self.lib.hypo_host_long_arms
+            f.restype = C.c_long
+            n = f(C.c_uint32(nr), p(start), p(rtype), p(contig4), *tail)
+        else:
+            info, anchors = u32(regions.info), np.ascontiguousarray(regions.anchor_kmers, dtype=np.uint64)
+            f = self.lib.hypo_host_short_arms
+            f.restype = C.c_long
+            n = f(C.c_uint32(nr), p(start), p(rtype), p(info), C.c_uint64(anchors.size), p(anchors), C.c_uint32(regions.k), p(contig4), *tail)
+        if n < 0:
+            raise RuntimeError(f"hypo_host_{'long' if long_mode else 'short'}_arms rc={n}")
+        return valid, counts.reshape(nr, 4), text.raw[:n].decode().split("\n")[:-1]
+
+    def short_arms(self, regions, reads):
+        """Alignment::find_short_arms of every record in file order (reads.file_rank, or the order given) + Contig::fill_short_windows over
+        the flat arrays hypo_gpu_arms_build takes (attributes named as in HypoArmsRegions / HypoArmsReads): (valid [n_regions], internal /
+        prefix / suffix / empty [n_regions, 4], Window::dump_text of every remaining window in region order)"""
+        return self._arms(False, regions, reads)
+
+    def long_arms(self, regions, reads):
+        """the same through Alignment::find_long_arms + Contig::fill_long_windows over pseudo regions (SR / LONG)"""
+        return self._arms(True, regions, reads)

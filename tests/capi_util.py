@@ -36,3 +36,12 @@ def exact_reads(codes, n_reads, read_len, rng):
     cigar_off = np.arange(m + 1, dtype=np.uint32)
     cigar = np.full(m, (read_len << 4) | 0, dtype=np.uint32)
     return rb, re, qae, seq_off, reads2, cigar_off, cigar
+
+
+class ArmsRegions(C.Structure):                    # HypoArmsRegions
+    _fields_ = [("n_regions", C.c_uint32), ("start", C.c_void_p), ("type", C.c_void_p), ("info", C.c_void_p), ("n_anchor_kmers", C.c_uint64),
+                ("anchor_kmers", C.c_void_p), ("k", C.c_uint32), ("contig4", C.c_void_p)]
+
+
+class ArmsSummary(C.Structure):                    # HypoArmsSummary
+    _fields_ = [("n_windows", C.c_uint32), ("n_arms", C.c_uint32), ("arms2_bytes", C.c_uint64), ("draft4_bytes", C.c_uint64), ("out_bytes", C.c_uint64)]

@@ -408,3 +408,11 @@ def test_arms_build_long_small_batch_equals_the_recorded_one():
     assert summary2 == summary and valid2.tolist() == is_long and arrays2 == arrays
     got = dict(summary=summary, sha256={k: hashlib.sha256(v).hexdigest() for k, v in arrays.items()})
     assert got == json.load(open(GOLDEN))
+    # ... and what was recorded is the contract's: the same arrays from the plain restatement of the host loops (tests/arms_checker.py)
+    import arms_cases
+    import arms_checker
+    R = arms_cases.Regions(len(types) - 1, _u32(*start), np.array(types, dtype=np.uint8), None, 0, None, 10, p4, codes)
+    A = arms_cases.Reads(reads[0], reads[1], reads[2], reads[3], reads[4], reads[4].size, reads[5], reads[6], None)
+    x = arms_checker.build(R, A, long_mode=True)
+    assert x.summary == summary and x.region_valid == is_long
+    assert {k: v.tobytes() for k, v in arms_cases.as_arrays(x).items()} == arrays
