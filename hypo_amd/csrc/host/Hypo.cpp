@@ -6,6 +6,7 @@
 #include "KmerGuard.hpp"
 #include "KmerFix.hpp"
 #include "QvReport.hpp"
+#include "ReadKmerSet.hpp"
 #include "SpectraReport.hpp"
 #include <ctime>
 #include <omp.h>
@@ -21,22 +22,23 @@ extern std::atomic<uint64_t> g_stage_counters[5];      // host/Contig.cpp
 // --vcf, --qv, --qv-bed, --qv-spectra, --kmer-guard, --kmer-fix: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
 struct Extras {
     EditScriptsFn edit_fn = nullptr, guard_edit_fn = nullptr;
-    QvReport qv;
-    KmerGuard guard;
-    SpectraReport spectra;
-    KmerFix fix;
+    ReadKmerSet set;                                       // the k-mers of the reads, on context 0 from bind_extras to commit_outputs
+    QvReport qv{set};
+    KmerGuard guard{set};
+    SpectraReport spectra{set};
+    KmerFix fix{set};
     bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false, fix_on = false;
     uint32_t min_given = 1;                                // --qv-min-count: 1 = off, 0 = the valley
     bool min_on() const { return min_given != 1; }
     bool ask_on = false;                                   // --qv or --qv-bed: every contig's texts are put to the set
     bool text_on = false;                                  // ... or --qv-spectra: every contig's texts are needed as strings
     bool set_on = false;                                   // ... or --kmer-guard or --kmer-fix: the set is built
-    ReadSink qv_sink;                                      // (holds a pointer to qv: an Extras stays where it is)
+    ReadSink set_sink;                                     // (holds a pointer to set: an Extras stays where it is)
     VcfStats vstats;
     Extras() = default; Extras(const Extras&) = delete;
-    [[noreturn]] void qv_fail(const char* what) {
+    [[noreturn]] void set_fail(const char* what) {
         std::fprintf(stderr, "[Hypo::QV] Error: %s: %s\n", what, hypo_gpu_last_error());
-        qv.end();
+        set.end();
         std::exit(1);
     }
     // one contig's two texts to whoever wants them: the set's queries, then the marks of --qv-spectra
@@ -48,16 +50,16 @@ struct Extras {
         const int rc = ask_on ? qv.flush() : HYPO_OK;
         return rc == HYPO_OK && spectra_on ? spectra.flush() : rc;
     }
-    void qv_reads_done(const SolidBuildStats& st, bool shared_pass) {
-        if (qv.read_size() != HYPO_OK) qv_fail("hypo_gpu_kset_size");
+    void set_reads_done(const SolidBuildStats& st, bool shared_pass) {
+        if (set.reads_done() != HYPO_OK) set_fail("hypo_gpu_kset_size");
         // --qv-min-count: the last read is in and nothing has been asked yet; from here on the set answers for the reliable k-mers
         if (min_on()) {
-            if (qv.set_min_count(min_given) != HYPO_OK) qv_fail("hypo_gpu_kset_spectrum / hypo_gpu_kset_min_count");
-            std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer min count (k = %u): >= %u (%s), %llu of %llu read k-mers reliable\n", qv.k(), qv.min_count(),
-                         min_given ? "given" : "valley", (unsigned long long)qv.n_reliable(), (unsigned long long)qv.n_distinct());
+            if (set.set_min_count(min_given) != HYPO_OK) set_fail("hypo_gpu_kset_spectrum / hypo_gpu_kset_min_count");
+            std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer min count (k = %u): >= %u (%s), %llu of %llu read k-mers reliable\n", set.k(), set.min_count(),
+                         min_given ? "given" : "valley", (unsigned long long)set.n_reliable(), (unsigned long long)set.n_distinct());
         }
-        std::fprintf(stderr, "[Hypo::QV] Info: k-mer set of the reads (k = %u): %llu distinct k-mers, %.3f s in the insert calls of %.3f GB%s\n", qv.k(),
-                     (unsigned long long)qv.n_distinct(), st.sink_s, st.seq_bytes / 1e9, shared_pass ? " (the parse pass of the solid k-mers)" : " (reads parsed for the QV alone)");
+        std::fprintf(stderr, "[Hypo::QV] Info: k-mer set of the reads (k = %u): %llu distinct k-mers, %.3f s in the insert calls of %.3f GB%s\n", set.k(),
+                     (unsigned long long)set.n_distinct(), st.sink_s, st.seq_bytes / 1e9, shared_pass ? " (the parse pass of the solid k-mers)" : " (reads parsed for the QV alone)");
     }
 };
 
@@ -90,6 +92,17 @@ void host_fallback(const Batch& b, const char* what) {
     std::fflush(nullptr);
     RunOutputs::discard();
     std::_Exit(1);
+}
+// What a flag needs of the device library: an entry point or a group of them as the error line names it (with the blank, comma or
+// "and" in front of it), and whether the library has it.  The run ends when one is absent; the line names all of them, or
+// (only_absent) the absent ones.
+struct Needed { std::string named; bool present; };
+void require(const char* flag, std::initializer_list<Needed> needs, bool only_absent = false) {
+    std::string absent, all;
+    for (const Needed& n : needs) { all += n.named; if (!n.present) absent += n.named; }
+    if (absent.empty()) return;
+    std::fprintf(stderr, "[Hypo::Hypo] Error: %s needs%s, which the device library does not provide\n", flag, (only_absent ? absent : all).c_str());
+    std::exit(1);
 }
 }
 
@@ -161,85 +174,57 @@ void Hypo::polish() {
 
 // ---- once per run, before the batches ----------------------------------------------------------------------------------------
 void Hypo::bind_extras(Extras& ex) {
-    // --kmer-fix: the fixes query and the track query, bound by name and only under the flag, and the set they ask.  Checked
-    // first: its error names what is lacking.
     ex.fix_on = !_cFlags.kmer_fix_filename.empty();
-    if (ex.fix_on) {
-        ex.fix.set_k(_cFlags.qv_k);
-        const bool have_all = ex.fix.bind(), have_set = QvReport().bind();
-        if (!have_all || !have_set) {
-            std::fprintf(stderr, "[Hypo::Hypo] Error: --kmer-fix needs%s%s%s, which the device library does not provide\n", ex.fix.have_fixes() ? "" : " hypo_gpu_kset_query_fixes",
-                         ex.fix.have_track() ? "" : " hypo_gpu_kset_query_track", have_set ? "" : " hypo_gpu_kset_begin / _add / _size / _end");
-            std::exit(1);
-        }
-    }
-    // --qv-min-count: counts on the set and the threshold of its queries, bound by name and only under the flag (1 is the run
-    // without it).  Checked first: its error names them.
     ex.min_given = _cFlags.qv_min_count;
-    if (ex.min_on() && !(ex.qv.bind_min_count() && ex.qv.bind())) {
-        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv-min-count needs hypo_gpu_kset_counts_enable, hypo_gpu_kset_spectrum and hypo_gpu_kset_min_count, and hypo_gpu_kset_begin / _add / _size / _end, which the device library does not provide\n");
-        std::exit(1);
-    }
-    // --qv-spectra: counts on the set, bound by name and only under the flag.  Checked first: its error names them.
     ex.spectra_on = !_cFlags.qv_spectra_filename.empty();
-    if (ex.spectra_on && !(ex.spectra.bind() && ex.qv.bind())) {
-        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv-spectra needs hypo_gpu_kset_counts_enable, hypo_gpu_kset_mark and hypo_gpu_kset_spectrum, and hypo_gpu_kset_begin / _add / _size / _end, which the device library does not provide\n");
-        std::exit(1);
-    }
-    // --qv-bed: the track query, bound by name and only under the flag, and the set it asks.  Checked first: its error names it.
     ex.bed_on = !_cFlags.qv_bed_filename.empty();
-    if (ex.bed_on && !(ex.qv.bind_track() && ex.qv.bind())) {
-        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv-bed needs hypo_gpu_kset_query_track and hypo_gpu_kset_begin / _add / _size / _end, which the device library does not provide\n");
-        std::exit(1);
-    }
-    // --kmer-guard: the k-mer set of --qv (with or without its table), the spans query against it, and the edit scripts whether
-    // or not a VCF is written.  Checked first, so that its error names everything the guard lacks.
     ex.guard_on = _cFlags.kmer_guard;
-    if (ex.guard_on) {
-        ex.guard.set_k(_cFlags.qv_k);
-        // --guard-records: the variants query as well, bound by name and only under the flag
-        if (_cFlags.guard_records && !ex.guard.bind_variants(_cFlags.guard_records_max)) {
-            std::fprintf(stderr, "[Hypo::Hypo] Error: --guard-records needs hypo_gpu_kset_query_variants, which the device library does not provide\n");
-            std::exit(1);
-        }
-        const bool have_spans = ex.guard.bind(), have_set = QvReport().bind();
-        ex.guard_edit_fn = bind_edit_scripts();
-        if (!have_spans || !have_set || !ex.guard_edit_fn) {
-            std::fprintf(stderr, "[Hypo::Hypo] Error: --kmer-guard needs%s%s%s, which the device library does not provide\n", have_spans ? "" : " hypo_gpu_kset_query_spans",
-                         have_set ? "" : " hypo_gpu_kset_begin / _add / _size / _end", ex.guard_edit_fn ? "" : " hypo_gpu_edit_scripts");
-            std::exit(1);
-        }
-    }
-    // --vcf: the device library must provide the edit scripts (C-ABI 10); bound by name, and only here, so that libraries without
-    // the entry point still serve every run without --vcf
-    if (!_cFlags.vcf_filename.empty() && !(ex.edit_fn = bind_edit_scripts())) {
-        std::fprintf(stderr, "[Hypo::Hypo] Error: --vcf needs hypo_gpu_edit_scripts (C-ABI 10), which the device library does not provide\n");
-        std::exit(1);
-    }
-    // --qv: likewise the exact k-mer set (C-ABI 11).  It lives on context 0 from here until the last contig is written.
     ex.qv_on = !_cFlags.qv_filename.empty();
-    if (ex.qv_on && !ex.qv.bind()) {
-        std::fprintf(stderr, "[Hypo::Hypo] Error: --qv needs hypo_gpu_kset_begin / _add / _size / _query / _end (C-ABI 11), which the device library does not provide\n");
-        std::exit(1);
-    }
     ex.ask_on = ex.qv_on || ex.bed_on;
     ex.text_on = ex.ask_on || ex.spectra_on;
     ex.set_on = ex.text_on || ex.guard_on || ex.fix_on;
-    if ((ex.guard_on || ex.fix_on) && !ex.ask_on) (void)ex.qv.bind();   // (the guard's or the fix's check above found the entry points)
+    // Every entry point behind these flags is bound by name, and only under its flag, so that libraries without it still serve every
+    // run without the flag.  The flags are checked in this order, and each one's error names what it needs.
+    const bool have_set = (ex.set_on || ex.min_on()) && ex.set.bind();
+    const std::string the_set = ReadKmerSet::kNames;
+    // --kmer-fix: the fixes query and the track query, and the set they ask
+    if (ex.fix_on)
+        require("--kmer-fix", {{" hypo_gpu_kset_query_fixes", ex.fix.bind()}, {" hypo_gpu_kset_query_track", ex.set.bind_track()}, {" " + the_set, have_set}}, true);
+    // --qv-min-count: counts on the set and the threshold of its queries (1 is the run without it)
+    if (ex.min_on())
+        require("--qv-min-count", {{" hypo_gpu_kset_counts_enable, hypo_gpu_kset_spectrum and hypo_gpu_kset_min_count,", ex.set.bind_counts()}, {" and " + the_set, have_set}});
+    // --qv-spectra: counts on the set, and the marks
+    if (ex.spectra_on) {
+        (void)ex.set.bind_counts();
+        require("--qv-spectra", {{" hypo_gpu_kset_counts_enable, hypo_gpu_kset_mark and hypo_gpu_kset_spectrum,", ex.spectra.bind() && ex.set.have_counts()}, {" and " + the_set, have_set}});
+    }
+    // --qv-bed: the track query, and the set it asks
+    if (ex.bed_on) {
+        require("--qv-bed", {{" hypo_gpu_kset_query_track", ex.set.bind_track()}, {" and " + the_set, have_set}});
+        ex.qv.keep_track();
+    }
+    // --kmer-guard: the spans query against the set, and the edit scripts whether or not a VCF is written; --guard-records: the
+    // variants query as well
+    if (ex.guard_on) {
+        if (_cFlags.guard_records) require("--guard-records", {{" hypo_gpu_kset_query_variants", ex.guard.bind_variants(_cFlags.guard_records_max)}});
+        ex.guard_edit_fn = bind_edit_scripts();
+        require("--kmer-guard", {{" hypo_gpu_kset_query_spans", ex.guard.bind()}, {" " + the_set, have_set}, {" hypo_gpu_edit_scripts", ex.guard_edit_fn != nullptr}}, true);
+    }
+    // --vcf: the edit scripts (C-ABI 10)
+    if (!_cFlags.vcf_filename.empty()) require("--vcf", {{" hypo_gpu_edit_scripts (C-ABI 10)", (ex.edit_fn = bind_edit_scripts()) != nullptr}});
+    // --qv: the set and its query (C-ABI 11)
+    if (ex.qv_on) require("--qv", {{" hypo_gpu_kset_begin / _add / _size / _query / _end (C-ABI 11)", ex.qv.bind() && have_set}});
+    // the set lives on context 0 from here until the last contig is written
     if (ex.set_on) {
         // (sized for one k-mer per genome position; what the read errors add makes it grow)
         const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
-        if (ex.qv.begin(_cFlags.qv_k, _cFlags.genome_size, cap, 0) != HYPO_OK) ex.qv_fail("the k-mer set could not be created");
-        ex.qv_sink = ex.qv.sink();
-        // --qv-spectra: the set counts from its first k-mer on, and the reads reach it window by window, each once
-        if (ex.spectra_on) {
-            if (ex.spectra.enable() != HYPO_OK) ex.qv_fail("the k-mer set could not be made to count");
-            ex.qv_sink.exact = true;
-        }
-        // --qv-min-count: likewise, with one plane less when no text is going to be marked
-        if (ex.min_on()) {
-            if (!ex.spectra_on && ex.qv.enable_counts() != HYPO_OK) ex.qv_fail("the k-mer set could not be made to count");
-            ex.qv_sink.exact = true;
+        if (ex.set.begin(_cFlags.qv_k, _cFlags.genome_size, cap) != HYPO_OK) ex.set_fail("the k-mer set could not be created");
+        ex.set_sink = ex.set.sink();
+        // --qv-spectra, --qv-min-count: the set counts from its first k-mer on, with a plane of copy bytes for each text that is
+        // going to be marked (one at the least), and the reads reach it window by window, each once
+        if (ex.spectra_on || ex.min_on()) {
+            if (ex.set.enable_counts(ex.spectra_on ? SpectraReport::N_TEXTS : 1) != HYPO_OK) ex.set_fail("the k-mer set could not be made to count");
+            ex.set_sink.exact = true;
         }
     }
 }
@@ -250,8 +235,8 @@ void Hypo::solid_kmers(Extras& ex, std::ofstream& stagefile, SolidKmers& sk) {
     if (_cFlags.done_stage < 1) {
         SolidBuildStats st;
         std::string err;
-        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err, ex.set_on ? &ex.qv_sink : nullptr);
-        if (rc == SOLID_E_SINK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); ex.qv.end(); std::exit(1); }
+        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err, ex.set_on ? &ex.set_sink : nullptr);
+        if (rc == SOLID_E_SINK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); ex.set.end(); std::exit(1); }
         if (rc == SOLID_E_UNDEFINED) {                   // the reference's own line for a failed initialise (src/Hypo.cpp:53)
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: %s\n", err.c_str());
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: KMC Output: Could not have successful run of SUK for computing Solid kmers!\n");
@@ -263,7 +248,7 @@ void Hypo::solid_kmers(Extras& ex, std::ofstream& stagefile, SolidKmers& sk) {
         }
         std::fprintf(stderr, "[Hypo::SolidKmers] Info: device construction: %.3f s (parse %.3f s of %.3f GB, count %.3f s of %.3f GB sent, "
                              "histogram %.3f s, set %.3f s)\n", st.total_s, st.parse_s, st.file_bytes / 1e9, st.count_s, st.seq_bytes / 1e9, st.hist_s, st.fill_s);
-        if (ex.set_on) ex.qv_reads_done(st, true);
+        if (ex.set_on) ex.set_reads_done(st, true);
         if (_cFlags.intermed) {
             if (!sk.store(HYPO_SKFILE)) {
                 std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Saving: Could not store the DS for Solid kmers!\n");
@@ -285,9 +270,9 @@ void Hypo::solid_kmers(Extras& ex, std::ofstream& stagefile, SolidKmers& sk) {
         if (ex.set_on) {                                 // the stored set needs no reads; the QV and the guard do
             SolidBuildStats st;
             std::string err;
-            const int rc = stream_reads(_cFlags.sr_filenames, ex.qv_sink, st, err);
-            if (rc != SOLID_OK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); ex.qv.end(); std::exit(1); }
-            ex.qv_reads_done(st, false);
+            const int rc = stream_reads(_cFlags.sr_filenames, ex.set_sink, st, err);
+            if (rc != SOLID_OK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); ex.set.end(); std::exit(1); }
+            ex.set_reads_done(st, false);
         }
         stop("[Hypo:Hypo]: Loaded Solid kmers. ");
     }
@@ -749,69 +734,49 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
         if (hypo_gpu_use_device(0) != HYPO_OK || edit_scripts_for(ex.guard_on ? ex.guard_edit_fn : ex.edit_fn, _contigs, initial_cid, final_cid, *edits) != HYPO_OK)
             writer_fatal("edit scripts");
     }
-    // --qv: the draft and the polished text of every contig of the batch go to the k-mer set in one query on context 0
-    int qrc = ex.text_on || ex.fix_on ? hypo_gpu_use_device(0) : HYPO_OK;
-    // --kmer-fix: every contig's text goes through the fixes first; what comes back is written and handed on in its place
-    const KmerFix::Emit write_fixed = [&](uint32_t c, const std::string& draft, const std::string& text) {
-        ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;
+    // Every contig takes one path.  Its source: under --kmer-guard the batch's records are made first, their clusters judged by the
+    // set, and the contig comes as its draft, the draft with the accepted records applied, and the records with the rejected ones
+    // marked; otherwise as its draft and its polished text.  --kmer-fix: the text goes through the fixes, and what comes back takes
+    // its place.  Its sink: the FASTA record, and both texts to the reports (the set's queries on context 0, the marks).
+    const char* stage = "k-mer set query";
+    int rc = ex.text_on || ex.fix_on ? hypo_gpu_use_device(0) : HYPO_OK;
+    const KmerFix::Emit file_text = [&](uint32_t c, const std::string& draft, const std::string& text) {
+        ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;      // (operator<<'s bytes)
         return ex.texts(c, draft, text);
     };
-    // --kmer-guard: the batch's records are made first, their clusters judged by the set, and every contig is written as
-    // its draft with the accepted records applied
-    if (ex.guard_on && ex.fix_on) {
+    auto text_out = [&](uint32_t c, auto&& draft, auto&& text) {
+        if (!ex.fix_on) return file_text(c, draft, text);
+        return ex.fix.push(c, _contigs[c]->get_name(), ex.text_on ? std::string(std::forward<decltype(draft)>(draft)) : std::string(), std::forward<decltype(text)>(text), file_text);
+    };
+    // the VCF records while the contig's windows exist, then the windows go; recs: the guard's, with which of them it rejected
+    auto records_out = [&](uint32_t c, const VcfContigRecords* recs, const std::vector<uint8_t>* rejected) {
+        if (recs && ex.edit_fn) vcf_write_records(vfile, *_contigs[c], *recs, rejected);
+        if (!recs && edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, ex.vstats);
+        _contigs[c]->release_after_output();
+    };
+    if (rc == HYPO_OK && ex.guard_on) {
+        stage = "k-mer guard";
         VcfStats unused;
-        int grc = ex.guard.run_batch(_contigs, initial_cid, final_cid, *edits, ex.edit_fn ? ex.vstats : unused,
+        rc = ex.guard.run_batch(_contigs, initial_cid, final_cid, *edits, ex.edit_fn ? ex.vstats : unused,
             [&](uint32_t c, const std::string& draft, const std::string& text, const VcfContigRecords& recs, const std::vector<uint8_t>& rejected) {
-                if (ex.edit_fn) vcf_write_records(vfile, *_contigs[c], recs, &rejected);
-                const std::string name = _contigs[c]->get_name();
-                _contigs[c]->release_after_output();
-                return ex.fix.push(c, name, ex.text_on ? draft : std::string(), text, write_fixed);
+                records_out(c, &recs, &rejected);
+                return text_out(c, draft, text);
             });
-        if (grc == HYPO_OK) grc = ex.fix.flush(write_fixed);
-        if (grc == HYPO_OK) qrc = ex.texts_flush();
-        if (grc != HYPO_OK || qrc != HYPO_OK) writer_fatal(grc != HYPO_OK ? "k-mer guard / k-mer fix" : "k-mer set query");
-        return;
-    }
-    if (ex.guard_on) {
-        VcfStats unused;
-        const int grc = ex.guard.run_batch(_contigs, initial_cid, final_cid, *edits, ex.edit_fn ? ex.vstats : unused,
-            [&](uint32_t c, const std::string& draft, const std::string& text, const VcfContigRecords& recs, const std::vector<uint8_t>& rejected) {
-                ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;
-                if (ex.edit_fn) vcf_write_records(vfile, *_contigs[c], recs, &rejected);
-                _contigs[c]->release_after_output();
-                return ex.texts(c, draft, text);
-            });
-        if (grc == HYPO_OK) qrc = ex.texts_flush();
-        if (grc != HYPO_OK || qrc != HYPO_OK) writer_fatal(grc != HYPO_OK ? "k-mer guard" : "k-mer set query");
-        return;
-    }
-    if (ex.fix_on) {
-        for (uint32_t c = initial_cid; c < final_cid && qrc == HYPO_OK; ++c) {
+    } else if (ex.text_on || ex.fix_on) {
+        if (ex.fix_on) stage = "k-mer fix / k-mer set query";
+        for (uint32_t c = initial_cid; c < final_cid && rc == HYPO_OK; ++c) {
             std::string text = _contigs[c]->polished_text();
             std::string draft = ex.text_on ? _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()) : std::string();
-            if (edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, ex.vstats);
-            const std::string name = _contigs[c]->get_name();
-            _contigs[c]->release_after_output();
-            qrc = ex.fix.push(c, name, std::move(draft), std::move(text), write_fixed);
+            records_out(c, nullptr, nullptr);
+            rc = text_out(c, std::move(draft), std::move(text));
         }
-        if (qrc == HYPO_OK) qrc = ex.fix.flush(write_fixed);
-        if (qrc == HYPO_OK) qrc = ex.texts_flush();
-        if (qrc != HYPO_OK) writer_fatal("k-mer fix / k-mer set query");
-        return;
+    } else {
+        // the plain run: the record is streamed, no report wants its text
+        for (uint32_t c = initial_cid; c < final_cid; ++c) { ofile << *_contigs[c]; records_out(c, nullptr, nullptr); }
     }
-    for (uint32_t c = initial_cid; c < final_cid; ++c) {
-        if (ex.text_on) {
-            const std::string text = _contigs[c]->polished_text();
-            ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;      // (operator<<'s bytes)
-            if (qrc == HYPO_OK) qrc = ex.texts(c, _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()), text);
-        } else {
-            ofile << *_contigs[c];
-        }
-        if (edits) vcf_records(vfile, *_contigs[c], *edits, c - initial_cid, ex.vstats);
-        _contigs[c]->release_after_output();
-    }
-    if (qrc == HYPO_OK) qrc = ex.texts_flush();
-    if (qrc != HYPO_OK) writer_fatal("k-mer set query");
+    if (rc == HYPO_OK && ex.fix_on) { stage = "k-mer fix / k-mer set query"; rc = ex.fix.flush(file_text); }
+    if (rc == HYPO_OK) { stage = "k-mer set query"; rc = ex.texts_flush(); }
+    if (rc != HYPO_OK) writer_fatal(stage);
 }
 
 // ---- once per run, behind the batches ---------------------------------------------------------------------------------------
@@ -820,21 +785,18 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
     if (_writer.joinable()) _writer.join();
     // --qv-spectra: the two spectra leave the device before the set goes
     if (ex.spectra_on) {
-        if (hypo_gpu_use_device(0) != HYPO_OK || ex.spectra.fetch(ex.qv.k(), ex.qv.n_distinct(), _cFlags.qv_reliable_min) != HYPO_OK) ex.qv_fail("hypo_gpu_kset_spectrum");
+        if (hypo_gpu_use_device(0) != HYPO_OK || ex.spectra.fetch(_cFlags.qv_reliable_min) != HYPO_OK) ex.set_fail("hypo_gpu_kset_spectrum");
         ex.spectra.write(out.open_spectra(_cFlags.qv_spectra_filename));
     }
     if (ex.fix_on) ex.fix.write(out.open_fixes(_cFlags.kmer_fix_filename));
-    // --qv: the table is formatted once, closed and checked like the others; the set has answered its last query
-    if (ex.set_on) ex.qv.end();
-    if (ex.qv_on) {
+    // the set has answered its last query
+    if (ex.set_on) ex.set.end();
+    // --qv, --qv-bed: the table and the track are formatted once, closed and checked like the others
+    if (ex.ask_on) {
         std::vector<std::string> names;
         for (const auto& c : _contigs) names.push_back(c->get_name());
-        ex.qv.write(out.open_qv(_cFlags.qv_filename), names);
-    }
-    if (ex.bed_on) {
-        std::vector<std::string> names;
-        for (const auto& c : _contigs) names.push_back(c->get_name());
-        ex.qv.write_track(out.open_bed(_cFlags.qv_bed_filename), names);
+        if (ex.qv_on) ex.qv.write(out.open_qv(_cFlags.qv_filename), names);
+        if (ex.bed_on) ex.qv.write_track(out.open_bed(_cFlags.qv_bed_filename), names);
     }
     out.commit([&](RunOutputs::Which w) {
         if (w == RunOutputs::FASTA && ex.guard_on && ex.guard.by_record()) {
@@ -855,8 +817,8 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
             std::fprintf(stdout, "[Hypo::Hypo] Info: VCF %s: %llu records, %llu substituted, %llu inserted, %llu deleted bases\n", _cFlags.vcf_filename.c_str(),
                          (unsigned long long)ex.vstats.records, (unsigned long long)ex.vstats.sub, (unsigned long long)ex.vstats.ins, (unsigned long long)ex.vstats.del);
         if (w == RunOutputs::QV)
-            std::fprintf(stdout, "[Hypo::Hypo] Info: QV %s (k = %u, %llu distinct read k-mers): draft %s, polished %s\n", _cFlags.qv_filename.c_str(), ex.qv.k(),
-                         (unsigned long long)ex.qv.n_distinct(), ex.qv.draft_qv().c_str(), ex.qv.polished_qv().c_str());
+            std::fprintf(stdout, "[Hypo::Hypo] Info: QV %s (k = %u, %llu distinct read k-mers): draft %s, polished %s\n", _cFlags.qv_filename.c_str(), ex.set.k(),
+                         (unsigned long long)ex.set.n_distinct(), ex.qv.draft_qv().c_str(), ex.qv.polished_qv().c_str());
         if (w == RunOutputs::SPECTRA)
             std::fprintf(stdout, "[Hypo::Hypo] Info: spectra %s (k = %u, reliable >= %u): completeness draft %s, polished %s\n", _cFlags.qv_spectra_filename.c_str(), ex.spectra.k(),
                          ex.spectra.threshold(), ex.spectra.completeness(SpectraReport::DRAFT).c_str(), ex.spectra.completeness(SpectraReport::POLISHED).c_str());
@@ -868,7 +830,7 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         }
         if (w == RunOutputs::BED) {
             const QvReport::TrackSums ts = ex.qv.track_sums();
-            std::fprintf(stdout, "[Hypo::Hypo] Info: QV track %s (k = %u): %llu intervals covering %llu bases, %llu missing k-mers\n", _cFlags.qv_bed_filename.c_str(), ex.qv.k(),
+            std::fprintf(stdout, "[Hypo::Hypo] Info: QV track %s (k = %u): %llu intervals covering %llu bases, %llu missing k-mers\n", _cFlags.qv_bed_filename.c_str(), ex.set.k(),
                          (unsigned long long)ts.intervals, (unsigned long long)ts.bases, (unsigned long long)ts.missing);
         }
     });

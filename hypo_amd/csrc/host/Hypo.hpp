@@ -27,7 +27,7 @@
 namespace hypo {
 
 class RunOutputs;
-struct Extras;           // run-wide optional outputs: --vcf, --qv, --kmer-guard (Hypo.cpp)
+struct Extras;           // run-wide optional outputs: --vcf, the k-mer set of the reads (ReadKmerSet) and the flags that ask it (Hypo.cpp)
 struct Batch;            // the contig batch in hand (Hypo.cpp)
 struct WriterJob { uint32_t initial_cid = 0, final_cid = 0; };      // what the writer thread is given by value: the contigs to file
 

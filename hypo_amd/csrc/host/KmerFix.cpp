@@ -14,13 +14,11 @@ struct Site { size_t contig; uint64_t start, n, lo, hi, c0, c1; };     // positi
 
 bool KmerFix::bind() {
     _fixes = (decltype(_fixes))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_query_fixes");
-    _track = (decltype(_track))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_query_track");
-    return _fixes && _track;
+    return _fixes != nullptr;
 }
 
 int KmerFix::push(uint32_t contig, const std::string& name, std::string draft, std::string text, const Emit& emit) {
-    constexpr size_t kFlushAt = (size_t)512 << 20;
-    if (!_pending.empty() && _text.size() + text.size() > kFlushAt) {
+    if (!_pending.empty() && _text.size() + text.size() > ReadKmerSet::kTextPerCall) {
         const int rc = flush(emit);
         if (rc != HYPO_OK) return rc;
     }
@@ -34,19 +32,15 @@ int KmerFix::push(uint32_t contig, const std::string& name, std::string draft, s
 int KmerFix::flush(const Emit& emit) {
     if (_pending.empty()) return HYPO_OK;
     const uint32_t n = (uint32_t)_pending.size();
-    const uint64_t k = _k;
-    // the intervals of every text: one track call (a call that finds more than there is room for says how many)
-    std::vector<uint64_t> off(n + 1), total(n), missing(n), iv_off(n + 1);
+    const uint64_t k = _set.k();
+    // the intervals of every text: one track query
+    std::vector<uint64_t> off(n + 1);
     for (uint32_t i = 0; i < n; ++i) off[i] = _pending[i].off;
     off[n] = _text.size();
-    const size_t room = 1024 + _text.size() / 1024;
-    std::vector<uint64_t> start(room), end(room), count(room);
-    int rc = _track(_text.data(), off.data(), n, nullptr, total.data(), missing.data(), iv_off.data(), start.data(), end.data(), count.data(), start.size());
-    if (rc == HYPO_E_WORKSPACE) {
-        start.resize(iv_off[n]); end.resize(iv_off[n]); count.resize(iv_off[n]);
-        rc = _track(_text.data(), off.data(), n, nullptr, total.data(), missing.data(), iv_off.data(), start.data(), end.data(), count.data(), start.size());
-    }
+    ReadKmerSet::Track t;
+    int rc = _set.query_track(_text, off, nullptr, t);
     if (rc != HYPO_OK) return rc;
+    const std::vector<uint64_t> &iv_off = t.iv_off, &start = t.start, &end = t.end, &count = t.count;
     // the sites: rules (a) to (e) of DESIGN.md "k-mer fix"
     std::vector<Site> sites;
     for (uint32_t i = 0; i < n; ++i) {

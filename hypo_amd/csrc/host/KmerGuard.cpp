@@ -48,17 +48,17 @@ std::string KmerGuard::apply(const std::string& draft, const std::vector<VcfRec>
 }
 
 int KmerGuard::run_batch(const std::vector<std::unique_ptr<Contig>>& contigs, uint32_t c0, uint32_t c1, const EditBatchResult& eb, VcfStats& vst, const Emit& emit) {
-    constexpr size_t kFlushAt = (size_t)512 << 20;
+    const uint32_t k = _set.k();
     for (uint32_t c = c0; c < c1; ++c) {
         const Contig& ctg = *contigs[c];
         Pending p;
         p.contig = c;
         vcf_make_records(ctg, eb, c - c0, vst, p.recs);
-        clusters_of(p.recs.recs, _k, p.clusters);            // (none for a contig written as nothing: its <DEL> record is not guarded)
+        clusters_of(p.recs.recs, k, p.clusters);              // (none for a contig written as nothing: its <DEL> record is not guarded)
         std::string d = ctg.draft_segment(0, (uint32_t)ctg.get_len()), q = ctg.polished_text();
         uint64_t variants = 0;                                   // by record: what the contig adds to the call's sum of 2^n
         if (by_record()) for (const Cluster& cl : p.clusters) variants += cl.r1 - cl.r0 <= _max_records ? 1ull << (cl.r1 - cl.r0) : 2;
-        if (!_pending.empty() && (_text.size() + d.size() + q.size() > kFlushAt || _lo.size() + 2 * p.clusters.size() >= (1ull << 32) ||
+        if (!_pending.empty() && (_text.size() + d.size() + q.size() > ReadKmerSet::kTextPerCall || _lo.size() + 2 * p.clusters.size() >= (1ull << 32) ||
                                   _eb.size() + p.recs.recs.size() >= (1ull << 32) || _n_variants + variants >= (1ull << 31))) {
             const int rc = flush(emit);
             if (rc != HYPO_OK) return rc;
@@ -68,7 +68,7 @@ int KmerGuard::run_batch(const std::vector<std::unique_ptr<Contig>>& contigs, ui
             _n_variants += variants;
             // one site per cluster: its records are the edits, or (more than N records) one edit that is its whole polished span
             p.span0 = _lo.size();
-            const uint64_t flank = _k - 1;
+            const uint64_t flank = k - 1;
             for (const Cluster& cl : p.clusters) {
                 _lo.push_back(p.d_off + (cl.b > flank ? cl.b - flank : 0)); _hi.push_back(p.d_off + std::min<uint64_t>(p.d_len, cl.e + flank));
                 if (_edit_off.empty()) _edit_off.push_back(0);
@@ -89,7 +89,7 @@ int KmerGuard::run_batch(const std::vector<std::unique_ptr<Contig>>& contigs, ui
         }
         p.p_off = _text.size(); p.p_len = q.size(); _text += q;
         p.span0 = _lo.size();
-        const uint64_t flank = _k - 1;
+        const uint64_t flank = k - 1;
         for (const Cluster& cl : p.clusters) {
             _lo.push_back(p.d_off + (cl.b > flank ? cl.b - flank : 0)); _hi.push_back(p.d_off + std::min<uint64_t>(p.d_len, cl.e + flank));
             _lo.push_back(p.p_off + (cl.qb > flank ? cl.qb - flank : 0)); _hi.push_back(p.p_off + std::min<uint64_t>(p.p_len, cl.qe + flank));

@@ -1,0 +1,73 @@
+// ReadKmerSet.hpp — the exact set of the canonical k-mers of the short reads on device context 0 (hypo_gpu_kset_*, kset_kernel.hip;
+// DESIGN.md "k-mer QV"), from hypo_gpu_kset_begin to hypo_gpu_kset_end.  The parse pass of stage 0 fills it through sink(); then
+// --qv and --qv-bed (QvReport), --qv-spectra (SpectraReport), --kmer-guard (KmerGuard) and --kmer-fix (KmerFix) ask it, each with
+// an entry point of its own, bound where it is used.  What more than one of them needs is here: the set's k, its counts and the
+// least count of --qv-min-count (DESIGN.md "k-mer min count"), the shape of the count histogram, the track query with its retry,
+// and the bound on the text of one call.
+#pragma once
+#include <cstdint>
+#include <string>
+#include <vector>
+#include "SolidBuild.hpp"
+
+namespace hypo {
+
+class ReadKmerSet {
+public:
+    static constexpr size_t kTextPerCall = (size_t)512 << 20;       // text per query, mark, spans or track call (a batch of small contigs: one call)
+    static constexpr uint32_t kRows = 256, kCols = 5;            // hypo_gpu_kset_spectrum: hist[c * 5 + min(copy number, 4)], c = 0..255
+    static constexpr const char* kNames = "hypo_gpu_kset_begin / _add / _size / _end";
+    // the valley of a read histogram h[0 .. kRows): the smallest c in 2..254 at which it stops falling, h[c] <= h[c + 1]; 2 when it
+    // never does (the default of --qv-reliable-min, and `valley` of --qv-min-count)
+    static uint32_t valley(const uint64_t* h);
+
+    // The entry points, bound by name: only runs that build the set need them.  bind: the four of kNames; bind_counts:
+    // hypo_gpu_kset_counts_enable, _spectrum and _min_count; bind_track: hypo_gpu_kset_query_track.  false: the device library
+    // lacks one of them, and the have_* say which group.
+    bool bind();
+    bool bind_counts();
+    bool bind_track();
+    bool have_set() const { return _begin && _add && _size && _end; }
+    bool have_counts() const { return _counts_enable && _spectrum; }             // what --qv-spectra needs of the three
+    bool have_min_count() const { return _set_min_count != nullptr; }
+    bool have_track() const { return _track != nullptr; }
+
+    // the set on the calling thread's context; max_bytes 0 = the library's default cap
+    int begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes);
+    // once, right after begin: the set counts, and keeps n_texts planes of copy bytes (--qv-spectra: 2, --qv-min-count alone: 1)
+    int enable_counts(uint32_t n_texts);
+    ReadSink sink();                                         // (holds a pointer to the set; the caller sets `exact`)
+    int reads_done();                                        // after the reads: fetches the number of distinct k-mers
+    // --qv-min-count, after the reads and before the first query: reads the histogram of the read counts, takes t = `given` or, for
+    // 0, its valley, and from then on every query of the set is answered against the k-mers seen at least t times
+    int set_min_count(uint32_t given);
+    void end();                                              // frees the set (safe to call twice, and after a begin that failed)
+
+    bool open() const { return _open; }
+    uint32_t k() const { return _k; }
+    uint64_t n_distinct() const { return _n_distinct; }
+    uint32_t min_count() const { return _min_count; }
+    uint64_t n_reliable() const { return _n_reliable; }      // distinct read k-mers seen at least min_count() times
+
+    // hypo_gpu_kset_spectrum of one text plane: kRows * kCols values
+    int spectrum(uint32_t text, std::vector<uint64_t>& hist) const;
+    // hypo_gpu_kset_query_track over the sequences text[off[s], off[s + 1]), s < off.size() - 1 (want: per sequence, or NULL for all).
+    // The first call has room for 1024 intervals and one per KiB of text; a call that finds more says how many, and a second call
+    // with that room asks the set everything again (rare at one interval per kbp).  HYPO_OK or the C-ABI's error.
+    struct Track { std::vector<uint64_t> total, missing, iv_off, start, end, count; };
+    int query_track(const std::string& text, const std::vector<uint64_t>& off, const uint8_t* want, Track& out) const;
+private:
+    int (*_begin)(uint32_t, uint64_t, uint64_t) = nullptr;
+    int (*_add)(const char*, uint64_t) = nullptr;
+    int (*_size)(uint64_t*, uint64_t*) = nullptr;
+    int (*_end)(void) = nullptr;
+    int (*_counts_enable)(uint32_t) = nullptr;
+    int (*_spectrum)(uint32_t, uint64_t*) = nullptr;
+    int (*_set_min_count)(uint32_t) = nullptr;
+    int (*_track)(const char*, const uint64_t*, uint32_t, const uint8_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t) = nullptr;
+    bool _open = false;
+    uint32_t _k = 0, _min_count = 1;
+    uint64_t _n_distinct = 0, _n_reliable = 0;
+};
+
+}  // namespace hypo

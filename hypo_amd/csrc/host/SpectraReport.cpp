@@ -2,27 +2,18 @@
 #include "SpectraReport.hpp"
 #include <dlfcn.h>
 #include <cstdio>
-#include "../../../include/hypo_gpu.h"
 
 namespace hypo {
 
 bool SpectraReport::bind() {
-    _enable = (decltype(_enable))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_counts_enable");
     _mark = (decltype(_mark))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_mark");
-    _spectrum = (decltype(_spectrum))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_spectrum");
-    return _enable && _mark && _spectrum;
-}
-
-int SpectraReport::enable() {
-    for (auto& o : _off) o.assign(1, 0);
-    return _enable(N_TEXTS);
+    return _mark != nullptr;
 }
 
 int SpectraReport::push(const std::string& draft, const std::string& polished) {
-    constexpr size_t kFlushAt = (size_t)512 << 20;           // text per batch of mark calls (QvReport's bound per query call)
     _text[DRAFT] += draft; _off[DRAFT].push_back(_text[DRAFT].size());
     _text[POLISHED] += polished; _off[POLISHED].push_back(_text[POLISHED].size());
-    return _text[DRAFT].size() + _text[POLISHED].size() >= kFlushAt ? flush() : HYPO_OK;
+    return _text[DRAFT].size() + _text[POLISHED].size() >= ReadKmerSet::kTextPerCall ? flush() : HYPO_OK;
 }
 
 int SpectraReport::flush() {
@@ -37,12 +28,10 @@ int SpectraReport::flush() {
     return HYPO_OK;
 }
 
-int SpectraReport::fetch(uint32_t k, uint64_t reads_distinct, uint32_t reliable_min) {
-    _k = k; _reads_distinct = reads_distinct;
+int SpectraReport::fetch(uint32_t reliable_min) {
     for (int t = 0; t < N_TEXTS; ++t) {
         std::string().swap(_text[t]);
-        _hist[t].assign((size_t)kRows * kCols, 0);
-        const int rc = _spectrum((uint32_t)t, _hist[t].data());
+        const int rc = _set.spectrum((uint32_t)t, _hist[t]);
         if (rc != HYPO_OK) return rc;
     }
     _given = reliable_min != 0;
@@ -50,14 +39,9 @@ int SpectraReport::fetch(uint32_t k, uint64_t reads_distinct, uint32_t reliable_
     if (!_given) {
         uint64_t h[kRows];
         for (uint32_t c = 0; c < kRows; ++c) { h[c] = 0; for (uint32_t j = 0; j < kCols; ++j) h[c] += at(DRAFT, c, j); }
-        _t = valley(h);
+        _t = ReadKmerSet::valley(h);
     }
     return HYPO_OK;
-}
-
-uint32_t SpectraReport::valley(const uint64_t* h) {
-    for (uint32_t c = 2; c < kRows - 1; ++c) if (h[c] <= h[c + 1]) return c;
-    return 2;
 }
 
 void SpectraReport::sums(Text t, uint64_t& reliable, uint64_t& found) const {
@@ -76,7 +60,7 @@ std::string SpectraReport::completeness(Text t) const {
 }
 
 void SpectraReport::write(std::ostream& os) const {
-    os << "##hypo-qv-spectra\tk=" << _k << "\treads_distinct=" << _reads_distinct << "\treliable_min=" << _t << '\t' << (_given ? "given" : "valley") << '\n';
+    os << "##hypo-qv-spectra\tk=" << _set.k() << "\treads_distinct=" << _set.n_distinct() << "\treliable_min=" << _t << '\t' << (_given ? "given" : "valley") << '\n';
     os << "#text\treliable\tfound\tcompleteness\tasm_only_windows\n";
     static const char* const name[N_TEXTS] = {"draft", "polished"};
     for (int t = 0; t < N_TEXTS; ++t) {
