@@ -28,7 +28,7 @@ EXPORTS = [
     "hypo_gpu_reads_upload", "hypo_gpu_support_kmers", "hypo_gpu_support_minimizers",
     "hypo_gpu_solid_scan_keep", "hypo_gpu_solid_release", "hypo_gpu_support_kmers_kept", "hypo_gpu_host_alloc", "hypo_gpu_host_free", "hypo_gpu_host_register", "hypo_gpu_host_unregister",
     "hypo_gpu_kmer_count_begin", "hypo_gpu_kmer_count_add", "hypo_gpu_kmer_histogram", "hypo_gpu_solid_set_build",
-    "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts",
+    "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts", "hypo_gpu_edit_last_counts",
     "hypo_gpu_kset_begin", "hypo_gpu_kset_add", "hypo_gpu_kset_size", "hypo_gpu_kset_query", "hypo_gpu_kset_end",
     "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants", "hypo_gpu_kset_query_track", "hypo_gpu_kset_query_fixes",
     "hypo_gpu_kset_counts_enable", "hypo_gpu_kset_mark", "hypo_gpu_kset_spectrum", "hypo_gpu_kset_min_count",
@@ -254,6 +254,17 @@ class HypoGpu:
         ops = "=XDI"
         cigars = ["".join(f"{int(r) >> 2}{ops[int(r) & 3]}" for r in runs[int(run_off[i]):int(run_off[i + 1])]) for i in range(len(dist))]
         return dist, cigars
+
+    EDIT_COUNTS = ("pairs", "long", "wide", "second", "runs", "passes", "long_launches", "wide_launches")
+
+    def edit_last_counts(self):
+        """hypo_gpu_edit_last_counts as a dict: what the last computing edit_scripts call on this thread's context did"""
+        out = np.zeros(8, dtype=np.uint64)
+        self._check(self.lib.hypo_gpu_edit_last_counts(_p(out)))
+        return dict(zip(self.EDIT_COUNTS, (int(x) for x in out)))
+
+    def set_option(self, name: str, value: int):
+        self._check(self.lib.hypo_gpu_set_option(name.encode(), C.c_int(value)))
 
     # ---- the exact k-mer set of the reads (ABI 11; hypo --qv) ---------------------------------------------------------------
     def use_device(self, slot: int):

@@ -7,6 +7,7 @@
 #include <string.h>
 #include <dlfcn.h>
 #include <algorithm>
+#include <atomic>
 #include <chrono>
 #include <condition_variable>
 #include <mutex>
@@ -156,7 +157,8 @@ struct Ctx {
         bool valid = false; const char* a = nullptr; const char* b = nullptr; uint64_t a0 = 0, b0 = 0, n_runs = 0;
         std::vector<uint64_t> aoff, boff; std::vector<uint32_t> res;
     };
-    struct EditBufs { DevBuf a, b, a_off, b_off, res, pool, lists, ctr, moves, moves_off, vals, vals_off; EditKept kept; };
+    // last_counts: what the last computing call did (hypo_gpu_edit_last_counts; numbers the host loop holds anyway)
+    struct EditBufs { DevBuf a, b, a_off, b_off, res, pool, lists, ctr, moves, moves_off, vals, vals_off; EditKept kept; uint64_t last_counts[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };
     EditBufs ed;
     // hypo_gpu_kset_begin .. _end: the hash table (exact size; replaced by a larger one when it grows), the number of keys in it, the
     // bytes / offsets / results of the call in hand, the two counters of the kernels; what the growths cost (HYPO_KSET_STATS).
@@ -473,6 +475,7 @@ static void release_ctx(Ctx& c) {
         c.kc.in.release(); c.kc.misc.release(); c.kc = Ctx::KmerCount();
         for (DevBuf* d : {&c.ed.a, &c.ed.b, &c.ed.a_off, &c.ed.b_off, &c.ed.res, &c.ed.pool, &c.ed.lists, &c.ed.ctr, &c.ed.moves, &c.ed.moves_off, &c.ed.vals, &c.ed.vals_off}) d->release();
         c.ed.kept = Ctx::EditKept();
+        memset(c.ed.last_counts, 0, sizeof c.ed.last_counts);
         if (c.ks.table) (void)hipFree(c.ks.table);
         if (c.ks.planes) (void)hipFree(c.ks.planes);
         for (DevBuf* d : {&c.ks.in, &c.ks.off, &c.ks.res, &c.ks.ctr}) d->release();
@@ -521,6 +524,9 @@ int hypo_gpu_init(const int* device_ids, int n_devices) {
     return HYPO_OK;
 }
 
+// hypo_gpu_set_option("edit_chunk_mb"): move storage per launch of the long / wide paths of hypo_gpu_edit_scripts (more when one pair needs it)
+static std::atomic<uint64_t> g_edit_chunk_bytes{(uint64_t)256 << 20};
+
 int hypo_gpu_set_option(const char* name, int value) {
     if (!name) return fail(HYPO_E_INVALID, "NULL option name");
     if (!strcmp(name, "native_klov")) {                  // all contexts: the mode belongs to the run, not to a device
@@ -535,6 +541,11 @@ int hypo_gpu_set_option(const char* name, int value) {
     if (!strcmp(name, "giant_arena_mb")) {               // HBM of size class 6 per POA context created from now on (poa_giant.hpp); 0 = none
         if (value < 0 || value > (1 << 20)) return fail(HYPO_E_INVALID, "giant_arena_mb %d out of range", value);
         hypo::poa_set_giant_arena_mb(value);
+        return HYPO_OK;
+    }
+    if (!strcmp(name, "edit_chunk_mb")) {                // move storage per launch of the long / wide edit paths; results do not depend on it
+        if (value < 1 || value > 4096) return fail(HYPO_E_INVALID, "edit_chunk_mb %d out of range 1..4096", value);
+        g_edit_chunk_bytes = (uint64_t)value << 20;
         return HYPO_OK;
     }
     return fail(HYPO_E_INVALID, "unknown option %s", name);
@@ -1686,12 +1697,11 @@ int hypo_gpu_kset_end(void) {
 }
 
 // ---- edit scripts of the replacement units (edit_kernel.hip; hypo --vcf) ---------------------------------------------------------
-static constexpr uint64_t kEditChunkBytes = (uint64_t)256 << 20;   // move storage per launch of the long / wide paths (more when one pair needs it)
-
-// Runs the long or the wide list in chunks of at most kEditChunkBytes of move storage.  need(e) = (moves bytes, values bytes).
+// Runs the long or the wide list in chunks of at most chunk_bytes of move storage (option "edit_chunk_mb"; a pair that needs more
+// runs alone).  need(e) = (moves bytes, values bytes).  launches: one more per chunk.
 }  // extern "C"
 template <class Need, class Launch>
-static int edit_run_list(const uint4* dlist, const std::vector<uint4>& list, Need need, Launch launch) {
+static int edit_run_list(const uint4* dlist, const std::vector<uint4>& list, uint64_t chunk_bytes, uint64_t& launches, Need need, Launch launch) {
     Ctx::EditBufs& ed = g_ctx.ed;
     hipStream_t st = g_ctx.stream;
     std::vector<uint64_t> moff, voff;
@@ -1702,8 +1712,9 @@ static int edit_run_list(const uint4* dlist, const std::vector<uint4>& list, Nee
         for (; e1 < list.size(); ++e1) {
             uint64_t m, v;
             need(list[e1], m, v);
-            if (e1 > e0 && mb + m > kEditChunkBytes) break;
-            moff.push_back(mb); voff.push_back(vb);
+            if (e1 > e0 && mb + m > chunk_bytes) break;
+            // moves is addressed in bytes, vals in its int32 elements (edit_wide_run: `vals + vals_off[e]`)
+            moff.push_back(mb); voff.push_back(vb / 4);
             mb += (m + 15) & ~15ull; vb += (v + 15) & ~15ull;
         }
         HIP_TRY(ed.moves.alloc(mb));
@@ -1714,6 +1725,7 @@ static int edit_run_list(const uint4* dlist, const std::vector<uint4>& list, Nee
         HIP_TRY(hipMemcpyAsync(ed.vals_off.p, voff.data(), voff.size() * 8, hipMemcpyHostToDevice, st));
         HIP_TRY(launch(dlist + e0, (uint32_t)(e1 - e0)));
         HIP_TRY(hipStreamSynchronize(st));                    // (the offsets' host vectors are refilled for the next chunk)
+        ++launches;
         e0 = e1;
     }
     return HYPO_OK;
@@ -1759,7 +1771,10 @@ int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run
         // the pool starts at 4 runs per pair (the polishing runs measured 2.2 - 2.6) or what the context has; a call that overflows it
         // (counted, never written past) runs again with the size it reported, and the grown pool stays for the calls after it
         HIP_TRY(ed.pool.alloc(std::max<size_t>(ed.pool.cap, ((size_t)np * 4 + 1024) * 4)));
+        const uint64_t chunk_bytes = g_edit_chunk_bytes.load();
+        uint64_t n_long = 0, n_wide = 0, n_second = 0, long_launches = 0, wide_launches = 0, passes = 0;
         for (int attempt = 0;; ++attempt) {
+            n_long = n_wide = n_second = long_launches = wide_launches = 0; ++passes;
             io.pool = (uint32_t*)ed.pool.p; io.pool_cap = ed.pool.cap / 4;
             HIP_TRY(hipMemsetAsync(ed.ctr.p, 0, 32, st));
             HIP_TRY(hypo::edit_fast_run(io, g_ctx.num_cus, st));
@@ -1769,7 +1784,8 @@ int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run
                 std::vector<uint4> list((size_t)ctr[1]);
                 HIP_TRY(hipMemcpyAsync(list.data(), io.long_list, list.size() * 16, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
-                const int rc = edit_run_list(io.long_list, list, [&](const uint4& e, uint64_t& mb, uint64_t& vb) {
+                n_long = list.size();
+                const int rc = edit_run_list(io.long_list, list, chunk_bytes, long_launches, [&](const uint4& e, uint64_t& mb, uint64_t& vb) {
                     mb = 16 * (aoff[e.x + 1] - aoff[e.x] + boff[e.x + 1] - boff[e.x] - 2 * e.y + 2); vb = 0;
                 }, [&](const uint4* dl, uint32_t n) { return hypo::edit_long_run(io, dl, n, (uint8_t*)ed.moves.p, (const uint64_t*)ed.moves_off.p, st); });
                 if (rc != HYPO_OK) return rc;
@@ -1784,7 +1800,8 @@ int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run
                 std::vector<uint4> list((size_t)ctr[2 + w]);
                 HIP_TRY(hipMemcpyAsync(list.data(), dlist, list.size() * 16, hipMemcpyDeviceToHost, st));
                 HIP_TRY(hipStreamSynchronize(st));
-                const int rc = edit_run_list(dlist, list, [&](const uint4& e, uint64_t& mb, uint64_t& vb) {
+                (w ? n_second : n_wide) = list.size();
+                const int rc = edit_run_list(dlist, list, chunk_bytes, wide_launches, [&](const uint4& e, uint64_t& mb, uint64_t& vb) {
                     const uint32_t n = (uint32_t)(aoff[e.x + 1] - aoff[e.x]) - e.y, m = (uint32_t)(boff[e.x + 1] - boff[e.x]) - e.y;
                     int64_t lo, hi;
                     hypo::edit_wide_band(n, m, e.z, lo, hi);
@@ -1807,6 +1824,8 @@ int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run
         HIP_TRY(hipStreamSynchronize(st));
         kept.a = in->a; kept.b = in->b; kept.a0 = in->a_off[0]; kept.b0 = in->b_off[0]; kept.n_runs = ctr[0];
         kept.aoff.swap(aoff); kept.boff.swap(boff);
+        const uint64_t counts[8] = {np, n_long, n_wide, n_second, ctr[0], passes, long_launches, wide_launches};
+        memcpy(ed.last_counts, counts, sizeof counts);
     }
     const uint32_t *rstart = kept.res.data() + np, *rcount = rstart + np;
     for (uint32_t p = 0; p < np; ++p) run_off[p + 1] = run_off[p] + rcount[p];
@@ -1820,6 +1839,14 @@ int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run
     if (kept.n_runs) HIP_TRY(d2h(pool.data(), ed.pool.p, pool.size() * 4, st));
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t p = 0; p < np; ++p) memcpy(runs + run_off[p], pool.data() + rstart[p], (size_t)rcount[p] * 4);
+    return HYPO_OK;
+}
+
+int hypo_gpu_edit_last_counts(uint64_t out[8]) {
+    HYPO_LOCKED();
+    if (!out) return fail(HYPO_E_INVALID, "NULL");
+    if (!g_ctx.ready) return fail(HYPO_E_NOTINIT, "hypo_gpu_init was not called");
+    memcpy(out, g_ctx.ed.last_counts, sizeof g_ctx.ed.last_counts);
     return HYPO_OK;
 }
 

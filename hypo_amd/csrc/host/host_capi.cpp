@@ -10,6 +10,7 @@
 #include "Window.hpp"
 #include "SolidBuild.hpp"
 #include "CtxPlan.hpp"
+#include "../edit_kernel.hpp"
 
 using namespace hypo;
 
@@ -326,5 +327,10 @@ int hypo_host_minimizer_votes(uint32_t n_contigs, const uint32_t* contig_base, c
     }
     return 0;
 }
+
+// The two host inline functions of edit_kernel.hpp that hypo_gpu_edit_scripts sizes the move storage of a wide pair with, as the
+// device code compiles them (tests/test_edit_band_model_cpu.py holds tests/edit_band_model.py against them).
+void hypo_host_edit_wide_band(uint32_t n, uint32_t m, uint32_t d, int64_t* lo, int64_t* hi) { hypo::edit_wide_band(n, m, d, *lo, *hi); }
+uint64_t hypo_host_edit_wide_groups(int64_t lo, int64_t hi) { return hypo::edit_wide_groups(lo, hi); }
 
 }  // extern "C"

@@ -135,7 +135,10 @@ int hypo_gpu_use_device(int slot);
  *   "giant_arena_mb" megabytes of HBM that size class 6 of the POA kernel gets per POA context created after the call (default 1024): the
  *                  windows beyond the table-driven classes — an arm or draft of more than 1 021 bases, more than 16 382 sequences, more
  *                  than 32 767 nodes — run there with their whole state in a slice of it (two windows at a time), by the reference's own
- *                  procedure with its full score matrix.  A window that needs more than a slice answers HYPO_ST_CAPACITY; 0 = no class 6. */
+ *                  procedure with its full score matrix.  A window that needs more than a slice answers HYPO_ST_CAPACITY; 0 = no class 6.
+ *   "edit_chunk_mb" 1..4096 (default 256): megabytes of move storage one launch of the long / wide paths of hypo_gpu_edit_scripts may
+ *                  use; a list that needs more runs in several launches (a single pair that needs more runs alone).  Results do not
+ *                  depend on it; the tests use 1 to run the chunk loop with small inputs. */
 int hypo_gpu_set_option(const char* name, int value);
 /* First 16 hex digits of the SHA-256 over the library's sources (the .hip and .hpp files of hypo_amd/csrc and this header, in sorted
  * order), embedded at build time: says which sources a prebuilt libhypo_gpu.so came from (tests/test_abi.py checks it). */
@@ -405,6 +408,14 @@ typedef struct HypoEditBatch {
     const char* b; const uint64_t* b_off;
 } HypoEditBatch;
 int hypo_gpu_edit_scripts(const HypoEditBatch* in, uint32_t* dist, uint64_t* run_off, uint32_t* runs, uint64_t runs_cap);
+/* What the last computing hypo_gpu_edit_scripts call on the calling thread's context did (zeros before the first; a call that only
+ * copied kept results out after HYPO_E_WORKSPACE leaves it alone).  Additive to ABI 11: bind it by name.
+ *   out[0] pairs; out[1] entries of the long list (fast band, move codes in device memory); out[2] entries of the wide list (pairs the
+ *   fast band could not decide, and probes of pairs with |m - n| > 127); out[3] entries of the second wide list (probes that were not
+ *   exact); out[4] runs written; out[5] passes over the run pool (2: the pool was too small and the call ran again with the size it
+ *   had counted); out[6], out[7]: launches of the long and of the wide kernel in the last pass (one per chunk of "edit_chunk_mb").
+ * All of them are numbers the host loop holds; the routing itself is in DESIGN.md "Edit scripts". */
+int hypo_gpu_edit_last_counts(uint64_t out[8]);
 
 /* ABI 11: an exact set of the canonical k-mers of the reads, and how many k-mers of a sequence it lacks (hypo --qv; DESIGN.md
  * "k-mer QV").  A hash table in device memory on the calling thread's context: presence only, no false positives.
