@@ -26,6 +26,14 @@ KSET_MAX_FIX_SPAN = 2048
 FIXES_UNTOUCHED64 = 0xFFFFFFFFFFFFFFFF
 FIXES_UNTOUCHED32 = 0xFFFFFFFF
 
+# hypo_gpu_kset_query_walks (HYPO_KSET_MAX_WALK, HYPO_KSET_MAX_WALK_BUDGET, HYPO_WALK_*); hypo_amd.capi fills the outputs with the
+# sentinels before a call (no status, step count or length is that large, and no base is that byte)
+KSET_MAX_WALK = 256
+KSET_MAX_WALK_BUDGET = 65536
+WALK_NONE, WALK_UNIQUE, WALK_AMBIGUOUS, WALK_BUDGET, WALK_NOANCHOR = 0, 1, 2, 3, 4
+WALKS_UNTOUCHED32 = 0xFFFFFFFF
+WALKS_UNTOUCHED8 = 0xFF
+
 # hypo_gpu_kset_counts_enable / _mark / _spectrum (HYPO_KSET_MAX_TEXTS, HYPO_KSET_SPECTRUM_BINS): hist[count * 5 + min(copies, 4)]
 KSET_MAX_TEXTS = 4
 KSET_SPECTRUM_ROWS, KSET_SPECTRUM_COLS = 256, 5

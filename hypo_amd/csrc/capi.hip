@@ -1607,6 +1607,56 @@ int hypo_gpu_kset_query_fixes(const char* bytes, uint64_t n_bytes, const uint64_
     return HYPO_OK;
 }
 
+int hypo_gpu_kset_query_walks(const char* bytes, uint64_t n_bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi,
+                              uint32_t n_sites, uint32_t budget, uint32_t* status, uint32_t* steps, uint32_t* len, uint8_t* walk) {
+    HYPO_KSET_ENTRY();
+    if (!n_sites) return HYPO_OK;
+    if (!bytes || !from || !to || !dlo || !dhi || !status || !steps || !len || !walk) return fail(HYPO_E_INVALID, "NULL buffer");
+    static_assert(hypo::KSET_MAX_WALK == HYPO_KSET_MAX_WALK && hypo::KSET_MAX_WALK_BUDGET == HYPO_KSET_MAX_WALK_BUDGET, "the header's limits");
+    // everything is checked before a buffer is touched: the kernel trusts what it is given
+    const uint32_t k = ks.k;
+    if (budget < 1 || budget > hypo::KSET_MAX_WALK_BUDGET) return fail(HYPO_E_INVALID, "budget = %u out of range 1..%u (HYPO_KSET_MAX_WALK_BUDGET)", budget, hypo::KSET_MAX_WALK_BUDGET);
+    for (uint32_t s = 0; s < n_sites; ++s) {
+        if (n_bytes < k || from[s] > n_bytes - k || to[s] > n_bytes - k)
+            return fail(HYPO_E_INVALID, "site %u: the anchors at %llu and %llu (k = %u) do not lie inside %llu bytes", s, (unsigned long long)from[s], (unsigned long long)to[s], k,
+                        (unsigned long long)n_bytes);
+        if (dlo[s] < 1 || dlo[s] > dhi[s] || dhi[s] > hypo::KSET_MAX_WALK)
+            return fail(HYPO_E_INVALID, "site %u: 1 <= dlo <= dhi <= %u (HYPO_KSET_MAX_WALK) does not hold for %u .. %u", s, hypo::KSET_MAX_WALK, dlo[s], dhi[s]);
+    }
+    hipStream_t st = g_ctx.stream;
+    // ks.in: bytes.  ks.off: from | to | dlo | dhi.  ks.res: status | steps | len | walk.  Every section starts at a multiple of 256 bytes.
+    Carver co, cr;
+    const size_t o_from = co.take((size_t)n_sites * 8), o_to = co.take((size_t)n_sites * 8), o_dlo = co.take((size_t)n_sites * 4), o_dhi = co.take((size_t)n_sites * 4);
+    const size_t r_st = cr.take((size_t)n_sites * 4), r_steps = cr.take((size_t)n_sites * 4), r_len = cr.take((size_t)n_sites * 4),
+                 r_walk = cr.take((size_t)n_sites * hypo::KSET_MAX_WALK);
+    HIP_TRY(ks.in.alloc(n_bytes));
+    HIP_TRY(ks.off.alloc(co.at));
+    HIP_TRY(ks.res.alloc(cr.at));
+    char* d_off = (char*)ks.off.p; char* d_res = (char*)ks.res.p;
+    HIP_TRY(h2d(ks.in.p, bytes, n_bytes, st));
+    HIP_TRY(h2d(d_off + o_from, from, (size_t)n_sites * 8, st));
+    HIP_TRY(h2d(d_off + o_to, to, (size_t)n_sites * 8, st));
+    HIP_TRY(h2d(d_off + o_dlo, dlo, (size_t)n_sites * 4, st));
+    HIP_TRY(h2d(d_off + o_dhi, dhi, (size_t)n_sites * 4, st));
+    HIP_TRY(hypo::kset_walks_run((const uint8_t*)ks.in.p, (const uint64_t*)(d_off + o_from), (const uint64_t*)(d_off + o_to), (const uint32_t*)(d_off + o_dlo),
+                                 (const uint32_t*)(d_off + o_dhi), n_sites, budget, k, ks.table, ks.slots, (uint32_t*)(d_res + r_st), (uint32_t*)(d_res + r_steps),
+                                 (uint32_t*)(d_res + r_len), (uint8_t*)(d_res + r_walk), ks.planes, ks.min_count, st));
+    // through host buffers of the call's own: of a walk only its len bytes reach the caller, what lies beyond them stays as it was
+    std::vector<uint32_t> h_st(n_sites), h_steps(n_sites), h_len(n_sites);
+    std::vector<uint8_t> h_walk((size_t)n_sites * hypo::KSET_MAX_WALK);
+    HIP_TRY(d2h(h_st.data(), d_res + r_st, (size_t)n_sites * 4, st));
+    HIP_TRY(d2h(h_steps.data(), d_res + r_steps, (size_t)n_sites * 4, st));
+    HIP_TRY(d2h(h_len.data(), d_res + r_len, (size_t)n_sites * 4, st));
+    HIP_TRY(d2h(h_walk.data(), d_res + r_walk, h_walk.size(), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t s = 0; s < n_sites; ++s) {
+        status[s] = h_st[s]; steps[s] = h_steps[s]; len[s] = h_len[s];
+        const uint32_t n = h_len[s] <= hypo::KSET_MAX_WALK ? h_len[s] : 0;
+        for (uint32_t i = 0; i < n; ++i) walk[(size_t)s * hypo::KSET_MAX_WALK + i] = h_walk[(size_t)s * hypo::KSET_MAX_WALK + i];
+    }
+    return HYPO_OK;
+}
+
 // ---- read counts, copy numbers and the spectrum (hypo --qv-spectra) ---------------------------------------------------------------
 int hypo_gpu_kset_counts_enable(uint32_t n_texts) {
     HYPO_KSET_ENTRY();

@@ -4,6 +4,7 @@
 #include "SolidBuild.hpp"
 #include "EditVcf.hpp"
 #include "KmerGuard.hpp"
+#include "KmerBridge.hpp"
 #include "KmerFix.hpp"
 #include "QvReport.hpp"
 #include "ReadKmerSet.hpp"
@@ -19,7 +20,7 @@
 namespace hypo {
 extern std::atomic<uint64_t> g_stage_counters[5];      // host/Contig.cpp
 
-// --vcf, --qv, --qv-bed, --qv-spectra, --kmer-guard, --kmer-fix: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
+// --vcf, --qv, --qv-bed, --qv-spectra, --kmer-guard, --kmer-fix, --kmer-bridge: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
 struct Extras {
     EditScriptsFn edit_fn = nullptr, guard_edit_fn = nullptr;
     ReadKmerSet set;                                       // the k-mers of the reads, on context 0 from bind_extras to commit_outputs
@@ -27,12 +28,13 @@ struct Extras {
     KmerGuard guard{set};
     SpectraReport spectra{set};
     KmerFix fix{set};
-    bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false, fix_on = false;
+    KmerBridge bridge{set};
+    bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false, fix_on = false, bridge_on = false;
     uint32_t min_given = 1;                                // --qv-min-count: 1 = off, 0 = the valley
     bool min_on() const { return min_given != 1; }
     bool ask_on = false;                                   // --qv or --qv-bed: every contig's texts are put to the set
     bool text_on = false;                                  // ... or --qv-spectra: every contig's texts are needed as strings
-    bool set_on = false;                                   // ... or --kmer-guard or --kmer-fix: the set is built
+    bool set_on = false;                                   // ... or --kmer-guard, --kmer-fix or --kmer-bridge: the set is built
     ReadSink set_sink;                                     // (holds a pointer to set: an Extras stays where it is)
     VcfStats vstats;
     Extras() = default; Extras(const Extras&) = delete;
@@ -175,6 +177,7 @@ void Hypo::polish() {
 // ---- once per run, before the batches ----------------------------------------------------------------------------------------
 void Hypo::bind_extras(Extras& ex) {
     ex.fix_on = !_cFlags.kmer_fix_filename.empty();
+    ex.bridge_on = !_cFlags.kmer_bridge_filename.empty();
     ex.min_given = _cFlags.qv_min_count;
     ex.spectra_on = !_cFlags.qv_spectra_filename.empty();
     ex.bed_on = !_cFlags.qv_bed_filename.empty();
@@ -182,11 +185,16 @@ void Hypo::bind_extras(Extras& ex) {
     ex.qv_on = !_cFlags.qv_filename.empty();
     ex.ask_on = ex.qv_on || ex.bed_on;
     ex.text_on = ex.ask_on || ex.spectra_on;
-    ex.set_on = ex.text_on || ex.guard_on || ex.fix_on;
+    ex.set_on = ex.text_on || ex.guard_on || ex.fix_on || ex.bridge_on;
     // Every entry point behind these flags is bound by name, and only under its flag, so that libraries without it still serve every
     // run without the flag.  The flags are checked in this order, and each one's error names what it needs.
     const bool have_set = (ex.set_on || ex.min_on()) && ex.set.bind();
     const std::string the_set = ReadKmerSet::kNames;
+    // --kmer-bridge: the walks query and the track query, and the set they ask
+    if (ex.bridge_on) {
+        require("--kmer-bridge", {{" hypo_gpu_kset_query_walks", ex.bridge.bind()}, {" hypo_gpu_kset_query_track", ex.set.bind_track()}, {" " + the_set, have_set}}, true);
+        ex.bridge.configure(_cFlags.kmer_bridge_max, _cFlags.kmer_bridge_slack);
+    }
     // --kmer-fix: the fixes query and the track query, and the set they ask
     if (ex.fix_on)
         require("--kmer-fix", {{" hypo_gpu_kset_query_fixes", ex.fix.bind()}, {" hypo_gpu_kset_query_track", ex.set.bind_track()}, {" " + the_set, have_set}}, true);
@@ -737,16 +745,23 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
     // Every contig takes one path.  Its source: under --kmer-guard the batch's records are made first, their clusters judged by the
     // set, and the contig comes as its draft, the draft with the accepted records applied, and the records with the rejected ones
     // marked; otherwise as its draft and its polished text.  --kmer-fix: the text goes through the fixes, and what comes back takes
-    // its place.  Its sink: the FASTA record, and both texts to the reports (the set's queries on context 0, the marks).
+    // its place; --kmer-bridge: that text goes through the bridges, likewise.  Its sink: the FASTA record, and both texts to the reports (the set's queries on context 0, the marks).
     const char* stage = "k-mer set query";
-    int rc = ex.text_on || ex.fix_on ? hypo_gpu_use_device(0) : HYPO_OK;
+    int rc = ex.text_on || ex.fix_on || ex.bridge_on ? hypo_gpu_use_device(0) : HYPO_OK;
     const KmerFix::Emit file_text = [&](uint32_t c, const std::string& draft, const std::string& text) {
         ofile << ">" << _contigs[c]->get_name() << std::endl << text << std::endl;      // (operator<<'s bytes)
         return ex.texts(c, draft, text);
     };
+    // (what the fixes hand on: to the bridges when they are on, to the file otherwise)
+    const KmerFix::Emit bridge_text = [&](uint32_t c, const std::string& draft, const std::string& text) {
+        return ex.bridge.push(c, _contigs[c]->get_name(), draft, text, file_text);
+    };
+    const KmerFix::Emit& fixed_text = ex.bridge_on ? bridge_text : file_text;
     auto text_out = [&](uint32_t c, auto&& draft, auto&& text) {
-        if (!ex.fix_on) return file_text(c, draft, text);
-        return ex.fix.push(c, _contigs[c]->get_name(), ex.text_on ? std::string(std::forward<decltype(draft)>(draft)) : std::string(), std::forward<decltype(text)>(text), file_text);
+        if (!ex.fix_on && !ex.bridge_on) return file_text(c, draft, text);
+        std::string d = ex.text_on ? std::string(std::forward<decltype(draft)>(draft)) : std::string();
+        if (!ex.fix_on) return ex.bridge.push(c, _contigs[c]->get_name(), std::move(d), std::forward<decltype(text)>(text), file_text);
+        return ex.fix.push(c, _contigs[c]->get_name(), std::move(d), std::forward<decltype(text)>(text), fixed_text);
     };
     // the VCF records while the contig's windows exist, then the windows go; recs: the guard's, with which of them it rejected
     auto records_out = [&](uint32_t c, const VcfContigRecords* recs, const std::vector<uint8_t>* rejected) {
@@ -762,8 +777,9 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
                 records_out(c, &recs, &rejected);
                 return text_out(c, draft, text);
             });
-    } else if (ex.text_on || ex.fix_on) {
+    } else if (ex.text_on || ex.fix_on || ex.bridge_on) {
         if (ex.fix_on) stage = "k-mer fix / k-mer set query";
+        else if (ex.bridge_on) stage = "k-mer bridge / k-mer set query";
         for (uint32_t c = initial_cid; c < final_cid && rc == HYPO_OK; ++c) {
             std::string text = _contigs[c]->polished_text();
             std::string draft = ex.text_on ? _contigs[c]->draft_segment(0, (uint32_t)_contigs[c]->get_len()) : std::string();
@@ -774,7 +790,8 @@ void Hypo::write_batch(WriterJob job, Extras& ex, RunOutputs& out) {
         // the plain run: the record is streamed, no report wants its text
         for (uint32_t c = initial_cid; c < final_cid; ++c) { ofile << *_contigs[c]; records_out(c, nullptr, nullptr); }
     }
-    if (rc == HYPO_OK && ex.fix_on) { stage = "k-mer fix / k-mer set query"; rc = ex.fix.flush(file_text); }
+    if (rc == HYPO_OK && ex.fix_on) { stage = "k-mer fix / k-mer set query"; rc = ex.fix.flush(fixed_text); }
+    if (rc == HYPO_OK && ex.bridge_on) { stage = "k-mer bridge / k-mer set query"; rc = ex.bridge.flush(file_text); }
     if (rc == HYPO_OK) { stage = "k-mer set query"; rc = ex.texts_flush(); }
     if (rc != HYPO_OK) writer_fatal(stage);
 }
@@ -789,6 +806,7 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         ex.spectra.write(out.open_spectra(_cFlags.qv_spectra_filename));
     }
     if (ex.fix_on) ex.fix.write(out.open_fixes(_cFlags.kmer_fix_filename));
+    if (ex.bridge_on) ex.bridge.write(out.open_bridges(_cFlags.kmer_bridge_filename));
     // the set has answered its last query
     if (ex.set_on) ex.set.end();
     // --qv, --qv-bed: the table and the track are formatted once, closed and checked like the others
@@ -827,6 +845,13 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
             std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer fix %s (k = %u): %llu intervals, %llu sites, %llu fixed (%llu sub, %llu del, %llu ins), %llu ambiguous, %llu missing k-mers removed\n",
                          _cFlags.kmer_fix_filename.c_str(), ex.fix.k(), (unsigned long long)fs.intervals, (unsigned long long)fs.sites, (unsigned long long)fs.fixed,
                          (unsigned long long)fs.sub, (unsigned long long)fs.del, (unsigned long long)fs.ins, (unsigned long long)fs.ambiguous, (unsigned long long)fs.removed);
+        }
+        if (w == RunOutputs::BRIDGES) {
+            const KmerBridge::Stats& bs = ex.bridge.stats();
+            std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer bridge %s (k = %u, max %u, slack %u): %llu intervals, %llu sites, %llu bridged (%llu bases out, %llu bases in), %llu ambiguous, "
+                                 "%llu over budget, %llu missing k-mers removed\n", _cFlags.kmer_bridge_filename.c_str(), ex.bridge.k(), ex.bridge.max_dist(), ex.bridge.slack(),
+                         (unsigned long long)bs.intervals, (unsigned long long)bs.sites, (unsigned long long)bs.bridged, (unsigned long long)bs.bases_out,
+                         (unsigned long long)bs.bases_in, (unsigned long long)bs.ambiguous, (unsigned long long)bs.over_budget, (unsigned long long)bs.removed);
         }
         if (w == RunOutputs::BED) {
             const QvReport::TrackSums ts = ex.qv.track_sums();

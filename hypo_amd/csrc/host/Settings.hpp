@@ -36,6 +36,9 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     uint32_t qv_reliable_min = 0;          // new, opt-in: --qv-reliable-min (1..255: the least read count of a reliable k-mer; 0 = the valley of the read histogram)
     uint32_t qv_min_count = 1;             // new, opt-in: --qv-min-count (1..255, 0 = valley: a read k-mer counts for --qv, --qv-bed and the guards when the reads have it this often; 1 = presence, the run without the flag)
     std::string kmer_fix_filename;         // new, opt-in: --kmer-fix <file> (one pass of single-base fixes the read k-mers pin down, listed in the file)
+    std::string kmer_bridge_filename;      // new, opt-in: --kmer-bridge <file> (one pass of local reassembly between k-mers of the reads, listed in the file)
+    uint32_t kmer_bridge_max = 64;         // new, opt-in: --kmer-bridge-max (2..192: the largest anchor distance tried)
+    uint32_t kmer_bridge_slack = 8;        // new, opt-in: --kmer-bridge-slack (0..64: the most bases a bridge may add or remove)
     uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
 };
 

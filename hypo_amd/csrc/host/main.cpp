@@ -34,7 +34,8 @@ const struct option long_options[] = {
     {"guard-records", no_argument, nullptr, 1012}, {"guard-records-max", required_argument, nullptr, 1013},
     {"qv-bed", required_argument, nullptr, 1014}, {"qv-spectra", required_argument, nullptr, 1015},
     {"qv-reliable-min", required_argument, nullptr, 1016}, {"qv-min-count", required_argument, nullptr, 1017},
-    {"kmer-fix", required_argument, nullptr, 1018}, {nullptr, 0, nullptr, 0}};
+    {"kmer-fix", required_argument, nullptr, 1018}, {"kmer-bridge", required_argument, nullptr, 1019},
+    {"kmer-bridge-max", required_argument, nullptr, 1020}, {"kmer-bridge-slack", required_argument, nullptr, 1021}, {nullptr, 0, nullptr, 0}};
 
 // Same layout as the reference's usage() (src/main.cpp:363-430): "Usage: hypo <args>", the mandatory block, the optional
 // block, every flag as "-x, --long <type>" followed by what it does and its default.  The wording is this build's own.
@@ -80,6 +81,9 @@ void usage() {
         {"    --qv-reliable-min <int>", "[MI355X build] Least number of times the short reads must contain a k-mer for it to count as reliable in the completeness of --qv-spectra, 1 to 255.", "the valley of the read k-mer histogram: the smallest multiplicity from 2 on at which it stops falling"},
         {"    --qv-min-count <int|valley>", "[MI355X build] Count a read k-mer only when the short reads contain it at least this often, 1 to 255, or `valley`: the valley of the read k-mer histogram, the default of --qv-reliable-min. A k-mer seen fewer times is mostly a sequencing error and then counts as missing wherever the reads are asked: in the missing columns and QVs of --qv, the intervals of --qv-bed, and the decisions of --kmer-guard and --guard-records. Needs at least one of those four; 1 is the run without the flag. The k-mer set then counts as for --qv-spectra (one more byte a slot under --qv-mem), whose file does not change.", "1: a k-mer seen once is present"},
         {"    --kmer-fix <str>", "[MI355X build] Make one pass of single-base fixes over the text that would otherwise be written (with --kmer-guard the guarded text), where the k-mers of the short reads pin an isolated error down: a stretch of at most 2k - 1 bases in which every k-mer is one no read contains, at least k - 1 bases from the next such stretch and not at a contig end, is tried with every substitution, deletion and insertion of one base at the positions all its k-mers share, and fixed when exactly one of the edited texts lacks no k-mer of the reads; two such texts (a heterozygous base, a read error) leave it alone. The file lists the fixes, tab-separated: contig, pos (0-based, in the text before the fixes), kind (sub, del, ins), ref, alt, and the missing k-mers the fix removes. --qv, --qv-bed and --qv-spectra then describe the fixed text; --vcf still describes the text before the fixes. Uses the k-mer set of --qv (--qv-k, --qv-mem, --qv-min-count) with or without the other flags; the edits are tried on the device.", "no fixes"},
+        {"    --kmer-bridge <str>", "[MI355X build] Make one pass of local reassembly over the text that would otherwise be written (after --kmer-guard and --kmer-fix), where the k-mers of the short reads spell exactly one other text: a stretch under k-mers no read contains, at least 2 bases from the next such stretch and not at a contig end, lies between two k-mers the reads do contain, one base in front of it and one behind it. When those two anchors are at most --kmer-bridge-max bases apart, the k-mers of the reads are walked as a de Bruijn graph from the left anchor to the right one, letting the stretch grow or shrink by up to --kmer-bridge-slack bases, and when exactly one walk arrives its text replaces the stretch; several walks (a heterozygous site, a repeat) or a search that gives up leave it alone. This reaches what --kmer-fix leaves behind: length errors of two or more bases in homopolymers and short tandem repeats, substitutions closer than k, an indel next to a substitution. The file lists the bridges, tab-separated: contig, pos (0-based, in the text before this pass), ref, alt (`.` when empty), the missing k-mers the bridge removes, and the steps of the search. --qv, --qv-bed and --qv-spectra then describe the bridged text; --vcf still describes the text before the fixes and bridges. Uses the k-mer set of --qv (--qv-k, --qv-mem, --qv-min-count) with or without the other flags; the graph is walked on the device.", "no bridges"},
+        {"    --kmer-bridge-max <int>", "[MI355X build] Largest distance of the two anchors --kmer-bridge still tries, 2 to 192 bases. Needs --kmer-bridge.", "64"},
+        {"    --kmer-bridge-slack <int>", "[MI355X build] Most bases a bridge of --kmer-bridge may add to or remove from the stretch it replaces, 0 to 64. Needs --kmer-bridge.", "8"},
         {"-h, --help", "Print the usage.", nullptr}};
     std::printf("\n Usage: hypo <args>\n\n ** Mandatory args:\n");
     for (const auto& e : mandatory) std::printf("\t%s\n\t%s\n\n", e.flag, e.what);
@@ -143,6 +147,13 @@ int main(int argc, char** argv) {
     bool is_sr = false, is_draft = false, is_size = false, is_cov = false, is_bamsr = false;
     std::string given_sz, kind = "sr";
     int opt;
+    bool bridge_opts = false;                                              // --kmer-bridge-max or --kmer-bridge-slack was given
+    auto int_in = [](const char* flag, const char* arg, long lo, long hi) {
+        char* end = nullptr;
+        const long v = std::strtol(arg, &end, 10);
+        if (end == arg || *end || v < lo || v > hi) { std::fprintf(stderr, "[Hypo::] Error: Arg Error: %s must be between %ld and %ld %s!\n", flag, lo, hi, arg); std::exit(1); }
+        return (uint32_t)v;
+    };
     auto need_file = [](const char* what, const std::string& p) {
         if (!file_exists(p)) { std::fprintf(stderr, "[Hypo::] Error: File Error: %s file does not exist %s!\n", what, p.c_str()); std::exit(1); }
     };
@@ -217,6 +228,9 @@ int main(int argc, char** argv) {
                 flags.qv_min_count = valley ? 0 : (uint32_t)v; break;                // (0: the valley, found when the reads are in)
             }
             case 1018: flags.kmer_fix_filename = optarg; break;
+            case 1019: flags.kmer_bridge_filename = optarg; break;
+            case 1020: flags.kmer_bridge_max = int_in("--kmer-bridge-max", optarg, 2, 192); bridge_opts = true; break;
+            case 1021: flags.kmer_bridge_slack = int_in("--kmer-bridge-slack", optarg, 0, 64); bridge_opts = true; break;
             case 1002: {
                 flags.devices.clear();
                 for (const char* c = optarg; *c;) { flags.devices.push_back(std::atoi(c)); while (*c && *c != ',') ++c; if (*c == ',') ++c; }
@@ -225,8 +239,13 @@ int main(int argc, char** argv) {
             default: usage(); return 0;                                    // -h and unknown options alike (src/main.cpp:302-304)
         }
     }
-    if (flags.qv_min_count != 1 && flags.qv_filename.empty() && flags.qv_bed_filename.empty() && !flags.kmer_guard && flags.kmer_fix_filename.empty()) {   // (1 is the run without the flag)
+    if (flags.qv_min_count != 1 && flags.qv_filename.empty() && flags.qv_bed_filename.empty() && !flags.kmer_guard && flags.kmer_fix_filename.empty() &&
+        flags.kmer_bridge_filename.empty()) {   // (1 is the run without the flag)
         std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-min-count changes what --qv, --qv-bed, --kmer-guard, --guard-records and --kmer-fix ask the reads: it needs at least one of them!\n");
+        std::exit(1);
+    }
+    if (bridge_opts && flags.kmer_bridge_filename.empty()) {
+        std::fprintf(stderr, "[Hypo::] Error: Arg Error: --kmer-bridge-max and --kmer-bridge-slack set how --kmer-bridge searches: they need --kmer-bridge!\n");
         std::exit(1);
     }
     if (!(is_sr && is_draft && is_size && is_bamsr && is_cov)) {

@@ -19,6 +19,8 @@
 //     with another source of bytes.
 //   * kset_fixes_kernel / kset_fixes_reduce_kernel (below, with comments of their own; hypo --kmer-fix): every one-base edit of many
 //     short regions, a group per candidate, ks_group_scan once more, and a lane per site that picks the best candidate.
+//   * kset_walks_kernel (below, with comments of its own; hypo --kmer-bridge): the set as a de Bruijn graph, a depth-first search
+//     between two anchors per site, 4 lanes a site, dependent probes, the stack in LDS.
 //   * counts (hypo --qv-spectra; further down, with comments of their own): a count byte and up to four copy bytes per slot in planes
 //     beside the table, a saturating byte add that serves both, and the counted variants of the insert and rehash kernels, the mark
 //     kernel (the query body with a probe that returns the slot) and the spectrum kernel.
@@ -877,6 +879,140 @@ hipError_t kset_fixes_run(const uint8_t* bytes, const uint64_t* site_lo, const u
     kset_fixes_reduce_kernel<<<dim3((n_sites + KS_THREADS - 1) / KS_THREADS), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_c0, site_w, item_off, item_res, n_sites, none_total,
                                                                                                            none_missing, best_cand, best_total, best_missing, zeros,
                                                                                                            cand_total, cand_missing);
+    return hipGetLastError();
+}
+
+// ---- walks between two anchors (hypo --kmer-bridge; DESIGN.md "k-mer bridge") ----------------------------------------------------------
+// The set as a de Bruijn graph: a k-mer's children are the four k-mers that drop its first base and append one, those of them
+// whose canonical code the set holds.  Site s asks for the walks from L = bytes[from, from + k) that arrive at R = bytes[to, to + k)
+// after dlo .. dhi steps, a walk ending at its first arrival in that range.  The search is the depth-first one of include/hypo_gpu.h,
+// children in ACGT order, every visit counted, and it answers NONE, UNIQUE, AMBIGUOUS (a second walk arrived), BUDGET (more than
+// `budget` visits) or NOANCHOR (an anchor holds a byte that is no base), with the visits made and the first walk's bases.
+// A group of 4 lanes owns a site, a wave 16 sites, a workgroup 64.  All four lanes carry the same state (depth, the forward and
+// reverse-complement codes of the k-mer the group stands on, the counters), so every branch on it is uniform within the group.
+// When the group steps onto a k-mer, lane b rolls child b as KmerRoll does, takes the canonical code and probes the table; the
+// group's four bits of one wave-wide ballot are the children that exist.  The stack is one byte per depth in LDS: the children not
+// tried yet in bits 0..3, the base taken last in bits 4..5.  Every lane of the group stores and loads the same bytes, so no lane
+// reads what another wrote.  On a backtrack the parent's codes come back in one step from the child's: the base that fell off the
+// front is base d - 1 of L + the path, which L's code or the stack still holds.  The first walk that arrives is copied from the
+// stack to walk[] by the group, a byte per lane and pass, with plain stores.  No atomics, no scratch.
+// The loop is wave-uniform: an iteration expands the groups that stepped onto a k-mer (the probes, one ballot), then every group
+// takes its next untried child (a visit) or, with none left, steps back.  A wave runs as long as its slowest site.
+// Bounds: a site makes at most `budget` <= KSET_MAX_WALK_BUDGET visits and no more steps back than visits, so the loop ends after
+// at most 2 budget + 2 iterations; a probe takes at most `slots` steps; depth <= dhi <= KSET_MAX_WALK = 256, the stack is indexed
+// at depth < dhi (a k-mer at depth dhi is never expanded), below KS_WALK_STACK; walk[] is written at [s * 256, s * 256 + len),
+// len <= dhi; bytes are read at [from, from + k) and [to, to + k), which the caller checked to lie inside the text; status / steps
+// / len are indexed below n_sites.
+constexpr int KS_WALK_LANES = 4;                                // lanes per site: one per child
+constexpr int KS_WALK_SITES = KS_THREADS / KS_WALK_LANES;       // sites per workgroup
+constexpr int KS_WALK_STACK = 260;                              // bytes per site: 256 depths, padded so that the sites of a wave fall into different banks
+enum { KS_WALK_NONE = 0, KS_WALK_UNIQUE = 1, KS_WALK_AMBIGUOUS = 2, KS_WALK_BUDGET = 3, KS_WALK_NOANCHOR = 4 };
+
+// the forward and reverse-complement codes of bytes[at, at + k); false when one of them is no base
+__device__ __forceinline__ bool ks_anchor(const uint8_t* __restrict__ bytes, uint64_t at, uint32_t k, uint64_t& fwd, uint64_t& rc) {
+    fwd = rc = 0;
+    bool ok = true;
+    for (uint32_t i = 0; i < k; ++i) {
+        const uint32_t c = base_code(bytes[at + i]);
+        ok = ok && c < 4;
+        fwd = (fwd << 2) | (c & 3u);
+        rc = (rc >> 2) | ((uint64_t)(3u - (c & 3u)) << (2 * (k - 1)));
+    }
+    return ok;
+}
+
+template <bool MIN>
+__device__ __forceinline__ void ks_walks_body(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ from, const uint64_t* __restrict__ to,
+                                              const uint32_t* __restrict__ dlo, const uint32_t* __restrict__ dhi, uint32_t n_sites, uint32_t budget,
+                                              uint32_t k, const uint64_t* __restrict__ table, uint64_t slots, uint32_t* __restrict__ status,
+                                              uint32_t* __restrict__ steps_out, uint32_t* __restrict__ len_out, uint8_t* __restrict__ walk,
+                                              const uint8_t* __restrict__ counts, uint32_t t) {
+    __shared__ uint8_t stacks[KS_WALK_SITES * KS_WALK_STACK];
+    const uint32_t lane = threadIdx.x & 63, b = lane & (KS_WALK_LANES - 1), gshift = lane & ~(uint32_t)(KS_WALK_LANES - 1);
+    const uint64_t site = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / KS_WALK_LANES;
+    uint8_t* const stack = stacks + (threadIdx.x / KS_WALK_LANES) * KS_WALK_STACK;
+    const bool have = site < n_sites;
+    const uint64_t mask = (1ull << (2 * k)) - 1;
+    const uint32_t rsh = 2 * (k - 1);
+    uint64_t lf = 0, lr = 0, rf = 0, rr = 0, fwd = 0, rc = 0;
+    uint32_t lo = 0, hi = 0, st = KS_WALK_NONE, steps = 0, found = 0, len = 0, d = 0;
+    bool done = true, expand = false;
+    if (have) {
+        lo = dlo[site]; hi = dhi[site];
+        const bool ok_l = ks_anchor(bytes, from[site], k, lf, lr), ok_r = ks_anchor(bytes, to[site], k, rf, rr);
+        if (ok_l && ok_r) { done = false; expand = true; steps = 1; fwd = lf; rc = lr; }     // the visit of L: depth 0 < dlo, no arrival
+        else st = KS_WALK_NOANCHOR;
+    }
+    while (__any(!done)) {
+        // the groups that stepped onto a k-mer: which of its children does the set hold?
+        bool hit = false;
+        if (!done && expand) {
+            const uint64_t yf = ((fwd << 2) | b) & mask, yr = (rc >> 2) | ((uint64_t)(3u - b) << rsh);
+            const uint64_t key = yf < yr ? yf : yr;
+            hit = MIN ? ks_contains_min(table, slots, counts, key, t) : ks_contains(table, slots, key);
+        }
+        const uint32_t kids = (uint32_t)(__ballot(hit) >> gshift) & 15u;
+        if (done) continue;
+        if (expand) { stack[d] = (uint8_t)kids; expand = false; }
+        const uint32_t m = stack[d] & 15u;
+        if (!m) {                                               // every child tried: one step back, or the search is over
+            if (!d) { done = true; continue; }
+            const uint32_t i = d - 1;                           // the base that fell off when the group stepped here: base i of L + path
+            const uint32_t c = i < k ? (uint32_t)(lf >> (2 * (k - 1 - i))) & 3u : ((uint32_t)stack[i - k] >> 4) & 3u;
+            fwd = (fwd >> 2) | ((uint64_t)c << rsh);
+            rc = ((rc << 2) | (3u - c)) & mask;
+            d = i;
+            continue;
+        }
+        const uint32_t c = (uint32_t)__ffs(m) - 1;
+        stack[d] = (uint8_t)((m & (m - 1)) | (c << 4));
+        const uint64_t yf = ((fwd << 2) | c) & mask;
+        if (++steps > budget) { st = KS_WALK_BUDGET; done = true; continue; }
+        if (d + 1 >= lo && yf == rf) {                           // an arrival ends the walk
+            if (++found == 2) { st = KS_WALK_AMBIGUOUS; done = true; continue; }
+            len = d + 1;
+            for (uint32_t x = b; x < len; x += KS_WALK_LANES) walk[site * KSET_MAX_WALK + x] = (uint8_t)ks_base_char(((uint32_t)stack[x] >> 4) & 3u);
+            continue;
+        }
+        if (d + 1 == hi) continue;
+        fwd = yf; rc = (rc >> 2) | ((uint64_t)(3u - c) << rsh);
+        ++d; expand = true;
+    }
+    if (have && b == 0) {
+        if (st == KS_WALK_NONE && found) st = KS_WALK_UNIQUE;
+        if (st == KS_WALK_BUDGET) len = 0;
+        status[site] = st; steps_out[site] = steps; len_out[site] = len;
+    }
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_walks_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ from,
+                                                                 const uint64_t* __restrict__ to, const uint32_t* __restrict__ dlo,
+                                                                 const uint32_t* __restrict__ dhi, uint32_t n_sites, uint32_t budget, uint32_t k,
+                                                                 const uint64_t* __restrict__ table, uint64_t slots, uint32_t* __restrict__ status,
+                                                                 uint32_t* __restrict__ steps, uint32_t* __restrict__ len, uint8_t* __restrict__ walk) {
+    ks_walks_body<false>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, status, steps, len, walk, nullptr, 1);
+}
+
+// kset_walks_kernel against R_t (hypo --qv-min-count; the section "a least count" above)
+__global__ void __launch_bounds__(KS_THREADS) kset_walks_min_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ from,
+                                                                     const uint64_t* __restrict__ to, const uint32_t* __restrict__ dlo,
+                                                                     const uint32_t* __restrict__ dhi, uint32_t n_sites, uint32_t budget, uint32_t k,
+                                                                     const uint64_t* __restrict__ table, uint64_t slots, uint32_t* __restrict__ status,
+                                                                     uint32_t* __restrict__ steps, uint32_t* __restrict__ len, uint8_t* __restrict__ walk,
+                                                                     const uint8_t* __restrict__ counts, uint32_t t) {
+    ks_walks_body<true>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, status, steps, len, walk, counts, t);
+}
+
+hipError_t kset_walks_run(const uint8_t* bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites,
+                          uint32_t budget, uint32_t k, const uint64_t* table, uint64_t slots, uint32_t* status, uint32_t* steps, uint32_t* len, uint8_t* walk,
+                          const uint32_t* planes, uint32_t min_count, hipStream_t st) {
+    if (!n_sites) return hipSuccess;
+    static_assert(KSET_MAX_WALK <= KS_WALK_STACK, "a stack byte per depth");
+    const uint32_t blocks = (n_sites + KS_WALK_SITES - 1) / KS_WALK_SITES;
+    if (min_count > 1)
+        kset_walks_min_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, status, steps, len, walk,
+                                                                         (const uint8_t*)planes, min_count);
+    else kset_walks_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, status, steps, len, walk);
     return hipGetLastError();
 }
 

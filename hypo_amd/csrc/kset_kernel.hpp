@@ -98,4 +98,16 @@ hipError_t kset_fixes_run(const uint8_t* bytes, const uint64_t* site_lo, const u
                           unsigned long long* best_missing, uint32_t* zeros, unsigned long long* cand_total, unsigned long long* cand_missing, int group,
                           const uint32_t* planes, uint32_t min_count, hipStream_t st);
 
+// Walks through the set as a de Bruijn graph (hypo --kmer-bridge; DESIGN.md "k-mer bridge"): site s starts at the k-mer
+// bytes[from[s], from[s] + k) and asks for the walks that arrive at bytes[to[s], to[s] + k) after dlo[s] .. dhi[s] steps, by the
+// depth-first search of include/hypo_gpu.h with at most `budget` visits.  status / steps / len: n_sites values each; walk: n_sites
+// * KSET_MAX_WALK bytes, the first walk's bases at walk[s * KSET_MAX_WALK, + len[s]).  The caller has checked every range (see the
+// bounds comment of the kernels): from + k and to + k inside the text, 1 <= dlo <= dhi <= KSET_MAX_WALK, 1 <= budget <=
+// KSET_MAX_WALK_BUDGET.
+constexpr uint32_t KSET_MAX_WALK = 256;
+constexpr uint32_t KSET_MAX_WALK_BUDGET = 65536;
+hipError_t kset_walks_run(const uint8_t* bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites,
+                          uint32_t budget, uint32_t k, const uint64_t* table, uint64_t slots, uint32_t* status, uint32_t* steps, uint32_t* len, uint8_t* walk,
+                          const uint32_t* planes, uint32_t min_count, hipStream_t st);
+
 }  // namespace hypo

@@ -501,6 +501,38 @@ int hypo_gpu_kset_query_fixes(const char* bytes, uint64_t n_bytes, const uint64_
                               uint64_t* none_total, uint64_t* none_missing, uint32_t* best_cand, uint64_t* best_total,
                               uint64_t* best_missing, uint32_t* zeros,
                               uint64_t* cand_total /* may be NULL */, uint64_t* cand_missing /* may be NULL */);
+/* Walks through the set as a de Bruijn graph (hypo --kmer-bridge; DESIGN.md "k-mer bridge").  Additive to ABI 11: callers bind it by
+ * name.  A general primitive: it knows nothing of intervals.  Site s has the left anchor L = bytes[from[s], from[s] + k) and the
+ * right anchor R = bytes[to[s], to[s] + k), k the set's; case is ignored.  A k-mer x has up to four children y = x[1:] + b, b in
+ * ACGT order, those whose canonical k-mer is in the set (under hypo_gpu_kset_min_count: in R_t, as for the other queries).  The
+ * answer is the result of this search and nothing else:
+ *     steps = found = 0
+ *     visit(x, depth, path):
+ *         steps += 1;  if steps > budget: stop with BUDGET
+ *         if depth >= dlo and x == R:                 (forward strings compared)
+ *             found += 1;  if found == 2: stop with AMBIGUOUS
+ *             first = path;  return                   (a walk ends at its first allowed arrival)
+ *         if depth == dhi: return
+ *         for b in A, C, G, T:  y = x[1:] + b;  if canonical(y) in the set: visit(y, depth + 1, path + b)
+ *     visit(L, 0, "");  status = UNIQUE if found == 1 else NONE
+ * L itself need not be in the set; R must be, or no walk arrives.  A k-mer may be visited more than once: cycles are bounded by dhi.
+ * status[s]: one of HYPO_WALK_*; NOANCHOR: an anchor holds a byte outside ACGTacgt.  steps[s]: the counter when the search ended,
+ * budget + 1 for BUDGET, 0 for NOANCHOR.  len[s]: for UNIQUE and AMBIGUOUS the first walk's number of steps, its bases written as
+ * ACGT bytes at walk[s * HYPO_KSET_MAX_WALK, + len[s]); 0 for NONE, BUDGET and NOANCHOR.  Bytes of walk beyond len are unspecified.
+ * Sites may repeat, overlap and come in any order; the answers depend on the input and the set alone.  HYPO_E_INVALID: from + k or
+ * to + k beyond n_bytes, dlo < 1, dlo > dhi, dhi > HYPO_KSET_MAX_WALK, budget == 0 or above HYPO_KSET_MAX_WALK_BUDGET, a NULL
+ * pointer with n_sites > 0, no set (as hypo_gpu_kset_query); a refused call changes nothing.  n_sites == 0 touches nothing.
+ * Synchronous, on the calling thread's context. */
+#define HYPO_KSET_MAX_WALK        256     /* largest dhi */
+#define HYPO_KSET_MAX_WALK_BUDGET 65536
+#define HYPO_WALK_NONE 0
+#define HYPO_WALK_UNIQUE 1
+#define HYPO_WALK_AMBIGUOUS 2
+#define HYPO_WALK_BUDGET 3
+#define HYPO_WALK_NOANCHOR 4
+int hypo_gpu_kset_query_walks(const char* bytes, uint64_t n_bytes, const uint64_t* from, const uint64_t* to,
+                              const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites, uint32_t budget,
+                              uint32_t* status, uint32_t* steps, uint32_t* len, uint8_t* walk);
 
 /* Read k-mer counts and copy numbers on the set (hypo --qv-spectra; DESIGN.md "k-mer spectra").  Additive to ABI 11: callers bind
  * the three by name.  Presence, and with it every answer of the query entry points above, is what it is without them.
@@ -528,7 +560,7 @@ int hypo_gpu_kset_mark(uint32_t text, const char* bytes, const uint64_t* off, ui
 int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist);
 /* A least count for the queries (hypo --qv-min-count; DESIGN.md "k-mer min count").  Additive to ABI 11: callers bind it by name.
  * R_t = the k-mers of the set whose count (hypo_gpu_kset_counts_enable) is at least t; R_1 is the set.  From the next call on
- * hypo_gpu_kset_query, _query_spans, _query_variants, _query_track and _query_fixes answer against R_t: a window whose k-mer the reads contain
+ * hypo_gpu_kset_query, _query_spans, _query_variants, _query_track, _query_fixes and _query_walks answer against R_t: a window whose k-mer the reads contain
  * fewer than t times is missing, and everything those entry points derive from "missing" (intervals, best masks) follows.  The
  * threshold is applied when a query runs, to the counts of that moment: it may be set any number of times, before or after adds
  * and marks, it does not close the set, and hypo_gpu_kset_add, _size, _mark and _spectrum do not know of it.  hypo_gpu_kset_begin
