@@ -33,6 +33,9 @@ KSET_MAX_WALK_BUDGET = 65536
 WALK_NONE, WALK_UNIQUE, WALK_AMBIGUOUS, WALK_BUDGET, WALK_NOANCHOR = 0, 1, 2, 3, 4
 WALKS_UNTOUCHED32 = 0xFFFFFFFF
 WALKS_UNTOUCHED8 = 0xFF
+# hypo_gpu_kset_query_walk_sets (HYPO_KSET_MAX_WALKS, HYPO_WALK_MANY); the sentinels are those above
+KSET_MAX_WALKS = 4
+WALK_MANY = 5
 
 # hypo_gpu_kset_counts_enable / _mark / _spectrum (HYPO_KSET_MAX_TEXTS, HYPO_KSET_SPECTRUM_BINS): hist[count * 5 + min(copies, 4)]
 KSET_MAX_TEXTS = 4

@@ -31,7 +31,7 @@ EXPORTS = [
     "hypo_gpu_kmer_count_end", "hypo_gpu_edit_scripts", "hypo_gpu_edit_last_counts",
     "hypo_gpu_kset_begin", "hypo_gpu_kset_add", "hypo_gpu_kset_size", "hypo_gpu_kset_query", "hypo_gpu_kset_end",
     "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants", "hypo_gpu_kset_query_track", "hypo_gpu_kset_query_fixes",
-    "hypo_gpu_kset_query_walks",
+    "hypo_gpu_kset_query_walks", "hypo_gpu_kset_query_walk_sets",
     "hypo_gpu_kset_counts_enable", "hypo_gpu_kset_mark", "hypo_gpu_kset_spectrum", "hypo_gpu_kset_min_count",
 ]
 KSET_SPAN_PIECE = 2048        # windows per piece of a long span (kset_kernel.hpp)
@@ -437,6 +437,33 @@ class HypoGpu:
         dhi[s] steps, by the depth-first search of include/hypo_gpu.h with at most `budget` visits.  (status, steps, len, walk): one of
         abi.WALK_*, the visits made, and the first walk's length and bases (walk[s, :len[s]])."""
         out = self.kset_query_walks_rc(data, frm, to, dlo, dhi, budget)
+        self._check(out[0])
+        return out[1:]
+
+    def kset_query_walk_sets_rc(self, data, frm, to, dlo, dhi, budget):
+        """(return code, status u32[n], steps u32[n], n_walks u32[n], len u32[n, W], low u32[n, W], walk u8[n, W, abi.KSET_MAX_WALK]) of
+        hypo_gpu_kset_query_walk_sets, W = abi.KSET_MAX_WALKS; nothing is checked here.  Every output is filled with
+        abi.WALKS_UNTOUCHED32 / 8 before the call."""
+        a = np.frombuffer(bytes(data), dtype=np.uint8) if not isinstance(data, np.ndarray) else np.ascontiguousarray(data, dtype=np.uint8)
+        frm, to = (np.ascontiguousarray(x, dtype=np.uint64) for x in (frm, to))
+        dlo, dhi = (np.ascontiguousarray(x, dtype=np.uint32) for x in (dlo, dhi))
+        n = frm.size
+        assert to.size == n and dlo.size == n and dhi.size == n
+        pad = lambda x, t: np.concatenate([x, np.zeros(1, t)])          # (an empty array still has an address)
+        u32 = lambda *shape: np.full((n + 1,) + shape, abi.WALKS_UNTOUCHED32, np.uint32)
+        status, steps, nw, ln, low = u32(), u32(), u32(), u32(abi.KSET_MAX_WALKS), u32(abi.KSET_MAX_WALKS)
+        walk = np.full((n + 1, abi.KSET_MAX_WALKS, abi.KSET_MAX_WALK), abi.WALKS_UNTOUCHED8, np.uint8)
+        rc = int(self.lib.hypo_gpu_kset_query_walk_sets(
+            _p(pad(a, np.uint8)), C.c_uint64(a.size), _p(pad(frm, np.uint64)), _p(pad(to, np.uint64)), _p(pad(dlo, np.uint32)), _p(pad(dhi, np.uint32)), C.c_uint32(n),
+            C.c_uint32(budget), _p(status), _p(steps), _p(nw), _p(ln), _p(low), _p(walk)))
+        return rc, status[:n], steps[:n], nw[:n], ln[:n], low[:n], walk[:n]
+
+    def kset_query_walk_sets(self, data, frm, to, dlo, dhi, budget):
+        """site s: up to abi.KSET_MAX_WALKS walks through the set from the k-mer data[frm[s]:frm[s] + k] that arrive at data[to[s]:to[s] + k]
+        after dlo[s] .. dhi[s] steps, by the depth-first search of include/hypo_gpu.h with at most `budget` visits, on a set that counts.
+        (status, steps, n_walks, len, low, walk): one of abi.WALK_*, the visits made, the walks reported and, for walk w < n_walks[s], its
+        length, the least read count along it and its bases (walk[s, w, :len[s, w]])."""
+        out = self.kset_query_walk_sets_rc(data, frm, to, dlo, dhi, budget)
         self._check(out[0])
         return out[1:]
 

@@ -1657,6 +1657,68 @@ int hypo_gpu_kset_query_walks(const char* bytes, uint64_t n_bytes, const uint64_
     return HYPO_OK;
 }
 
+int hypo_gpu_kset_query_walk_sets(const char* bytes, uint64_t n_bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi,
+                                  uint32_t n_sites, uint32_t budget, uint32_t* status, uint32_t* steps, uint32_t* n_walks, uint32_t* len, uint32_t* low,
+                                  uint8_t* walk) {
+    HYPO_KSET_ENTRY();
+    if (!n_sites) return HYPO_OK;
+    if (!bytes || !from || !to || !dlo || !dhi || !status || !steps || !n_walks || !len || !low || !walk) return fail(HYPO_E_INVALID, "NULL buffer");
+    static_assert(hypo::KSET_WALK_SETS == HYPO_KSET_MAX_WALKS, "the header's limits");
+    if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)");
+    // everything is checked before a buffer is touched: the kernel trusts what it is given
+    const uint32_t k = ks.k;
+    constexpr size_t W = hypo::KSET_WALK_SETS, MW = hypo::KSET_MAX_WALK;
+    if (budget < 1 || budget > hypo::KSET_MAX_WALK_BUDGET) return fail(HYPO_E_INVALID, "budget = %u out of range 1..%u (HYPO_KSET_MAX_WALK_BUDGET)", budget, hypo::KSET_MAX_WALK_BUDGET);
+    for (uint32_t s = 0; s < n_sites; ++s) {
+        if (n_bytes < k || from[s] > n_bytes - k || to[s] > n_bytes - k)
+            return fail(HYPO_E_INVALID, "site %u: the anchors at %llu and %llu (k = %u) do not lie inside %llu bytes", s, (unsigned long long)from[s], (unsigned long long)to[s], k,
+                        (unsigned long long)n_bytes);
+        if (dlo[s] < 1 || dlo[s] > dhi[s] || dhi[s] > hypo::KSET_MAX_WALK)
+            return fail(HYPO_E_INVALID, "site %u: 1 <= dlo <= dhi <= %u (HYPO_KSET_MAX_WALK) does not hold for %u .. %u", s, hypo::KSET_MAX_WALK, dlo[s], dhi[s]);
+    }
+    hipStream_t st = g_ctx.stream;
+    // ks.in: bytes.  ks.off: from | to | dlo | dhi.  ks.res: status | steps | n_walks | len | low | walk.  Every section starts at a multiple of 256 bytes.
+    Carver co, cr;
+    const size_t o_from = co.take((size_t)n_sites * 8), o_to = co.take((size_t)n_sites * 8), o_dlo = co.take((size_t)n_sites * 4), o_dhi = co.take((size_t)n_sites * 4);
+    const size_t r_st = cr.take((size_t)n_sites * 4), r_steps = cr.take((size_t)n_sites * 4), r_nw = cr.take((size_t)n_sites * 4), r_len = cr.take((size_t)n_sites * W * 4),
+                 r_low = cr.take((size_t)n_sites * W * 4), r_walk = cr.take((size_t)n_sites * W * MW);
+    HIP_TRY(ks.in.alloc(n_bytes));
+    HIP_TRY(ks.off.alloc(co.at));
+    HIP_TRY(ks.res.alloc(cr.at));
+    char* d_off = (char*)ks.off.p; char* d_res = (char*)ks.res.p;
+    HIP_TRY(h2d(ks.in.p, bytes, n_bytes, st));
+    HIP_TRY(h2d(d_off + o_from, from, (size_t)n_sites * 8, st));
+    HIP_TRY(h2d(d_off + o_to, to, (size_t)n_sites * 8, st));
+    HIP_TRY(h2d(d_off + o_dlo, dlo, (size_t)n_sites * 4, st));
+    HIP_TRY(h2d(d_off + o_dhi, dhi, (size_t)n_sites * 4, st));
+    HIP_TRY(hypo::kset_walk_sets_run((const uint8_t*)ks.in.p, (const uint64_t*)(d_off + o_from), (const uint64_t*)(d_off + o_to), (const uint32_t*)(d_off + o_dlo),
+                                     (const uint32_t*)(d_off + o_dhi), n_sites, budget, k, ks.table, ks.slots, ks.planes, ks.min_count, (uint32_t*)(d_res + r_st),
+                                     (uint32_t*)(d_res + r_steps), (uint32_t*)(d_res + r_nw), (uint32_t*)(d_res + r_len), (uint32_t*)(d_res + r_low),
+                                     (uint8_t*)(d_res + r_walk), st));
+    // through host buffers of the call's own: only the slots below n_walks and of a walk only its len bytes reach the caller, what lies
+    // beyond them stays as it was (the arena is not cleared: a slot the search did not fill holds an earlier call's bytes)
+    std::vector<uint32_t> h_st(n_sites), h_steps(n_sites), h_nw(n_sites), h_len(n_sites * W), h_low(n_sites * W);
+    std::vector<uint8_t> h_walk((size_t)n_sites * W * MW);
+    HIP_TRY(d2h(h_st.data(), d_res + r_st, (size_t)n_sites * 4, st));
+    HIP_TRY(d2h(h_steps.data(), d_res + r_steps, (size_t)n_sites * 4, st));
+    HIP_TRY(d2h(h_nw.data(), d_res + r_nw, (size_t)n_sites * 4, st));
+    HIP_TRY(d2h(h_len.data(), d_res + r_len, h_len.size() * 4, st));
+    HIP_TRY(d2h(h_low.data(), d_res + r_low, h_low.size() * 4, st));
+    HIP_TRY(d2h(h_walk.data(), d_res + r_walk, h_walk.size(), st));
+    HIP_TRY(hipStreamSynchronize(st));
+    for (uint32_t s = 0; s < n_sites; ++s) {
+        status[s] = h_st[s]; steps[s] = h_steps[s]; n_walks[s] = h_nw[s];
+        const size_t nw = h_nw[s] <= W ? h_nw[s] : 0;
+        for (size_t w = 0; w < nw; ++w) {
+            const size_t at = (size_t)s * W + w;
+            len[at] = h_len[at]; low[at] = h_low[at];
+            const size_t n = h_len[at] <= MW ? h_len[at] : 0;
+            for (size_t i = 0; i < n; ++i) walk[at * MW + i] = h_walk[at * MW + i];
+        }
+    }
+    return HYPO_OK;
+}
+
 // ---- read counts, copy numbers and the spectrum (hypo --qv-spectra) ---------------------------------------------------------------
 int hypo_gpu_kset_counts_enable(uint32_t n_texts) {
     HYPO_KSET_ENTRY();

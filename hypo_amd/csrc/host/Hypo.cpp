@@ -29,7 +29,7 @@ struct Extras {
     SpectraReport spectra{set};
     KmerFix fix{set};
     KmerBridge bridge{set};
-    bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false, fix_on = false, bridge_on = false;
+    bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false, fix_on = false, bridge_on = false, vote_on = false;
     uint32_t min_given = 1;                                // --qv-min-count: 1 = off, 0 = the valley
     bool min_on() const { return min_given != 1; }
     bool ask_on = false;                                   // --qv or --qv-bed: every contig's texts are put to the set
@@ -190,6 +190,13 @@ void Hypo::bind_extras(Extras& ex) {
     // run without the flag.  The flags are checked in this order, and each one's error names what it needs.
     const bool have_set = (ex.set_on || ex.min_on()) && ex.set.bind();
     const std::string the_set = ReadKmerSet::kNames;
+    // --kmer-bridge-vote: the walk-sets query, and counts on the set it asks
+    ex.vote_on = ex.bridge_on && _cFlags.kmer_bridge_vote != 0;
+    if (ex.vote_on) {
+        (void)ex.set.bind_counts();
+        require("--kmer-bridge-vote", {{" hypo_gpu_kset_query_walk_sets", ex.bridge.bind_vote()}, {" hypo_gpu_kset_counts_enable", ex.set.have_counts()}, {" " + the_set, have_set}}, true);
+        ex.bridge.configure_vote(_cFlags.kmer_bridge_vote);
+    }
     // --kmer-bridge: the walks query and the track query, and the set they ask
     if (ex.bridge_on) {
         require("--kmer-bridge", {{" hypo_gpu_kset_query_walks", ex.bridge.bind()}, {" hypo_gpu_kset_query_track", ex.set.bind_track()}, {" " + the_set, have_set}}, true);
@@ -228,9 +235,9 @@ void Hypo::bind_extras(Extras& ex) {
         const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
         if (ex.set.begin(_cFlags.qv_k, _cFlags.genome_size, cap) != HYPO_OK) ex.set_fail("the k-mer set could not be created");
         ex.set_sink = ex.set.sink();
-        // --qv-spectra, --qv-min-count: the set counts from its first k-mer on, with a plane of copy bytes for each text that is
-        // going to be marked (one at the least), and the reads reach it window by window, each once
-        if (ex.spectra_on || ex.min_on()) {
+        // --qv-spectra, --qv-min-count, --kmer-bridge-vote: the set counts from its first k-mer on, with a plane of copy bytes for each
+        // text that is going to be marked (one at the least), and the reads reach it window by window, each once
+        if (ex.spectra_on || ex.min_on() || ex.vote_on) {
             if (ex.set.enable_counts(ex.spectra_on ? SpectraReport::N_TEXTS : 1) != HYPO_OK) ex.set_fail("the k-mer set could not be made to count");
             ex.set_sink.exact = true;
         }
@@ -852,6 +859,12 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
                                  "%llu over budget, %llu missing k-mers removed\n", _cFlags.kmer_bridge_filename.c_str(), ex.bridge.k(), ex.bridge.max_dist(), ex.bridge.slack(),
                          (unsigned long long)bs.intervals, (unsigned long long)bs.sites, (unsigned long long)bs.bridged, (unsigned long long)bs.bases_out,
                          (unsigned long long)bs.bases_in, (unsigned long long)bs.ambiguous, (unsigned long long)bs.over_budget, (unsigned long long)bs.removed);
+            if (ex.vote_on) {
+                const KmerBridge::VoteStats& vs = ex.bridge.vote_stats();
+                std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer bridge vote (ratio %u, up to %u walks): %llu asked, %llu chosen, %llu too close, %llu more than %u walks, %llu over budget\n",
+                             ex.bridge.vote_ratio(), (unsigned)HYPO_KSET_MAX_WALKS, (unsigned long long)vs.asked, (unsigned long long)vs.chosen, (unsigned long long)vs.close,
+                             (unsigned long long)vs.many, (unsigned)HYPO_KSET_MAX_WALKS, (unsigned long long)vs.over_budget);
+            }
         }
         if (w == RunOutputs::BED) {
             const QvReport::TrackSums ts = ex.qv.track_sums();

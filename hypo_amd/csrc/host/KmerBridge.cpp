@@ -3,6 +3,7 @@
 #include <dlfcn.h>
 #include <algorithm>
 #include <cctype>
+#include <cstdio>
 
 namespace hypo {
 
@@ -19,6 +20,11 @@ static_assert(KmerBridge::kMaxHi + KmerBridge::kSlackHi <= HYPO_KSET_MAX_WALK &&
 bool KmerBridge::bind() {
     _walks = (decltype(_walks))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_query_walks");
     return _walks != nullptr;
+}
+
+bool KmerBridge::bind_vote() {
+    _walk_sets = (decltype(_walk_sets))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_query_walk_sets");
+    return _walk_sets != nullptr;
 }
 
 int KmerBridge::push(uint32_t contig, const std::string& name, std::string draft, std::string text, const Emit& emit) {
@@ -82,6 +88,53 @@ int KmerBridge::flush(const Emit& emit) {
                     wlen.data() + at, walk.data() + at * HYPO_KSET_MAX_WALK);
         if (rc != HYPO_OK) return rc;
     }
+    // --kmer-bridge-vote: the ambiguous sites once more, for up to 4 walks with their supports; a chosen site takes its place among
+    // the unique ones, with the second search's steps and the chosen walk's bases
+    std::vector<uint32_t> n_found, c_best, c_next;             // per site, under the vote: the walks found (1: unique), the two supports
+    if (_ratio) {
+        n_found.assign(ns, 1); c_best.assign(ns, 0); c_next.assign(ns, 0);
+        std::vector<size_t> asked;
+        for (size_t i = 0; i < ns; ++i) if (status[i] == HYPO_WALK_AMBIGUOUS) asked.push_back(i);
+        _vstats.asked += asked.size();
+        constexpr size_t W = HYPO_KSET_MAX_WALKS, kVotesPerCall = (size_t)1 << 16;
+        std::vector<uint32_t> vst, vsteps, vn, vlen, vlow;
+        std::vector<uint8_t> vwalk;
+        for (size_t at = 0; at < asked.size(); at += kVotesPerCall) {
+            const size_t m = std::min(kVotesPerCall, asked.size() - at);
+            std::vector<uint64_t> from(m), to(m);
+            std::vector<uint32_t> dlo(m), dhi(m);
+            for (size_t j = 0; j < m; ++j) {
+                const Site& st = sites[asked[at + j]];
+                from[j] = st.a; to[j] = st.b;
+                dlo[j] = st.d0 > _slack + 1 ? st.d0 - _slack : 1; dhi[j] = st.d0 + _slack;
+            }
+            vst.assign(m, 0); vsteps.assign(m, 0); vn.assign(m, 0); vlen.assign(m * W, 0); vlow.assign(m * W, 0); vwalk.assign(m * W * HYPO_KSET_MAX_WALK, 0);
+            rc = _walk_sets(_text.data(), _text.size(), from.data(), to.data(), dlo.data(), dhi.data(), (uint32_t)m, kBudget, vst.data(), vsteps.data(), vn.data(),
+                            vlen.data(), vlow.data(), vwalk.data());
+            if (rc != HYPO_OK) return rc;
+            for (size_t j = 0; j < m; ++j) {
+                if (vst[j] == HYPO_WALK_MANY) { ++_vstats.many; continue; }
+                if (vst[j] == HYPO_WALK_BUDGET) { ++_vstats.over_budget; continue; }
+                // the best and the second best support (the first among equals: two equal supports are never far enough apart)
+                size_t best = 0, next = W;
+                const uint32_t nw = std::min<uint32_t>(vn[j], (uint32_t)W);
+                for (size_t w = 1; w < nw; ++w) if (vlow[j * W + w] > vlow[j * W + best]) best = w;
+                for (size_t w = 0; w < nw; ++w) if (w != best && (next == W || vlow[j * W + w] > vlow[j * W + next])) next = w;
+                // the first search saw two walks arrive: a second one that sees fewer disagrees with it, and nothing it says is used
+                if (vst[j] != HYPO_WALK_AMBIGUOUS || next == W) {
+                    std::fprintf(stderr, "[Hypo::Hypo] Error: k-mer bridge vote: hypo_gpu_kset_query_walk_sets answers status %u with %u walks for a site that hypo_gpu_kset_query_walks "
+                                         "found ambiguous (anchors at %llu and %llu)\n", vst[j], vn[j], (unsigned long long)from[j], (unsigned long long)to[j]);
+                    return HYPO_E_INVALID;
+                }
+                if ((uint64_t)vlow[j * W + best] < (uint64_t)_ratio * vlow[j * W + next]) { ++_vstats.close; continue; }
+                const size_t i = asked[at + j];
+                ++_vstats.chosen;
+                status[i] = HYPO_WALK_UNIQUE; steps[i] = vsteps[j]; wlen[i] = vlen[j * W + best];
+                std::copy_n(vwalk.begin() + (ptrdiff_t)((j * W + best) * HYPO_KSET_MAX_WALK), wlen[i], walk.begin() + (ptrdiff_t)(i * HYPO_KSET_MAX_WALK));
+                n_found[i] = nw; c_best[i] = vlow[j * W + best]; c_next[i] = vlow[j * W + next];
+            }
+        }
+    }
     // the bridges go in contig by contig, in ascending order
     size_t s = 0;
     std::string out, fresh;
@@ -112,7 +165,12 @@ int KmerBridge::flush(const Emit& emit) {
             if (ref_len) _lines.append(_text, pos, ref_len); else _lines += '.';
             _lines += '\t';
             if (alt_len) _lines.append(fresh, pre, alt_len); else _lines += '.';
-            _lines += '\t'; _lines += std::to_string(st.n); _lines += '\t'; _lines += std::to_string(steps[s]); _lines += '\n';
+            _lines += '\t'; _lines += std::to_string(st.n); _lines += '\t'; _lines += std::to_string(steps[s]);
+            if (_ratio) {
+                _lines += '\t'; _lines += std::to_string(n_found[s]); _lines += '\t';
+                if (n_found[s] > 1) { _lines += std::to_string(c_best[s]); _lines += '/'; _lines += std::to_string(c_next[s]); } else _lines += '.';
+            }
+            _lines += '\n';
         }
         out.append(_text, from, p.off + p.len - from);
         rc = emit(p.contig, p.draft, out);
@@ -123,7 +181,7 @@ int KmerBridge::flush(const Emit& emit) {
 }
 
 void KmerBridge::write(std::ostream& os) const {
-    os << "#contig\tpos\tref\talt\tmissing_kmers\tsteps\n" << _lines;
+    os << "#contig\tpos\tref\talt\tmissing_kmers\tsteps" << (_ratio ? "\twalks\tsupport\n" : "\n") << _lines;
 }
 
 }  // namespace hypo

@@ -39,6 +39,7 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     std::string kmer_bridge_filename;      // new, opt-in: --kmer-bridge <file> (one pass of local reassembly between k-mers of the reads, listed in the file)
     uint32_t kmer_bridge_max = 64;         // new, opt-in: --kmer-bridge-max (2..192: the largest anchor distance tried)
     uint32_t kmer_bridge_slack = 8;        // new, opt-in: --kmer-bridge-slack (0..64: the most bases a bridge may add or remove)
+    uint32_t kmer_bridge_vote = 0;         // new, opt-in: --kmer-bridge-vote (2..255, 0 = off: an ambiguous bridge goes to the walk the reads support this many times better)
     uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
 };
 

@@ -35,7 +35,8 @@ const struct option long_options[] = {
     {"qv-bed", required_argument, nullptr, 1014}, {"qv-spectra", required_argument, nullptr, 1015},
     {"qv-reliable-min", required_argument, nullptr, 1016}, {"qv-min-count", required_argument, nullptr, 1017},
     {"kmer-fix", required_argument, nullptr, 1018}, {"kmer-bridge", required_argument, nullptr, 1019},
-    {"kmer-bridge-max", required_argument, nullptr, 1020}, {"kmer-bridge-slack", required_argument, nullptr, 1021}, {nullptr, 0, nullptr, 0}};
+    {"kmer-bridge-max", required_argument, nullptr, 1020}, {"kmer-bridge-slack", required_argument, nullptr, 1021},
+    {"kmer-bridge-vote", required_argument, nullptr, 1022}, {nullptr, 0, nullptr, 0}};
 
 // Same layout as the reference's usage() (src/main.cpp:363-430): "Usage: hypo <args>", the mandatory block, the optional
 // block, every flag as "-x, --long <type>" followed by what it does and its default.  The wording is this build's own.
@@ -84,6 +85,7 @@ void usage() {
         {"    --kmer-bridge <str>", "[MI355X build] Make one pass of local reassembly over the text that would otherwise be written (after --kmer-guard and --kmer-fix), where the k-mers of the short reads spell exactly one other text: a stretch under k-mers no read contains, at least 2 bases from the next such stretch and not at a contig end, lies between two k-mers the reads do contain, one base in front of it and one behind it. When those two anchors are at most --kmer-bridge-max bases apart, the k-mers of the reads are walked as a de Bruijn graph from the left anchor to the right one, letting the stretch grow or shrink by up to --kmer-bridge-slack bases, and when exactly one walk arrives its text replaces the stretch; several walks (a heterozygous site, a repeat) or a search that gives up leave it alone. This reaches what --kmer-fix leaves behind: length errors of two or more bases in homopolymers and short tandem repeats, substitutions closer than k, an indel next to a substitution. The file lists the bridges, tab-separated: contig, pos (0-based, in the text before this pass), ref, alt (`.` when empty), the missing k-mers the bridge removes, and the steps of the search. --qv, --qv-bed and --qv-spectra then describe the bridged text; --vcf still describes the text before the fixes and bridges. Uses the k-mer set of --qv (--qv-k, --qv-mem, --qv-min-count) with or without the other flags; the graph is walked on the device.", "no bridges"},
         {"    --kmer-bridge-max <int>", "[MI355X build] Largest distance of the two anchors --kmer-bridge still tries, 2 to 192 bases. Needs --kmer-bridge.", "64"},
         {"    --kmer-bridge-slack <int>", "[MI355X build] Most bases a bridge of --kmer-bridge may add to or remove from the stretch it replaces, 0 to 64. Needs --kmer-bridge.", "8"},
+        {"    --kmer-bridge-vote <int>", "[MI355X build] Settle the stretches --kmer-bridge leaves as ambiguous by read count: such a stretch is searched again for up to 4 walks, each with its support, the smallest number of times the short reads contain a k-mer of the walk, and when the best walk's support is at least this many times the second best's, 2 to 255, its text replaces the stretch (a read error seen once against an allele seen 30 times). Walks of similar support (a heterozygous site, a repeat), more than 4 walks or a search that gives up leave it alone. The file of --kmer-bridge gains two columns: the walks found (1 for a bridge that needed no vote) and the two supports as best/second (`.` without a vote). The k-mer set then counts as for --qv-min-count (one more byte a slot under --qv-mem), with or without --qv-min-count. Needs --kmer-bridge.", "no vote"},
         {"-h, --help", "Print the usage.", nullptr}};
     std::printf("\n Usage: hypo <args>\n\n ** Mandatory args:\n");
     for (const auto& e : mandatory) std::printf("\t%s\n\t%s\n\n", e.flag, e.what);
@@ -231,6 +233,7 @@ int main(int argc, char** argv) {
             case 1019: flags.kmer_bridge_filename = optarg; break;
             case 1020: flags.kmer_bridge_max = int_in("--kmer-bridge-max", optarg, 2, 192); bridge_opts = true; break;
             case 1021: flags.kmer_bridge_slack = int_in("--kmer-bridge-slack", optarg, 0, 64); bridge_opts = true; break;
+            case 1022: flags.kmer_bridge_vote = int_in("--kmer-bridge-vote", optarg, 2, 255); break;
             case 1002: {
                 flags.devices.clear();
                 for (const char* c = optarg; *c;) { flags.devices.push_back(std::atoi(c)); while (*c && *c != ',') ++c; if (*c == ',') ++c; }
@@ -246,6 +249,10 @@ int main(int argc, char** argv) {
     }
     if (bridge_opts && flags.kmer_bridge_filename.empty()) {
         std::fprintf(stderr, "[Hypo::] Error: Arg Error: --kmer-bridge-max and --kmer-bridge-slack set how --kmer-bridge searches: they need --kmer-bridge!\n");
+        std::exit(1);
+    }
+    if (flags.kmer_bridge_vote && flags.kmer_bridge_filename.empty()) {
+        std::fprintf(stderr, "[Hypo::] Error: Arg Error: --kmer-bridge-vote (2 to 255) settles what --kmer-bridge leaves ambiguous: it needs --kmer-bridge!\n");
         std::exit(1);
     }
     if (!(is_sr && is_draft && is_size && is_bamsr && is_cov)) {

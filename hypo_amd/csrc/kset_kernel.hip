@@ -21,6 +21,8 @@
 //     short regions, a group per candidate, ks_group_scan once more, and a lane per site that picks the best candidate.
 //   * kset_walks_kernel (below, with comments of its own; hypo --kmer-bridge): the set as a de Bruijn graph, a depth-first search
 //     between two anchors per site, 4 lanes a site, dependent probes, the stack in LDS.
+//   * kset_walk_sets_kernel (below, with comments of its own; hypo --kmer-bridge-vote): that search carried on to up to four walks,
+//     each with the least count byte along it.
 //   * counts (hypo --qv-spectra; further down, with comments of their own): a count byte and up to four copy bytes per slot in planes
 //     beside the table, a saturating byte add that serves both, and the counted variants of the insert and rehash kernels, the mark
 //     kernel (the query body with a probe that returns the slot) and the spectrum kernel.
@@ -1013,6 +1015,116 @@ hipError_t kset_walks_run(const uint8_t* bytes, const uint64_t* from, const uint
         kset_walks_min_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, status, steps, len, walk,
                                                                          (const uint8_t*)planes, min_count);
     else kset_walks_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, status, steps, len, walk);
+    return hipGetLastError();
+}
+
+// ---- up to four walks between two anchors, each with its support (hypo --kmer-bridge-vote; DESIGN.md "k-mer bridge vote") -------------
+// The search of kset_walks_kernel, not stopped at the second arrival: it goes on until the tree is exhausted, a fifth walk arrives
+// (MANY) or the budget is spent, and every walk that arrives is written into the site's next slot with its length and its `low`,
+// the least count byte among the k-mers at its depths 1 .. len (R included, L not).  A child exists iff its count byte is at least
+// t (t = 1: iff the set holds it; an absent key counts 0), so one kernel serves every t.  The geometry, the ballot, the stack byte
+// per depth and the rebuilt parent are the sibling's.
+// The running minimum: the count of the child a group steps onto was loaded by another lane in an earlier iteration, so the group
+// asks again.  In the iteration that expands the k-mer x at depth d >= 1 all four lanes also probe x itself (one address for the
+// group, issued with the child probes) and store lowmin[d] = min(lowmin[d - 1], count(x)) in a second LDS byte per depth;
+// lowmin[0] = 255 (L is not counted).  count(R) is loaded once per site, and an arrival from depth d has low = min(lowmin[d],
+// count(R)).  As with the stack, every lane of a group stores and loads the same bytes.  2 * 260 bytes a site, 33 280 a workgroup.
+// Bounds: a site makes at most `budget` <= KSET_MAX_WALK_BUDGET visits and no more steps back than visits, so the loop ends after
+// at most 2 budget + 2 iterations; a probe takes at most `slots` steps, an expansion makes two of them and a site one more for R;
+// depth <= dhi <= KSET_MAX_WALK = 256, stack and lowmin are indexed at depth < dhi (a k-mer at depth dhi is never expanded; d - 1
+// only with d >= 1), below KS_WALK_STACK; a walk is written only while found < KSET_WALK_SETS, at slot = s * 4 + found < n_sites * 4:
+// len / low at [slot], walk[] at [slot * 256, slot * 256 + len), len <= dhi; counts[] at a slot ks_find returned, < slots; bytes
+// are read at [from, from + k) and [to, to + k), which the caller checked to lie inside the text; status / steps / n_walks are
+// indexed below n_sites.
+enum { KS_WALK_MANY = 5 };
+
+// the count byte of the key, 0 when the set does not hold it
+__device__ __forceinline__ uint32_t ks_count_of(const uint64_t* __restrict__ table, uint64_t slots, const uint8_t* __restrict__ counts, uint64_t key) {
+    const uint64_t s = ks_find(table, slots, key);
+    return s == KSET_EMPTY ? 0u : (uint32_t)counts[s];
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_walk_sets_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ from,
+                                                                     const uint64_t* __restrict__ to, const uint32_t* __restrict__ dlo,
+                                                                     const uint32_t* __restrict__ dhi, uint32_t n_sites, uint32_t budget, uint32_t k,
+                                                                     const uint64_t* __restrict__ table, uint64_t slots, const uint8_t* __restrict__ counts,
+                                                                     uint32_t t, uint32_t* __restrict__ status, uint32_t* __restrict__ steps_out,
+                                                                     uint32_t* __restrict__ n_walks, uint32_t* __restrict__ len_out,
+                                                                     uint32_t* __restrict__ low_out, uint8_t* __restrict__ walk) {
+    __shared__ uint8_t stacks[KS_WALK_SITES * KS_WALK_STACK];
+    __shared__ uint8_t lowmins[KS_WALK_SITES * KS_WALK_STACK];
+    const uint32_t lane = threadIdx.x & 63, b = lane & (KS_WALK_LANES - 1), gshift = lane & ~(uint32_t)(KS_WALK_LANES - 1);
+    const uint64_t site = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / KS_WALK_LANES;
+    uint8_t* const stack = stacks + (threadIdx.x / KS_WALK_LANES) * KS_WALK_STACK;
+    uint8_t* const lowmin = lowmins + (threadIdx.x / KS_WALK_LANES) * KS_WALK_STACK;
+    const bool have = site < n_sites;
+    const uint64_t mask = (1ull << (2 * k)) - 1;
+    const uint32_t rsh = 2 * (k - 1);
+    uint64_t lf = 0, lr = 0, rf = 0, rr = 0, fwd = 0, rc = 0;
+    uint32_t lo = 0, hi = 0, st = KS_WALK_NONE, steps = 0, found = 0, d = 0, cr = 0;
+    bool done = true, expand = false;
+    if (have) {
+        lo = dlo[site]; hi = dhi[site];
+        const bool ok_l = ks_anchor(bytes, from[site], k, lf, lr), ok_r = ks_anchor(bytes, to[site], k, rf, rr);
+        if (ok_l && ok_r) {                                      // the visit of L: depth 0 < dlo, no arrival
+            done = false; expand = true; steps = 1; fwd = lf; rc = lr;
+            cr = ks_count_of(table, slots, counts, rf < rr ? rf : rr);
+        } else st = KS_WALK_NOANCHOR;
+    }
+    while (__any(!done)) {
+        // the groups that stepped onto a k-mer: the counts of its children, and its own
+        uint32_t cy = 0, cx = 255;
+        if (!done && expand) {
+            const uint64_t yf = ((fwd << 2) | b) & mask, yr = (rc >> 2) | ((uint64_t)(3u - b) << rsh);
+            cy = ks_count_of(table, slots, counts, yf < yr ? yf : yr);
+            if (d) cx = ks_count_of(table, slots, counts, fwd < rc ? fwd : rc);
+        }
+        const uint32_t kids = (uint32_t)(__ballot(cy >= t) >> gshift) & 15u;
+        if (done) continue;
+        if (expand) {
+            const uint32_t up = d ? (uint32_t)lowmin[d - 1] : 255u;
+            stack[d] = (uint8_t)kids; lowmin[d] = (uint8_t)(cx < up ? cx : up); expand = false;
+        }
+        const uint32_t m = stack[d] & 15u;
+        if (!m) {                                               // every child tried: one step back, or the search is over
+            if (!d) { done = true; continue; }
+            const uint32_t i = d - 1;                           // the base that fell off when the group stepped here: base i of L + path
+            const uint32_t c = i < k ? (uint32_t)(lf >> (2 * (k - 1 - i))) & 3u : ((uint32_t)stack[i - k] >> 4) & 3u;
+            fwd = (fwd >> 2) | ((uint64_t)c << rsh);
+            rc = ((rc << 2) | (3u - c)) & mask;
+            d = i;
+            continue;
+        }
+        const uint32_t c = (uint32_t)__ffs(m) - 1;
+        stack[d] = (uint8_t)((m & (m - 1)) | (c << 4));
+        const uint64_t yf = ((fwd << 2) | c) & mask;
+        if (++steps > budget) { st = KS_WALK_BUDGET; done = true; continue; }
+        if (d + 1 >= lo && yf == rf) {                           // an arrival ends the walk
+            if (found == KSET_WALK_SETS) { st = KS_WALK_MANY; done = true; continue; }
+            const uint64_t slot = site * KSET_WALK_SETS + found;
+            const uint32_t len = d + 1, up = lowmin[d];
+            if (b == 0) { len_out[slot] = len; low_out[slot] = cr < up ? cr : up; }
+            for (uint32_t x = b; x < len; x += KS_WALK_LANES) walk[slot * KSET_MAX_WALK + x] = (uint8_t)ks_base_char(((uint32_t)stack[x] >> 4) & 3u);
+            ++found;
+            continue;
+        }
+        if (d + 1 == hi) continue;
+        fwd = yf; rc = (rc >> 2) | ((uint64_t)(3u - c) << rsh);
+        ++d; expand = true;
+    }
+    if (have && b == 0) {
+        if (st == KS_WALK_NONE && found) st = found == 1 ? KS_WALK_UNIQUE : KS_WALK_AMBIGUOUS;
+        status[site] = st; steps_out[site] = steps; n_walks[site] = st == KS_WALK_BUDGET || st == KS_WALK_NOANCHOR ? 0u : found;
+    }
+}
+
+hipError_t kset_walk_sets_run(const uint8_t* bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites,
+                              uint32_t budget, uint32_t k, const uint64_t* table, uint64_t slots, const uint32_t* planes, uint32_t min_count, uint32_t* status,
+                              uint32_t* steps, uint32_t* n_walks, uint32_t* len, uint32_t* low, uint8_t* walk, hipStream_t st) {
+    if (!n_sites) return hipSuccess;
+    const uint32_t blocks = (n_sites + KS_WALK_SITES - 1) / KS_WALK_SITES;
+    kset_walk_sets_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, (const uint8_t*)planes,
+                                                                     min_count < 1 ? 1u : min_count, status, steps, n_walks, len, low, walk);
     return hipGetLastError();
 }
 

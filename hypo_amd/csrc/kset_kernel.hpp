@@ -109,5 +109,15 @@ constexpr uint32_t KSET_MAX_WALK_BUDGET = 65536;
 hipError_t kset_walks_run(const uint8_t* bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites,
                           uint32_t budget, uint32_t k, const uint64_t* table, uint64_t slots, uint32_t* status, uint32_t* steps, uint32_t* len, uint8_t* walk,
                           const uint32_t* planes, uint32_t min_count, hipStream_t st);
+// The same search carried on to the first KSET_WALK_SETS walks, each with its support (hypo --kmer-bridge-vote; DESIGN.md "k-mer bridge
+// vote"), on a set that counts: `planes` must not be NULL, a child exists iff its count byte is at least max(min_count, 1).  status
+// / steps / n_walks: n_sites values each; len / low: n_sites * KSET_WALK_SETS, walk: n_sites * KSET_WALK_SETS * KSET_MAX_WALK bytes;
+// walk w of site s sits at index s * KSET_WALK_SETS + w, in the order of arrival, low = the least count byte along it.  Slots at
+// or beyond n_walks[s] are work space (under BUDGET they hold the walks found before it), as are the bytes beyond a walk's len: the
+// caller passes on what lies below them only.  The caller has checked the ranges kset_walks_run asks for.
+constexpr uint32_t KSET_WALK_SETS = 4;
+hipError_t kset_walk_sets_run(const uint8_t* bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites,
+                              uint32_t budget, uint32_t k, const uint64_t* table, uint64_t slots, const uint32_t* planes, uint32_t min_count, uint32_t* status,
+                              uint32_t* steps, uint32_t* n_walks, uint32_t* len, uint32_t* low, uint8_t* walk, hipStream_t st);
 
 }  // namespace hypo

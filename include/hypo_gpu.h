@@ -533,6 +533,36 @@ int hypo_gpu_kset_query_fixes(const char* bytes, uint64_t n_bytes, const uint64_
 int hypo_gpu_kset_query_walks(const char* bytes, uint64_t n_bytes, const uint64_t* from, const uint64_t* to,
                               const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites, uint32_t budget,
                               uint32_t* status, uint32_t* steps, uint32_t* len, uint8_t* walk);
+/* Up to W = HYPO_KSET_MAX_WALKS walks between two anchors, each with its support (hypo --kmer-bridge-vote; DESIGN.md "k-mer bridge
+ * vote").  Additive to ABI 11: callers bind it by name.  The set must count (hypo_gpu_kset_counts_enable).  The anchors, the byte
+ * rules, the children in ACGT order and the limits on dlo, dhi and budget are those of hypo_gpu_kset_query_walks.  count(y) is the
+ * count byte of y's canonical k-mer, 0 when the set does not hold it; t is the least count in force (hypo_gpu_kset_min_count), 1
+ * otherwise.  The answer is the result of this search and nothing else:
+ *     steps = 0; walks = []
+ *     visit(x, depth, path, lo):
+ *         steps += 1;  if steps > budget: stop with BUDGET
+ *         if depth >= dlo and x == R:                 (forward strings compared)
+ *             if len(walks) == W: stop with MANY
+ *             walks.append((path, lo));  return       (a walk ends at its first allowed arrival)
+ *         if depth == dhi: return
+ *         for b in A, C, G, T:  y = x[1:] + b;  c = count(y);  if c >= t: visit(y, depth + 1, path + b, min(lo, c))
+ *     visit(L, 0, "", 255)
+ *     status = NONE / UNIQUE / AMBIGUOUS for 0 / 1 / 2..W walks
+ * The low of a walk is thus the smallest count among the k-mers at its depths 1 .. len: R is included, L is not, and counts stop at
+ * 255.  n_walks[s]: the walks reported, in the order of arrival; walk w of site s has len[s * W + w], low[s * W + w] and its bases as
+ * ACGT bytes at walk[(s * W + w) * HYPO_KSET_MAX_WALK, + len).  MANY (a walk beyond the Wth arrived) reports the first W; BUDGET and
+ * NOANCHOR report n_walks = 0.  status[s] and steps[s] are as for hypo_gpu_kset_query_walks: budget + 1 steps for BUDGET, 0 for
+ * NOANCHOR.  Bytes beyond a walk's len and the slots beyond n_walks are left as the caller had them.  Where neither search ends on
+ * BUDGET, the first walk here is hypo_gpu_kset_query_walks' and NONE / UNIQUE agree.  HYPO_E_INVALID: everything
+ * hypo_gpu_kset_query_walks refuses, and a set that keeps no counts; a refused call changes nothing.  n_sites == 0 touches nothing.
+ * Synchronous, on the calling thread's context. */
+#define HYPO_KSET_MAX_WALKS 4
+#define HYPO_WALK_MANY 5
+int hypo_gpu_kset_query_walk_sets(const char* bytes, uint64_t n_bytes, const uint64_t* from, const uint64_t* to,
+                                  const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites, uint32_t budget,
+                                  uint32_t* status, uint32_t* steps, uint32_t* n_walks,
+                                  uint32_t* len  /* [n_sites * 4] */, uint32_t* low /* [n_sites * 4] */,
+                                  uint8_t* walk  /* [n_sites * 4 * HYPO_KSET_MAX_WALK] */);
 
 /* Read k-mer counts and copy numbers on the set (hypo --qv-spectra; DESIGN.md "k-mer spectra").  Additive to ABI 11: callers bind
  * the three by name.  Presence, and with it every answer of the query entry points above, is what it is without them.
