@@ -42,6 +42,9 @@ KSET_MAX_TEXTS = 4
 KSET_SPECTRUM_ROWS, KSET_SPECTRUM_COLS = 256, 5
 KSET_SPECTRUM_BINS = KSET_SPECTRUM_ROWS * KSET_SPECTRUM_COLS
 
+# hypo_gpu_kset_export / _import (HYPO_KSET_EXPORT_END): the cursor a finished export sequence leaves
+KSET_EXPORT_END = 0xFFFFFFFFFFFFFFFF
+
 ST_OK = 0
 ST_CONS_OVERFLOW = 1
 ST_CAPACITY = 2

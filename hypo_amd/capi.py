@@ -33,6 +33,7 @@ EXPORTS = [
     "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants", "hypo_gpu_kset_query_track", "hypo_gpu_kset_query_fixes",
     "hypo_gpu_kset_query_walks", "hypo_gpu_kset_query_walk_sets",
     "hypo_gpu_kset_counts_enable", "hypo_gpu_kset_mark", "hypo_gpu_kset_spectrum", "hypo_gpu_kset_min_count",
+    "hypo_gpu_kset_export", "hypo_gpu_kset_import",
 ]
 KSET_SPAN_PIECE = 2048        # windows per piece of a long span (kset_kernel.hpp)
 KSET_MAX_EDITS = 12           # edits of a site of hypo_gpu_kset_query_variants (HYPO_KSET_MAX_EDITS)
@@ -507,6 +508,46 @@ class HypoGpu:
         """on a set that counts: from the next call on the four queries answer against the k-mers the reads have at least t times
         (1..255; 1 = the set itself)"""
         self._check(self.kset_min_count_rc(t))
+
+    def kset_export_rc(self, cursor: int, cap: int, keys, counts=None):
+        """(return code, cursor after the call, n_out, digest of the call) of ONE call of hypo_gpu_kset_export into the caller's arrays:
+        keys u64[>= cap], counts u8[>= cap] or None; nothing is checked here.  n_out is None when the call did not write it."""
+        untouched = 0xFFFFFFFFFFFFFFFF                                  # (no call hands back 2^64 - 1 records)
+        cur, n_out, dig = C.c_uint64(cursor), C.c_uint64(untouched), C.c_uint64(0)
+        rc = int(self.lib.hypo_gpu_kset_export(C.byref(cur), _p(keys), _p(counts) if counts is not None else None, C.c_uint64(cap), C.byref(n_out), C.byref(dig)))
+        return rc, int(cur.value), None if n_out.value == untouched else int(n_out.value), int(dig.value)
+
+    def kset_export(self, cap: int = 1 << 20, counts=True):
+        """one export sequence over the set with calls of `cap`: (keys u64[n], counts u8[n] or None, digest, the n_out of every call)"""
+        n = self.kset_size()[0]
+        keys = np.empty(n + cap, np.uint64)                              # (room for a whole call behind the last record)
+        cnts = np.empty(n + cap, np.uint8) if counts else None
+        cursor, at, digest, n_outs = 0, 0, 0, []
+        while cursor != abi.KSET_EXPORT_END:
+            rc, cursor, got, d = self.kset_export_rc(cursor, cap, keys[at:], cnts[at:] if counts else None)
+            self._check(rc)
+            at += got
+            digest = (digest + d) & 0xFFFFFFFFFFFFFFFF
+            n_outs.append(got)
+        return keys[:at], cnts[:at] if counts else None, digest, n_outs
+
+    def kset_import_rc(self, keys, counts=None):
+        """(return code, digest of the records as given) of one call of hypo_gpu_kset_import; nothing is checked here"""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        n = keys.size
+        pad = lambda x, t: np.concatenate([x, np.zeros(1, t)])          # (an empty array still has an address)
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, dtype=np.uint8)
+            assert counts.size == n
+        dig = C.c_uint64(0)
+        rc = int(self.lib.hypo_gpu_kset_import(_p(pad(keys, np.uint64)), _p(pad(counts, np.uint8)) if counts is not None else None, C.c_uint64(n), C.byref(dig)))
+        return rc, int(dig.value)
+
+    def kset_import(self, keys, counts=None) -> int:
+        """every key into the set, its count byte going up by counts[i] (None: 1 each) and stopping at 255; the digest of the records"""
+        rc, dig = self.kset_import_rc(keys, counts)
+        self._check(rc)
+        return dig
 
     def kset_end(self):
         self._check(self.lib.hypo_gpu_kset_end())

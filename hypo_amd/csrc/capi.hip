@@ -1206,6 +1206,20 @@ int ks_resize(Ctx::KSet& ks, uint64_t slots, hipStream_t st) {
     if (slots > ks.peak_slots) ks.peak_slots = slots;
     return HYPO_OK;
 }
+// Room for a call's worst case (every one of its `n_new` windows or records a new k-mer) is made before the table is touched: a call
+// that cannot get it leaves the set as it was (HYPO_E_CAPACITY), and no kernel ever meets a table more than half full.
+int ks_make_room(Ctx::KSet& ks, uint64_t n_new, const char* what, hipStream_t st) {
+    const uint64_t worst = ks.count + n_new;
+    const uint64_t need = ks_slots_for(worst);
+    if (need <= ks.slots) return HYPO_OK;
+    if (need > ks.max_slots)
+        return fail(HYPO_E_CAPACITY, "the k-mer set holds %llu distinct %u-mers in a table of %.3f GiB; %llu more %s need %.3f GiB, the cap is %.3f GiB (--qv-mem)",
+                    (unsigned long long)ks.count, ks.k, (double)ks.slots * ks.slot_bytes() / (1u << 30), (unsigned long long)n_new, what,
+                    (double)need * ks.slot_bytes() / (1u << 30), (double)ks.max_slots * ks.slot_bytes() / (1u << 30));
+    uint64_t slots = need > 2 * ks.slots ? need : 2 * ks.slots;
+    if (slots > ks.max_slots) slots = ks.max_slots;
+    return ks_resize(ks, slots, st);
+}
 // The entry points that need a live set: the lock, the device, `ks`.
 #define HYPO_KSET_ENTRY() \
     HYPO_ENTRY(); \
@@ -1288,20 +1302,7 @@ int hypo_gpu_kset_add(const char* bytes, uint64_t n) {
     if (n < ks.k) return HYPO_OK;                                       // holds no k-mer
     if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
     hipStream_t st = g_ctx.stream;
-    // Room for the call's worst case (every window a new k-mer) is made before the table is touched: a call that cannot get it
-    // leaves the set as it was, and no kernel ever meets a table more than half full.
-    const uint64_t worst = ks.count + (n - ks.k + 1);
-    const uint64_t need = ks_slots_for(worst);
-    if (need > ks.slots) {
-        if (need > ks.max_slots)
-            return fail(HYPO_E_CAPACITY, "the k-mer set holds %llu distinct %u-mers in a table of %.3f GiB; %llu more windows need %.3f GiB, the cap is %.3f GiB (--qv-mem)",
-                        (unsigned long long)ks.count, ks.k, (double)ks.slots * ks.slot_bytes() / (1u << 30), (unsigned long long)(n - ks.k + 1),
-                        (double)need * ks.slot_bytes() / (1u << 30), (double)ks.max_slots * ks.slot_bytes() / (1u << 30));
-        uint64_t slots = need > 2 * ks.slots ? need : 2 * ks.slots;
-        if (slots > ks.max_slots) slots = ks.max_slots;
-        const int rc = ks_resize(ks, slots, st);
-        if (rc != HYPO_OK) return rc;
-    }
+    if (const int rc = ks_make_room(ks, n - ks.k + 1, "windows", st)) return rc;
     HIP_TRY(ks.in.alloc(n < kKmerPiece ? n : kKmerPiece));
     // pieces as in hypo_gpu_kmer_count_add; a k-mer seen by two pieces is inserted twice, which changes nothing.  With counts on
     // every WINDOW must be in one piece only: consecutive pieces overlap by exactly k - 1 bytes (the step below), so a window lies
@@ -1791,6 +1792,87 @@ int hypo_gpu_kset_min_count(uint32_t t) {
     if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)");
     if (t < 1 || t > 255) return fail(HYPO_E_INVALID, "t = %u out of range 1..255 (the k-mer set counts up to 255)", t);
     ks.min_count = t;                                                  // read when a query launches: the counts are those of that moment
+    return HYPO_OK;
+}
+
+// ---- the set's records out and in (hypo --qv-save / --qv-load) ---------------------------------------------------------------------
+// The cursor of an export sequence is the first slot the next call looks at: a call takes at most `cap` slots, so it never has more
+// than `cap` records.  Arenas: ks.in holds the call's keys and, behind them, its count bytes; ks.off the tile sums and prefixes;
+// ks.res the digest.
+int hypo_gpu_kset_export(uint64_t* cursor, uint64_t* keys, uint8_t* counts, uint64_t cap, uint64_t* n_out, uint64_t* digest) {
+    HYPO_KSET_ENTRY();
+    if (!cursor || !keys || !n_out) return fail(HYPO_E_INVALID, "NULL buffer");
+    if (!cap || cap >= ((uint64_t)1 << 32)) return fail(HYPO_E_INVALID, "cap = %llu out of range 1..2^32 - 1", (unsigned long long)cap);
+    const uint64_t s0 = *cursor;
+    if (s0 == HYPO_KSET_EXPORT_END) { *n_out = 0; return HYPO_OK; }  // (the sequence has ended: nothing more comes)
+    if (s0 >= ks.slots) return fail(HYPO_E_INVALID, "cursor = %llu is no position in a table of %llu slots", (unsigned long long)s0, (unsigned long long)ks.slots);
+    const uint64_t n_slots = ks.slots - s0 < cap ? ks.slots - s0 : cap;
+    const uint32_t tiles = hypo::kset_export_tiles(n_slots);
+    hipStream_t st = g_ctx.stream;
+    HIP_TRY(ks.in.alloc((size_t)n_slots * 9));
+    HIP_TRY(ks.off.alloc(((size_t)tiles * 2 + 1) * 8));
+    HIP_TRY(ks.res.alloc(8));
+    uint64_t* d_keys = (uint64_t*)ks.in.p;
+    uint8_t* d_counts = (uint8_t*)ks.in.p + (size_t)n_slots * 8;
+    uint64_t* d_sums = (uint64_t*)ks.off.p;
+    uint64_t* d_pre = d_sums + tiles;
+    uint64_t got[2] = {0, 0};                                           // the records of the call, their digest
+    HIP_TRY(hipMemsetAsync(ks.res.p, 0, 8, st));
+    HIP_TRY(hypo::kset_export_run(ks.table, ks.planes, s0, n_slots, d_sums, d_pre, n_slots, d_keys, counts ? d_counts : nullptr,
+                                  (unsigned long long*)ks.res.p, st));
+    // the number of records comes back first: only the used prefix of the two arrays is copied
+    HIP_TRY(hipMemcpyAsync(&got[0], d_pre + tiles, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&got[1], ks.res.p, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (got[0] > n_slots) return fail(HYPO_E_HIP, "k-mer set: internal error: %llu records in %llu slots", (unsigned long long)got[0], (unsigned long long)n_slots);
+    if (got[0]) {
+        HIP_TRY(hipMemcpyAsync(keys, d_keys, (size_t)got[0] * 8, hipMemcpyDeviceToHost, st));
+        if (counts) HIP_TRY(hipMemcpyAsync(counts, d_counts, (size_t)got[0], hipMemcpyDeviceToHost, st));
+        HIP_TRY(hipStreamSynchronize(st));
+    }
+    *n_out = got[0];
+    if (digest) *digest += got[1];
+    *cursor = s0 + n_slots == ks.slots ? HYPO_KSET_EXPORT_END : s0 + n_slots;
+    return HYPO_OK;
+}
+
+int hypo_gpu_kset_import(const uint64_t* keys, const uint8_t* counts, uint64_t n, uint64_t* digest) {
+    HYPO_KSET_ENTRY();
+    if (ks.marked) return fail(HYPO_E_INVALID, "the k-mer set is closed: a text has been marked (hypo_gpu_kset_mark)");
+    if (n >= ((uint64_t)1 << 32)) return fail(HYPO_E_INVALID, "n = %llu records: a call takes fewer than 2^32", (unsigned long long)n);
+    if (!n) return HYPO_OK;
+    if (!keys) return fail(HYPO_E_INVALID, "NULL buffer");
+    hipStream_t st = g_ctx.stream;
+    HIP_TRY(ks.in.alloc((size_t)n * 9));
+    HIP_TRY(ks.res.alloc(24));
+    uint64_t* d_keys = (uint64_t*)ks.in.p;
+    uint8_t* d_counts = counts ? (uint8_t*)ks.in.p + (size_t)n * 8 : nullptr;
+    unsigned long long* d_bad = (unsigned long long*)ks.res.p;          // [0] a record was refused, [1] the least such index, [2] the digest
+    const unsigned long long fresh[3] = {0, ~0ull, 0};
+    unsigned long long bad[2] = {0, 0};
+    HIP_TRY(h2d(d_keys, keys, (size_t)n * 8, st));
+    if (counts) HIP_TRY(h2d(d_counts, counts, (size_t)n, st));
+    HIP_TRY(hipMemcpyAsync(d_bad, fresh, 24, hipMemcpyHostToDevice, st));
+    // every record is looked at on the device before the table is touched
+    HIP_TRY(hypo::kset_import_check_run(d_keys, d_counts, n, ks.k, d_bad, st));
+    HIP_TRY(hipMemcpyAsync(bad, d_bad, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (bad[0]) {
+        const uint64_t i = bad[1], key = keys[i];
+        if (key >> (2 * ks.k)) return fail(HYPO_E_INVALID, "record %llu: the key 0x%llx is not below 4^%u", (unsigned long long)i, (unsigned long long)key, ks.k);
+        if (counts && !counts[i]) return fail(HYPO_E_INVALID, "record %llu: the count byte is 0", (unsigned long long)i);
+        return fail(HYPO_E_INVALID, "record %llu: the key 0x%llx is not canonical: its reverse complement is smaller", (unsigned long long)i, (unsigned long long)key);
+    }
+    if (const int rc = ks_make_room(ks, n, "records", st)) return rc;
+    unsigned long long ctr[2] = {0, 0}, sum = 0;
+    HIP_TRY(hipMemsetAsync(ks.ctr.p, 0, 16, st));
+    HIP_TRY(hypo::kset_import_run(d_keys, d_counts, n, ks.table, ks.slots, (unsigned long long*)ks.ctr.p, ks.planes, d_bad + 2, st));
+    HIP_TRY(hipMemcpyAsync(ctr, ks.ctr.p, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(&sum, d_bad + 2, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    ks.count += ctr[0];
+    if (ctr[1]) return fail(HYPO_E_HIP, "k-mer set: internal error: a table of %llu slots with %llu keys had no room", (unsigned long long)ks.slots, (unsigned long long)ks.count);
+    if (digest) *digest += sum;
     return HYPO_OK;
 }
 

@@ -6,6 +6,7 @@
 #include "KmerGuard.hpp"
 #include "KmerBridge.hpp"
 #include "KmerFix.hpp"
+#include "KmerSetFile.hpp"
 #include "QvReport.hpp"
 #include "ReadKmerSet.hpp"
 #include "SpectraReport.hpp"
@@ -34,7 +35,10 @@ struct Extras {
     bool min_on() const { return min_given != 1; }
     bool ask_on = false;                                   // --qv or --qv-bed: every contig's texts are put to the set
     bool text_on = false;                                  // ... or --qv-spectra: every contig's texts are needed as strings
-    bool set_on = false;                                   // ... or --kmer-guard, --kmer-fix or --kmer-bridge: the set is built
+    bool set_on = false;                                   // ... or --kmer-guard, --kmer-fix, --kmer-bridge or --qv-save: the set is built
+    std::string save_to, load_from;                        // --qv-save / --qv-load: the set also goes to a file / comes from one, not from the reads
+    bool save_on() const { return !save_to.empty(); }
+    bool load_on() const { return !load_from.empty(); }
     ReadSink set_sink;                                     // (holds a pointer to set: an Extras stays where it is)
     VcfStats vstats;
     Extras() = default; Extras(const Extras&) = delete;
@@ -52,16 +56,66 @@ struct Extras {
         const int rc = ask_on ? qv.flush() : HYPO_OK;
         return rc == HYPO_OK && spectra_on ? spectra.flush() : rc;
     }
+    [[noreturn]] void set_file_fail(const char* flag, const std::string& why) {
+        std::fprintf(stderr, "[Hypo::QV] Error: %s: %s\n", flag, why.c_str());
+        set.end();
+        std::exit(1);
+    }
+    // --qv-load: the set comes from the file, where the reads would have been parsed for it.  Every block goes through
+    // hypo_gpu_kset_import; then the file's digest must be the sum those calls returned and its n_keys what hypo_gpu_kset_size says.
+    void set_load() {
+        const auto t0 = std::chrono::steady_clock::now();
+        KmerSetFileHeader h;
+        std::string err;
+        uint64_t in_file = 0, imported = 0;
+        int rc = 0;
+        auto block = [&](const uint64_t* keys, const uint8_t* counts, uint64_t n) { return set.import_records(keys, counts, n, &imported); };
+        if (!read_kmer_set_file(load_from, block, h, in_file, err, rc)) set_file_fail("--qv-load", rc ? err + ": " + hypo_gpu_last_error() : err);
+        char why[160];
+        if (imported != in_file) {
+            std::snprintf(why, sizeof why, ": digest mismatch: the file states %016llx, its records give %016llx", (unsigned long long)in_file, (unsigned long long)imported);
+            set_file_fail("--qv-load", load_from + why);
+        }
+        if (set.reads_done() != HYPO_OK) set_fail("hypo_gpu_kset_size");
+        if (set.n_distinct() != h.n_keys) {
+            std::snprintf(why, sizeof why, ": size mismatch: the file states %llu k-mers, the set holds %llu", (unsigned long long)h.n_keys, (unsigned long long)set.n_distinct());
+            set_file_fail("--qv-load", load_from + why);
+        }
+        const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+        std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer set loaded from %s (k = %u, %llu distinct k-mers, %.3f s)\n", load_from.c_str(), set.k(),
+                     (unsigned long long)set.n_distinct(), s);
+        set_ready();
+        std::fprintf(stderr, "[Hypo::QV] Info: k-mer set of the reads (k = %u): %llu distinct k-mers, from %s (no read parsed for it)\n", set.k(),
+                     (unsigned long long)set.n_distinct(), load_from.c_str());
+    }
     void set_reads_done(const SolidBuildStats& st, bool shared_pass) {
         if (set.reads_done() != HYPO_OK) set_fail("hypo_gpu_kset_size");
+        // --qv-save: the last read is in; every k-mer goes to the file, whatever the least count below is going to be
+        if (save_on()) {
+            const auto t0 = std::chrono::steady_clock::now();
+            std::string err;
+            uint64_t bytes = 0;
+            int rc = 0;
+            auto next = [&](uint64_t* cursor, uint64_t* keys, uint8_t* counts, uint64_t cap, uint64_t* n_out, uint64_t* digest) {
+                return set.export_records(cursor, keys, counts, cap, n_out, digest);
+            };
+            if (!write_kmer_set_file(save_to, set.k(), set.n_distinct(), next, bytes, err, rc)) set_file_fail("--qv-save", rc ? err + ": " + hypo_gpu_last_error() : err);
+            const double s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+            std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer set saved to %s (k = %u, %llu distinct k-mers, %llu bytes, %.3f s)\n", save_to.c_str(), set.k(),
+                         (unsigned long long)set.n_distinct(), (unsigned long long)bytes, s);
+        }
+        set_ready();
+        std::fprintf(stderr, "[Hypo::QV] Info: k-mer set of the reads (k = %u): %llu distinct k-mers, %.3f s in the insert calls of %.3f GB%s\n", set.k(),
+                     (unsigned long long)set.n_distinct(), st.sink_s, st.seq_bytes / 1e9, shared_pass ? " (the parse pass of the solid k-mers)" : " (reads parsed for the QV alone)");
+    }
+    // the set holds its last k-mer, from the reads or from a file
+    void set_ready() {
         // --qv-min-count: the last read is in and nothing has been asked yet; from here on the set answers for the reliable k-mers
         if (min_on()) {
             if (set.set_min_count(min_given) != HYPO_OK) set_fail("hypo_gpu_kset_spectrum / hypo_gpu_kset_min_count");
             std::fprintf(stdout, "[Hypo::Hypo] Info: k-mer min count (k = %u): >= %u (%s), %llu of %llu read k-mers reliable\n", set.k(), set.min_count(),
                          min_given ? "given" : "valley", (unsigned long long)set.n_reliable(), (unsigned long long)set.n_distinct());
         }
-        std::fprintf(stderr, "[Hypo::QV] Info: k-mer set of the reads (k = %u): %llu distinct k-mers, %.3f s in the insert calls of %.3f GB%s\n", set.k(),
-                     (unsigned long long)set.n_distinct(), st.sink_s, st.seq_bytes / 1e9, shared_pass ? " (the parse pass of the solid k-mers)" : " (reads parsed for the QV alone)");
     }
 };
 
@@ -185,11 +239,31 @@ void Hypo::bind_extras(Extras& ex) {
     ex.qv_on = !_cFlags.qv_filename.empty();
     ex.ask_on = ex.qv_on || ex.bed_on;
     ex.text_on = ex.ask_on || ex.spectra_on;
-    ex.set_on = ex.text_on || ex.guard_on || ex.fix_on || ex.bridge_on;
+    ex.save_to = _cFlags.qv_save_filename;
+    ex.load_from = _cFlags.qv_load_filename;
+    ex.set_on = ex.text_on || ex.guard_on || ex.fix_on || ex.bridge_on || ex.save_on();
     // Every entry point behind these flags is bound by name, and only under its flag, so that libraries without it still serve every
     // run without the flag.  The flags are checked in this order, and each one's error names what it needs.
     const bool have_set = (ex.set_on || ex.min_on()) && ex.set.bind();
     const std::string the_set = ReadKmerSet::kNames;
+    // --qv-save: the export of the set's records, and counts on the set so that the file serves every later flag
+    if (ex.save_on()) {
+        (void)ex.set.bind_counts();
+        require("--qv-save", {{" hypo_gpu_kset_export", ex.set.bind_export()}, {" hypo_gpu_kset_counts_enable", ex.set.have_counts()}, {" " + the_set, have_set}}, true);
+    }
+    // --qv-load: the import of records; the file's header is read now, so that a file that cannot serve ends the run before any stage
+    uint64_t load_keys = 0;
+    if (ex.load_on()) {
+        require("--qv-load", {{" hypo_gpu_kset_import", ex.set.bind_import()}, {" " + the_set, have_set}}, true);
+        KmerSetFileHeader h;
+        std::string err;
+        if (!read_kmer_set_header(ex.load_from, h, err)) { std::fprintf(stderr, "[Hypo::QV] Error: --qv-load: %s\n", err.c_str()); std::exit(1); }
+        if (h.k != _cFlags.qv_k) {
+            std::fprintf(stderr, "[Hypo::QV] Error: --qv-load: %s: the file holds k-mers of k = %u, --qv-k is %u\n", ex.load_from.c_str(), h.k, _cFlags.qv_k);
+            std::exit(1);
+        }
+        load_keys = h.n_keys;
+    }
     // --kmer-bridge-vote: the walk-sets query, and counts on the set it asks
     ex.vote_on = ex.bridge_on && _cFlags.kmer_bridge_vote != 0;
     if (ex.vote_on) {
@@ -231,13 +305,13 @@ void Hypo::bind_extras(Extras& ex) {
     if (ex.qv_on) require("--qv", {{" hypo_gpu_kset_begin / _add / _size / _query / _end (C-ABI 11)", ex.qv.bind() && have_set}});
     // the set lives on context 0 from here until the last contig is written
     if (ex.set_on) {
-        // (sized for one k-mer per genome position; what the read errors add makes it grow)
+        // (sized for one k-mer per genome position; what the read errors add makes it grow.  --qv-load: for the file's k-mers)
         const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
-        if (ex.set.begin(_cFlags.qv_k, _cFlags.genome_size, cap) != HYPO_OK) ex.set_fail("the k-mer set could not be created");
+        if (ex.set.begin(_cFlags.qv_k, ex.load_on() ? load_keys : _cFlags.genome_size, cap) != HYPO_OK) ex.set_fail("the k-mer set could not be created");
         ex.set_sink = ex.set.sink();
-        // --qv-spectra, --qv-min-count, --kmer-bridge-vote: the set counts from its first k-mer on, with a plane of copy bytes for each
+        // --qv-spectra, --qv-min-count, --kmer-bridge-vote, --qv-save: the set counts from its first k-mer on, with a plane of copy bytes for each
         // text that is going to be marked (one at the least), and the reads reach it window by window, each once
-        if (ex.spectra_on || ex.min_on() || ex.vote_on) {
+        if (ex.spectra_on || ex.min_on() || ex.vote_on || ex.save_on()) {
             if (ex.set.enable_counts(ex.spectra_on ? SpectraReport::N_TEXTS : 1) != HYPO_OK) ex.set_fail("the k-mer set could not be made to count");
             ex.set_sink.exact = true;
         }
@@ -250,7 +324,7 @@ void Hypo::solid_kmers(Extras& ex, std::ofstream& stagefile, SolidKmers& sk) {
     if (_cFlags.done_stage < 1) {
         SolidBuildStats st;
         std::string err;
-        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err, ex.set_on ? &ex.set_sink : nullptr);
+        const int rc = build_solid_kmers(_cFlags.sr_filenames, _cFlags.k, _cFlags.cov, (int)_cFlags.threads, sk, st, err, ex.set_on && !ex.load_on() ? &ex.set_sink : nullptr);
         if (rc == SOLID_E_SINK) { std::fprintf(stderr, "[Hypo::QV] Error: the k-mer set of the reads: %s\n", err.c_str()); ex.set.end(); std::exit(1); }
         if (rc == SOLID_E_UNDEFINED) {                   // the reference's own line for a failed initialise (src/Hypo.cpp:53)
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: %s\n", err.c_str());
@@ -263,7 +337,8 @@ void Hypo::solid_kmers(Extras& ex, std::ofstream& stagefile, SolidKmers& sk) {
         }
         std::fprintf(stderr, "[Hypo::SolidKmers] Info: device construction: %.3f s (parse %.3f s of %.3f GB, count %.3f s of %.3f GB sent, "
                              "histogram %.3f s, set %.3f s)\n", st.total_s, st.parse_s, st.file_bytes / 1e9, st.count_s, st.seq_bytes / 1e9, st.hist_s, st.fill_s);
-        if (ex.set_on) ex.set_reads_done(st, true);
+        if (ex.set_on && ex.load_on()) ex.set_load();          // (the solid k-mers were counted from the reads, without the sink)
+        else if (ex.set_on) ex.set_reads_done(st, true);
         if (_cFlags.intermed) {
             if (!sk.store(HYPO_SKFILE)) {
                 std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Saving: Could not store the DS for Solid kmers!\n");
@@ -282,7 +357,8 @@ void Hypo::solid_kmers(Extras& ex, std::ofstream& stagefile, SolidKmers& sk) {
             std::fprintf(stderr, "[Hypo::SolidKmers] Error: File Loading: Could not load the DS for Solid kmers (%s)!\n", HYPO_SKFILE);
             std::exit(1);
         }
-        if (ex.set_on) {                                 // the stored set needs no reads; the QV and the guard do
+        if (ex.set_on && ex.load_on()) ex.set_load();    // neither set needs the reads: none is opened
+        else if (ex.set_on) {                            // the stored set needs no reads; the QV and the guard do
             SolidBuildStats st;
             std::string err;
             const int rc = stream_reads(_cFlags.sr_filenames, ex.set_sink, st, err);

@@ -24,6 +24,16 @@ bool ReadKmerSet::bind_track() {
     return have_track();
 }
 
+bool ReadKmerSet::bind_export() {
+    _export = (decltype(_export))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_export");
+    return _export != nullptr;
+}
+
+bool ReadKmerSet::bind_import() {
+    _import = (decltype(_import))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_import");
+    return _import != nullptr;
+}
+
 int ReadKmerSet::begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes) {
     const int rc = _begin(k, expected_distinct, max_bytes);
     if (rc != HYPO_OK) return rc;

@@ -31,6 +31,9 @@ public:
     bool have_counts() const { return _counts_enable && _spectrum; }             // what --qv-spectra needs of the three
     bool have_min_count() const { return _set_min_count != nullptr; }
     bool have_track() const { return _track != nullptr; }
+    // --qv-save / --qv-load: hypo_gpu_kset_export / hypo_gpu_kset_import
+    bool bind_export();
+    bool bind_import();
 
     // the set on the calling thread's context; max_bytes 0 = the library's default cap
     int begin(uint32_t k, uint64_t expected_distinct, uint64_t max_bytes);
@@ -41,6 +44,12 @@ public:
     // --qv-min-count, after the reads and before the first query: reads the histogram of the read counts, takes t = `given` or, for
     // 0, its valley, and from then on every query of the set is answered against the k-mers seen at least t times
     int set_min_count(uint32_t given);
+    // --qv-save / --qv-load: one call of hypo_gpu_kset_export / hypo_gpu_kset_import (host/KmerSetFile.hpp moves the records between
+    // these and the file)
+    int export_records(uint64_t* cursor, uint64_t* keys, uint8_t* counts, uint64_t cap, uint64_t* n_out, uint64_t* digest) const {
+        return _export(cursor, keys, counts, cap, n_out, digest);
+    }
+    int import_records(const uint64_t* keys, const uint8_t* counts, uint64_t n, uint64_t* digest) { return _import(keys, counts, n, digest); }
     void end();                                              // frees the set (safe to call twice, and after a begin that failed)
 
     bool open() const { return _open; }
@@ -65,6 +74,8 @@ private:
     int (*_spectrum)(uint32_t, uint64_t*) = nullptr;
     int (*_set_min_count)(uint32_t) = nullptr;
     int (*_track)(const char*, const uint64_t*, uint32_t, const uint8_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t) = nullptr;
+    int (*_export)(uint64_t*, uint64_t*, uint8_t*, uint64_t, uint64_t*, uint64_t*) = nullptr;
+    int (*_import)(const uint64_t*, const uint8_t*, uint64_t, uint64_t*) = nullptr;
     bool _open = false;
     uint32_t _k = 0, _min_count = 1;
     uint64_t _n_distinct = 0, _n_reliable = 0;

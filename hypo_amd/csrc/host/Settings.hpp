@@ -40,6 +40,8 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     uint32_t kmer_bridge_max = 64;         // new, opt-in: --kmer-bridge-max (2..192: the largest anchor distance tried)
     uint32_t kmer_bridge_slack = 8;        // new, opt-in: --kmer-bridge-slack (0..64: the most bases a bridge may add or remove)
     uint32_t kmer_bridge_vote = 0;         // new, opt-in: --kmer-bridge-vote (2..255, 0 = off: an ambiguous bridge goes to the walk the reads support this many times better)
+    std::string qv_save_filename;          // new, opt-in: --qv-save <file> (the k-mer set of the reads, with its counts, is also written to the file)
+    std::string qv_load_filename;          // new, opt-in: --qv-load <file> (the k-mer set comes from the file of --qv-save; the reads are not parsed for it)
     uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
 };
 

@@ -36,7 +36,8 @@ const struct option long_options[] = {
     {"qv-reliable-min", required_argument, nullptr, 1016}, {"qv-min-count", required_argument, nullptr, 1017},
     {"kmer-fix", required_argument, nullptr, 1018}, {"kmer-bridge", required_argument, nullptr, 1019},
     {"kmer-bridge-max", required_argument, nullptr, 1020}, {"kmer-bridge-slack", required_argument, nullptr, 1021},
-    {"kmer-bridge-vote", required_argument, nullptr, 1022}, {nullptr, 0, nullptr, 0}};
+    {"kmer-bridge-vote", required_argument, nullptr, 1022}, {"qv-save", required_argument, nullptr, 1023},
+    {"qv-load", required_argument, nullptr, 1024}, {nullptr, 0, nullptr, 0}};
 
 // Same layout as the reference's usage() (src/main.cpp:363-430): "Usage: hypo <args>", the mandatory block, the optional
 // block, every flag as "-x, --long <type>" followed by what it does and its default.  The wording is this build's own.
@@ -74,6 +75,8 @@ void usage() {
         {"    --qv <str>", "[MI355X build] Also write the reference-free k-mer QV of every draft contig and of its polished text as a tab-separated file: the canonical k-mers of the short reads (-r) are kept as an exact set on the device, and a k-mer of a contig that is not among them counts as an error (Merqury's definition). The reads are parsed once for this and the solid k-mers; a run that starts from stage 1 (-i) parses them for the QV alone.", "no QV"},
         {"    --qv-k <int>", "[MI355X build] k-mer length of --qv, 12 to 31.", "21"},
         {"    --qv-mem <GiB>", "[MI355X build] Largest table the k-mer set of --qv may grow to; a read set that needs more ends the run before any contig is polished.", "half of the device's free memory"},
+        {"    --qv-save <str>", "[MI355X build] Also write the k-mer set of the short reads to this file when the last read is in, before any contig is polished: every k-mer with the number of times the reads contain it (up to 255), whatever --qv-min-count says, so that the file serves every flag of a later run. The set is built and stored even when no other flag asks for it, and counts as under --qv-min-count (one more byte a slot under --qv-mem); every other output is what it is without the flag. The file is written under <file>.tmp and complete the moment it has its name; a run that fails later keeps it.", "the set is not stored"},
+        {"    --qv-load <str>", "[MI355X build] Fill the k-mer set from a file of --qv-save instead of from the short reads: the reads are not parsed for it (a run that starts from stage 1 opens none), and every output file is byte for byte that of the run that built the set. The file's k must be --qv-k; a file that is damaged, or whose records do not add up to its digest, ends the run before any output is opened. Needs a flag that asks the set (--qv, --qv-bed, --qv-spectra, --kmer-guard, --kmer-fix, --kmer-bridge); not together with --qv-save.", "the set is built from the reads"},
         {"    --kmer-guard", "[MI355X build] Keep only the edits the k-mers of the short reads support: edits closer than k - 1 draft bases form a cluster, and a cluster that puts more k-mers no read contains into the contig than it removes is left out of the output (its VCF records get FILTER kmer instead of PASS; the polished columns of --qv describe the guarded text). Uses the k-mer set of --qv (--qv-k, --qv-mem) with or without --qv and --vcf.", "off"},
         {"    --guard-records", "[MI355X build] Implies --kmer-guard, and decides a cluster of 2 to --guard-records-max edits record by record: of all subsets of the cluster's records the one whose text lacks the fewest k-mers of the reads is kept (among equals the one with the most records), the other records get FILTER kmer. A single bad edit then no longer costs its neighbours. Larger clusters are accepted or rejected whole, as with --kmer-guard.", "off"},
         {"    --guard-records-max <int>", "[MI355X build] Most records of a cluster --guard-records still decides one by one, 2 to 12 (a cluster of n records has 2^n subsets). Without --guard-records it has no effect.", "8"},
@@ -234,6 +237,8 @@ int main(int argc, char** argv) {
             case 1020: flags.kmer_bridge_max = int_in("--kmer-bridge-max", optarg, 2, 192); bridge_opts = true; break;
             case 1021: flags.kmer_bridge_slack = int_in("--kmer-bridge-slack", optarg, 0, 64); bridge_opts = true; break;
             case 1022: flags.kmer_bridge_vote = int_in("--kmer-bridge-vote", optarg, 2, 255); break;
+            case 1023: flags.qv_save_filename = optarg; break;
+            case 1024: flags.qv_load_filename = optarg; break;
             case 1002: {
                 flags.devices.clear();
                 for (const char* c = optarg; *c;) { flags.devices.push_back(std::atoi(c)); while (*c && *c != ',') ++c; if (*c == ',') ++c; }
@@ -253,6 +258,15 @@ int main(int argc, char** argv) {
     }
     if (flags.kmer_bridge_vote && flags.kmer_bridge_filename.empty()) {
         std::fprintf(stderr, "[Hypo::] Error: Arg Error: --kmer-bridge-vote (2 to 255) settles what --kmer-bridge leaves ambiguous: it needs --kmer-bridge!\n");
+        std::exit(1);
+    }
+    if (!flags.qv_save_filename.empty() && !flags.qv_load_filename.empty()) {
+        std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-save stores the k-mer set a run builds from the reads, --qv-load takes it from a file instead: give one of them!\n");
+        std::exit(1);
+    }
+    if (!flags.qv_load_filename.empty() && flags.qv_filename.empty() && flags.qv_bed_filename.empty() && flags.qv_spectra_filename.empty() && !flags.kmer_guard &&
+        flags.kmer_fix_filename.empty() && flags.kmer_bridge_filename.empty()) {
+        std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-load fills the k-mer set that --qv, --qv-bed, --qv-spectra, --kmer-guard, --kmer-fix and --kmer-bridge ask: it needs at least one of them!\n");
         std::exit(1);
     }
     if (!(is_sr && is_draft && is_size && is_bamsr && is_cov)) {

@@ -29,6 +29,8 @@
 //   * a least count (hypo --qv-min-count; further down, with comments of their own): the query, track-flags, spans and variants
 //     kernels once more as kset_*_min_kernel, whose probe also loads the hit slot's count byte and answers "seen at least t times".
 //     They are instances of the same bodies with a compile-time switch; the kernels above do not know of t.
+//   * export and import (hypo --qv-save / --qv-load; at the end, with comments of their own): the table's records out in slot order
+//     by a stream compaction, and records back in with a saturating add of their count bytes.
 // Forward progress: every probe loop runs at most `slots` steps.  A lane of the insert or rehash kernel that finds neither its key
 // nor a free slot sets the overflow flag and leaves; lanes in a long probe look at the flag every 64 steps and leave too.  The host
 // keeps the table at most half full, so the flag says "internal error", but no input can make a kernel spin.
@@ -1186,6 +1188,189 @@ hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_
     if (min_count > 1)
         kset_query_min_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing, (const uint8_t*)planes, min_count);
     else kset_query_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing);
+    return hipGetLastError();
+}
+
+// ---- the set's records out of the table and back in (hypo --qv-save / --qv-load; DESIGN.md "k-mer set file") ------------------------
+// A record is a key as the table holds it and its count byte (1 on a set that keeps no counts).  The digest of a record is
+// mix64(key) + count * KS_DIGEST_MUL mod 2^64, that of a list the sum over its records: integers, so the order of the sum is free.
+// Export is an ordered stream compaction of the slot range [s0, s0 + n_slots), s0 + n_slots <= slots, which the host bounds to the
+// caller's `cap`: a range never holds more keys than slots.  A workgroup owns a tile of KS_THREADS consecutive slots of the range,
+// a lane one slot; lanes of the last tile beyond the range own nothing.
+//   * kset_export_count_kernel: the occupied slots of every tile, one plain store per workgroup.
+//   * kset_export_scan_kernel: ONE workgroup turns the tile sums into exclusive prefixes, KS_SCAN_THREADS of them per pass (the pattern of
+//     kset_track_scan_kernel with one field), and leaves the range's total behind the last one.
+//   * kset_export_emit_kernel: the same loads again; a lane's rank is the prefix of its tile, the occupied slots of the waves before
+//     its own (through LDS) and those of the lanes before it (a ballot and a popcount), so the records come in ascending slot order
+//     and the arrays are a function of the table alone.  Keys are stored as 8-byte values, counts as bytes.  The digests are summed
+//     per wave and added once per wave.
+// No kernel waits for another workgroup and none loops over slots.  Bounds: slots are read at s0 + i for i < n_slots only (the host
+// checked s0 + n_slots <= slots), count bytes at the same indices of a plane of ks_plane_words(slots) * 4 >= slots bytes; tile sums
+// below n_tiles = gridDim.x of the count and emit kernels, prefixes below n_tiles + 1; records below `cap` (checked per store; the
+// host passes cap >= n_slots).  Loops: scan passes = ceil(n_tiles / KS_SCAN_THREADS), the waves of a workgroup.
+constexpr uint64_t KS_DIGEST_MUL = 0x9e3779b97f4a7c15ull;
+
+__device__ __forceinline__ uint64_t ks_wave_sum64(uint64_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_export_count_kernel(const uint64_t* __restrict__ table, uint64_t s0, uint64_t n_slots,
+                                                                        uint64_t* __restrict__ sums) {
+    __shared__ uint32_t part[KS_THREADS / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x;
+    const bool used = i < n_slots && table[s0 + i] != KSET_EMPTY;
+    const uint32_t n = (uint32_t)__popcll(__ballot(used));
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = n;
+    __syncthreads();
+    if (threadIdx.x == 0) sums[blockIdx.x] = (uint64_t)part[0] + part[1] + part[2] + part[3];
+}
+
+// pre[t]: the occupied slots of the tiles before t; pre[n_tiles]: those of the range
+__global__ void __launch_bounds__(KS_SCAN_THREADS) kset_export_scan_kernel(const uint64_t* __restrict__ sums, uint32_t n_tiles, uint64_t* __restrict__ pre) {
+    constexpr int WAVES = KS_SCAN_THREADS / 64;
+    __shared__ uint64_t part[WAVES];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint64_t carry = 0;
+    for (uint32_t base = 0; base < n_tiles; base += KS_SCAN_THREADS) {
+        const uint32_t i = base + threadIdx.x;
+        const uint64_t v = i < n_tiles ? sums[i] : 0;
+        const uint64_t inc = ks_wave_inclusive(v);
+        if (lane == 63) part[wave] = inc;
+        __syncthreads();
+        uint64_t before = carry, all = 0;
+        for (int x = 0; x < WAVES; ++x) { const uint64_t t = part[x]; if ((uint32_t)x < wave) before += t; all += t; }
+        if (i < n_tiles) pre[i] = before + inc - v;
+        carry += all;
+        __syncthreads();                                        // (part is written again in the next pass)
+    }
+    if (threadIdx.x == 0) pre[n_tiles] = carry;
+}
+
+// counts: plane 0 as bytes, or NULL (every count is 1); out_counts: NULL when the caller wants none; digest: one 64-bit sum
+__global__ void __launch_bounds__(KS_THREADS) kset_export_emit_kernel(const uint64_t* __restrict__ table, const uint8_t* __restrict__ counts, uint64_t s0,
+                                                                       uint64_t n_slots, const uint64_t* __restrict__ pre, uint64_t cap,
+                                                                       uint64_t* __restrict__ out_keys, uint8_t* __restrict__ out_counts,
+                                                                       unsigned long long* digest) {
+    __shared__ uint32_t part[KS_THREADS / 64];
+    const uint64_t i = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x;
+    const uint32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const uint64_t key = i < n_slots ? table[s0 + i] : KSET_EMPTY;
+    const bool used = key != KSET_EMPTY;
+    const uint32_t c = used && counts ? counts[s0 + i] : 1u;
+    const uint64_t mask = __ballot(used);
+    if (lane == 0) part[wave] = (uint32_t)__popcll(mask);
+    __syncthreads();
+    uint64_t rank = pre[blockIdx.x] + (uint64_t)__popcll(mask & ((1ull << lane) - 1ull));
+    for (uint32_t x = 0; x < wave; ++x) rank += part[x];
+    if (used && rank < cap) {
+        out_keys[rank] = key;
+        if (out_counts) out_counts[rank] = (uint8_t)c;
+    }
+    const uint64_t d = ks_wave_sum64(used ? ks_mix64(key) + (uint64_t)c * KS_DIGEST_MUL : 0ull);
+    if (lane == 0 && mask) atomicAdd(digest, (unsigned long long)d);
+}
+
+// Import: n records handed in as two arrays.  kset_import_check_kernel looks at all of them before the table is touched, and
+// kset_import_kernel puts them in: a lane per record in a grid-stride loop (keys are loaded coalesced), ks_insert<true> for the
+// slot, and on a set that counts ks_byte_add for the count byte.  The same key twice in a call, in neighbouring lanes or not, is
+// two adds to one byte.
+//   * a record is refused when its key is not below 4^k, is greater than its reverse complement (not canonical), or its count byte
+//     is 0: a wave that holds one takes the least index among its lanes and lowers bad[1] to it with ONE atomic, and stores 1 in
+//     bad[0] (the same value from every wave).  bad[1] starts as all-ones, so it ends as the least refused index of the call.
+//   * new keys (32 bits a lane: a lane sees at most ceil(n / lanes of the grid) < 2^32 records) and digests are summed per wave and
+//     added once per wave.
+// Bounds: keys / counts are read below n; slots as ks_insert says (at most `slots` steps, the overflow flag looked at every 64); the
+// byte of a slot < slots in a plane of ks_plane_words(slots) words.  Loops: grid-stride, ceil(n / lanes of the grid) rounds.
+__device__ __forceinline__ uint64_t ks_revcomp(uint64_t key, uint32_t k) {     // of a code below 4^k
+    uint64_t x = ~key;                                          // (the bits above 2k turn to ones and leave at the low end)
+    x = ((x >> 2) & 0x3333333333333333ull) | ((x & 0x3333333333333333ull) << 2);
+    x = ((x >> 4) & 0x0f0f0f0f0f0f0f0full) | ((x & 0x0f0f0f0f0f0f0f0full) << 4);
+    return __builtin_bswap64(x) >> (64 - 2 * k);
+}
+
+// ks_byte_inc adding v = 1..255: byte `slot` of `plane` becomes min(255, byte + v).  The same compare-and-swap loop: the lane loads
+// first and does nothing once the byte reads 255; saturation is decided on the value the atomic returned, the new word differs
+// from that value in this slot's byte only, and it is only ever swapped in against the word it was made from, so no byte wraps and
+// no neighbour is touched.  Lock-free: a swap fails only because another lane's went through, every swap that goes through raises
+// a byte of the word by at least 1, and a word takes at most 4 * 255 of them: at most 1021 rounds whatever the input is.
+// Bounds: slot < slots, and a plane has ks_plane_words(slots) words.
+__device__ __forceinline__ void ks_byte_add(uint32_t* plane, uint64_t slot, uint32_t v) {
+    uint32_t* w = plane + (slot >> 2);
+    const uint32_t sh = 8u * (uint32_t)(slot & 3);
+    uint32_t cur = __hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (;;) {
+        const uint32_t b = (cur >> sh) & 0xffu;
+        if (b == 0xffu) return;
+        const uint32_t nb = b + v < 0xffu ? b + v : 0xffu;
+        const uint32_t prev = atomicCAS(w, cur, (cur & ~(0xffu << sh)) | (nb << sh));
+        if (prev == cur) return;
+        cur = prev;
+    }
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_import_check_kernel(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ counts, uint64_t n,
+                                                                        uint32_t k, unsigned long long* bad) {
+    const uint64_t stride = (uint64_t)gridDim.x * KS_THREADS;
+    const uint64_t end = 1ull << (2 * k);
+    unsigned long long first = ~0ull;                           // the least refused index this lane has seen
+    for (uint64_t i = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x; i < n; i += stride) {
+        const uint64_t key = keys[i];
+        if ((key >= end || key > ks_revcomp(key, k) || (counts && counts[i] == 0)) && i < first) first = i;
+    }
+    for (int o = 32; o > 0; o >>= 1) { const unsigned long long u = __shfl_xor(first, o); if (u < first) first = u; }
+    if ((threadIdx.x & 63) == 0 && first != ~0ull) { atomicMin(bad + 1, first); bad[0] = 1ull; }
+}
+
+// plane: the count plane of a set that counts, or NULL; counts: NULL = 1 each; ctr as for kset_insert_kernel
+__global__ void __launch_bounds__(KS_THREADS) kset_import_kernel(const uint64_t* __restrict__ keys, const uint8_t* __restrict__ counts, uint64_t n,
+                                                                  uint64_t* table, uint64_t slots, unsigned long long* ctr, uint32_t* plane,
+                                                                  unsigned long long* digest) {
+    const uint64_t stride = (uint64_t)gridDim.x * KS_THREADS;
+    uint32_t n_new = 0;
+    uint64_t d = 0;
+    for (uint64_t i = (uint64_t)blockIdx.x * KS_THREADS + threadIdx.x; i < n; i += stride) {
+        const uint64_t key = keys[i];
+        const uint32_t c = counts ? counts[i] : 1u;
+        uint64_t at;
+        n_new += ks_insert<true>(table, slots, key, ctr, &at);
+        if (plane && at != KSET_EMPTY) ks_byte_add(plane, at, c);
+        d += ks_mix64(key) + (uint64_t)c * KS_DIGEST_MUL;
+    }
+    ks_wave_add(ctr, n_new);
+    d = ks_wave_sum64(d);
+    if ((threadIdx.x & 63) == 0 && d) atomicAdd(digest, (unsigned long long)d);
+}
+
+uint32_t kset_export_tiles(uint64_t n_slots) { return (uint32_t)((n_slots + KS_THREADS - 1) / KS_THREADS); }
+
+hipError_t kset_export_run(const uint64_t* table, const uint32_t* planes, uint64_t s0, uint64_t n_slots, uint64_t* sums, uint64_t* pre, uint64_t cap,
+                           uint64_t* out_keys, uint8_t* out_counts, unsigned long long* digest, hipStream_t st) {
+    if (!n_slots) return hipSuccess;
+    const uint32_t tiles = kset_export_tiles(n_slots);
+    kset_export_count_kernel<<<dim3(tiles), dim3(KS_THREADS), 0, st>>>(table, s0, n_slots, sums);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return e;
+    kset_export_scan_kernel<<<dim3(1), dim3(KS_SCAN_THREADS), 0, st>>>(sums, tiles, pre);
+    if ((e = hipGetLastError()) != hipSuccess) return e;
+    kset_export_emit_kernel<<<dim3(tiles), dim3(KS_THREADS), 0, st>>>(table, (const uint8_t*)planes, s0, n_slots, pre, cap, out_keys, out_counts, digest);
+    return hipGetLastError();
+}
+
+hipError_t kset_import_check_run(const uint64_t* keys, const uint8_t* counts, uint64_t n, uint32_t k, unsigned long long* bad, hipStream_t st) {
+    if (!n) return hipSuccess;
+    uint64_t blocks = (n + KS_THREADS - 1) / KS_THREADS;
+    if (blocks > 16384) blocks = 16384;
+    kset_import_check_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(keys, counts, n, k, bad);
+    return hipGetLastError();
+}
+
+hipError_t kset_import_run(const uint64_t* keys, const uint8_t* counts, uint64_t n, uint64_t* table, uint64_t slots, unsigned long long* ctr,
+                           uint32_t* planes, unsigned long long* digest, hipStream_t st) {
+    if (!n) return hipSuccess;
+    uint64_t blocks = (n + KS_THREADS - 1) / KS_THREADS;
+    if (blocks > 16384) blocks = 16384;
+    kset_import_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(keys, counts, n, table, slots, ctr, planes, digest);
     return hipGetLastError();
 }
 

@@ -120,4 +120,20 @@ hipError_t kset_walk_sets_run(const uint8_t* bytes, const uint64_t* from, const 
                               uint32_t budget, uint32_t k, const uint64_t* table, uint64_t slots, const uint32_t* planes, uint32_t min_count, uint32_t* status,
                               uint32_t* steps, uint32_t* n_walks, uint32_t* len, uint32_t* low, uint8_t* walk, hipStream_t st);
 
+// The set's records out and in (hypo --qv-save / --qv-load; DESIGN.md "k-mer set file").  A record: a key of the table and its count
+// byte (1 when `planes` is NULL); its digest: mix64(key) + count * 0x9e3779b97f4a7c15.
+// export: the keys of slots [s0, s0 + n_slots) (s0 + n_slots <= slots, n_slots <= cap) in ascending slot order into out_keys /
+// out_counts (may be NULL), *digest += the sum of their digests, pre[tiles] = their number, tiles = kset_export_tiles(n_slots).
+// Work space: sums of tiles and pre of tiles + 1 64-bit words; neither needs clearing.
+uint32_t kset_export_tiles(uint64_t n_slots);
+hipError_t kset_export_run(const uint64_t* table, const uint32_t* planes, uint64_t s0, uint64_t n_slots, uint64_t* sums, uint64_t* pre, uint64_t cap,
+                           uint64_t* out_keys, uint8_t* out_counts, unsigned long long* digest, hipStream_t st);
+// import, first the check: bad[0] = 1 and bad[1] = the least index i with keys[i] >= 4^k, keys[i] above its reverse complement, or
+// counts[i] == 0 (counts may be NULL); the caller sets bad[] = {0, all-ones}.  Then the records into the table: ctr[0] += new keys,
+// ctr[1] the overflow flag, with `planes` every key's count byte becomes min(255, byte + counts[i]) (NULL counts: 1 each), *digest
+// += the sum of the records' digests.  The caller has made room for n new keys.
+hipError_t kset_import_check_run(const uint64_t* keys, const uint8_t* counts, uint64_t n, uint32_t k, unsigned long long* bad, hipStream_t st);
+hipError_t kset_import_run(const uint64_t* keys, const uint8_t* counts, uint64_t n, uint64_t* table, uint64_t slots, unsigned long long* ctr,
+                           uint32_t* planes, unsigned long long* digest, hipStream_t st);
+
 }  // namespace hypo

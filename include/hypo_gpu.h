@@ -598,6 +598,36 @@ int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist);
  * R_255 holds the k-mers seen 255 times or more.  HYPO_E_INVALID: no set, a set without counts, t outside 1..255; a refused call
  * changes nothing.  On the calling thread's context. */
 int hypo_gpu_kset_min_count(uint32_t t);
+/* The set's records out of the table and back in (hypo --qv-save / --qv-load; DESIGN.md "k-mer set file").  Additive to ABI 11:
+ * callers bind them by name.  A record is a canonical code as the table stores it (min(fwd, rc), A0 C1 G2 T3, MSB-first, below
+ * 4^k) and a count byte: 1..255 on a set that counts (hypo_gpu_kset_counts_enable), 1 on a set that does not.  The digest of a
+ * record is mix64(key) + count * 0x9e3779b97f4a7c15 (mod 2^64), where mix64 is the finaliser of MurmurHash3,
+ *     x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33;
+ * and the digest of a list is the sum of its records' digests (mod 2^64): it does not depend on their order.
+ *  - hypo_gpu_kset_export(cursor, keys, counts, cap, n_out, digest): a sequence of calls starts with *cursor == 0 and ends when a
+ *    call leaves HYPO_KSET_EXPORT_END in it (a call that finds it there writes *n_out = 0).  A call writes *n_out <= cap records
+ *    into keys[] and, unless it is NULL, counts[], and moves the cursor on; it may return fewer than cap, even none, before the
+ *    end.  Entries at and beyond *n_out are not written.  Over an unchanged set every record comes from exactly one call of the
+ *    sequence and the *n_out add up to hypo_gpu_kset_size's n_distinct; the answer is a function of the table, so two sequences
+ *    with the same caps return identical arrays.  With digest != NULL the digest of the call's records, summed on the device, is
+ *    added to *digest.  The copy bytes of hypo_gpu_kset_mark are not exported; a closed set exports as an open one.  Changing the
+ *    set between two calls of a sequence leaves open which records come, and nothing else.  HYPO_E_INVALID: a NULL cursor, keys or
+ *    n_out; cap == 0 or cap >= 2^32; a cursor that is neither 0, nor below the table's end, nor what a call handed back; no set.
+ *  - hypo_gpu_kset_import(keys, counts, n, digest): for each i < n, keys[i] enters the set if it is absent, and on a set that
+ *    counts its count becomes min(255, count + counts[i]) (counts == NULL: 1 each).  The same key several times, in one call or in
+ *    several, adds up: the exports of two halves of a read stream, imported one after the other, give the set and the counts of
+ *    the whole stream.  A set that does not count checks the counts and otherwise ignores them.  Before the table is touched
+ *    every record is checked on the device: keys[i] < 4^k, keys[i] <= its reverse complement, counts[i] >= 1; a violation is
+ *    HYPO_E_INVALID, hypo_gpu_last_error names the least offending index, and the set stays as it was.  Room for n new keys is
+ *    made as hypo_gpu_kset_add makes it, the counts move with a growth, and HYPO_E_CAPACITY leaves the set as it was.  With digest
+ *    != NULL the digest of the n records as given (not as merged) is added to *digest.  HYPO_E_INVALID also: a closed set (as
+ *    hypo_gpu_kset_add), n >= 2^32, NULL keys with n > 0, no set.  n == 0 touches nothing.
+ * A refused call changes nothing.  Both are synchronous and run on the calling thread's context. */
+#define HYPO_KSET_EXPORT_END 0xffffffffffffffffull
+int hypo_gpu_kset_export(uint64_t* cursor, uint64_t* keys, uint8_t* counts /* may be NULL */,
+                         uint64_t cap, uint64_t* n_out, uint64_t* digest /* may be NULL */);
+int hypo_gpu_kset_import(const uint64_t* keys, const uint8_t* counts /* NULL: 1 each */,
+                         uint64_t n, uint64_t* digest /* may be NULL */);
 
 /* Kernel timing: each kernel's own start and end time --------------------------------------------
  * hypo_gpu_profile_begin(max_calls) arms the next max_calls (<= 256) *_device calls: each binds HIP
