@@ -171,6 +171,7 @@ struct Ctx {
         uint32_t min_count = 1;                            // hypo_gpu_kset_min_count: the queries answer against the keys counted at least this often
         uint64_t plane_bytes(uint64_t n_slots) const { return n_texts ? (1 + (uint64_t)n_texts) * hypo::ks_plane_words(n_slots) * 4 : 0; }
         double slot_bytes() const { return n_texts ? 9.0 + n_texts : 8.0; }      // what max_bytes caps, per slot
+        hypo::KsetView view() const { return {table, slots, k, planes, min_count}; }   // what the queries' launchers read of the set
     };
     KSet ks;
     size_t mem_free_at_init = 0;                       // hipMemGetInfo when the context was created (default cap of the k-mer set)
@@ -333,15 +334,18 @@ struct Carver {                                       // lays arrays out in one 
     size_t take(size_t bytes) { const size_t o = at; at += pad(bytes); return o; }
 };
 
-// A device buffer that a Carver laid out, on the stream that fills it: dev.u32(o) / .u64(o) / .u8(o) / .at<T>(o) is the array at byte
-// offset o with the element type named; dev.up(o, src, bytes) sends host memory there (nothing for an empty array).
+// A device buffer that a Carver laid out, on the stream that fills it: dev.u32(o) / .u64(o) / .u8(o) / .ull(o) / .at<T>(o) is the array at byte
+// offset o with the element type named; dev.up(o, src, bytes) sends host memory there and dev.down(dst, o, bytes) brings it back
+// (nothing for an empty array; h2d / d2h, so the stream is the one to synchronise).
 struct DevAt {
     char* base; hipStream_t st;
     template <class T> T* at(size_t off) const { return (T*)(base + off); }
     uint32_t* u32(size_t off) const { return at<uint32_t>(off); }
     uint64_t* u64(size_t off) const { return at<uint64_t>(off); }
     uint8_t* u8(size_t off) const { return at<uint8_t>(off); }
+    unsigned long long* ull(size_t off) const { return at<unsigned long long>(off); }   // (the type of the kernels' atomic sums)
     hipError_t up(size_t off, const void* src, size_t bytes) const { return bytes ? h2d(base + off, src, bytes, st) : hipSuccess; }
+    hipError_t down(void* dst, size_t off, size_t bytes) const { return bytes ? d2h(dst, base + off, bytes, st) : hipSuccess; }
 };
 
 // ---- the alignment records of a HypoArmsReads: checked on the host, then on the device -------------------------------------------
@@ -1174,6 +1178,14 @@ uint64_t ks_slots_for(uint64_t keys) {                 // the smallest table tha
     const uint64_t s = (uint64_t)((double)keys / hypo::KSET_MAX_LOAD) + 1;
     return s < hypo::KSET_MIN_SLOTS ? hypo::KSET_MIN_SLOTS : s;
 }
+// The kernels' two counters: ks.ctr zeroed, launch(them on the device), both on their way down into ctr[].  The caller synchronises
+// (an import has one more copy to queue first) and says what ctr[0] and the overflow flag ctr[1] mean to it.
+template <class Launch>
+hipError_t ks_counted(Ctx::KSet& ks, unsigned long long ctr[2], hipStream_t st, Launch launch) {
+    hipError_t e = hipMemsetAsync(ks.ctr.p, 0, 16, st);
+    if (e == hipSuccess) e = launch((unsigned long long*)ks.ctr.p);
+    return e == hipSuccess ? hipMemcpyAsync(ctr, ks.ctr.p, 16, hipMemcpyDeviceToHost, st) : e;
+}
 // A fresh table of `slots` slots takes the keys of the present one (if any) and its place; with counts on, fresh planes beside it
 // take the count bytes (the copy bytes are zero until the set is closed, and a closed set does not grow).
 int ks_resize(Ctx::KSet& ks, uint64_t slots, hipStream_t st) {
@@ -1186,12 +1198,13 @@ int ks_resize(Ctx::KSet& ks, uint64_t slots, hipStream_t st) {
                                                                  (double)slots * ks.slot_bytes() / (1u << 30), (unsigned long long)ks.count, hipGetErrorString(e)); }
     auto drop = [&] { (void)hipFree(fresh); if (fresh_planes) (void)hipFree(fresh_planes); };
     unsigned long long ctr[2] = {0, 0};
-    if ((e = hipMemsetAsync(fresh, 0xff, slots * 8, st)) == hipSuccess && (e = hipMemsetAsync(ks.ctr.p, 0, 16, st)) == hipSuccess && fresh_planes)
-        e = hipMemsetAsync(fresh_planes, 0, ks.plane_bytes(slots), st);
-    if (e == hipSuccess && ks.table)
-        e = ks.planes ? hypo::kset_rehash_count_run(ks.table, ks.slots, ks.planes, fresh, slots, fresh_planes, (unsigned long long*)ks.ctr.p, st)
-                      : hypo::kset_rehash_run(ks.table, ks.slots, fresh, slots, (unsigned long long*)ks.ctr.p, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(ctr, ks.ctr.p, 16, hipMemcpyDeviceToHost, st);
+    if ((e = hipMemsetAsync(fresh, 0xff, slots * 8, st)) == hipSuccess)
+        e = ks_counted(ks, ctr, st, [&](unsigned long long* d_ctr) {
+            const hipError_t z = fresh_planes ? hipMemsetAsync(fresh_planes, 0, ks.plane_bytes(slots), st) : hipSuccess;
+            if (z != hipSuccess || !ks.table) return z;
+            return ks.planes ? hypo::kset_rehash_count_run(ks.table, ks.slots, ks.planes, fresh, slots, fresh_planes, d_ctr, st)
+                             : hypo::kset_rehash_run(ks.table, ks.slots, fresh, slots, d_ctr, st);
+        });
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) { drop(); return fail(HYPO_E_HIP, "k-mer set: resizing to %llu slots: %s", (unsigned long long)slots, hipGetErrorString(e)); }
     if (ctr[1] || ctr[0] != ks.count) {
@@ -1225,6 +1238,22 @@ int ks_make_room(Ctx::KSet& ks, uint64_t n_new, const char* what, hipStream_t st
     HYPO_ENTRY(); \
     Ctx::KSet& ks = g_ctx.ks; \
     if (!ks.k) return fail(HYPO_E_INVALID, "no k-mer set (hypo_gpu_kset_begin)")
+// Those that need its count bytes say so where the check stands in their order of checks.
+#define KS_NEEDS_COUNTS() if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)")
+// [lo, hi) is a range of the call's n_bytes; `what` is the noun of the message, "span" or "site"
+#define KS_CHECK_RANGE(what, s, lo, hi, n_bytes) \
+    if ((lo) > (hi) || (hi) > (n_bytes)) \
+        return fail(HYPO_E_INVALID, what " %u = [%llu, %llu) of %llu bytes", s, (unsigned long long)(lo), (unsigned long long)(hi), (unsigned long long)(n_bytes))
+
+// The three arenas of a call as a Carver laid them out, on the context's stream: sized in the order in, off, res.
+struct KsDev { DevAt in, off, res; };
+int ks_arenas(Ctx::KSet& ks, size_t in_bytes, size_t off_bytes, size_t res_bytes, KsDev& d) {
+    HIP_TRY(ks.in.alloc(in_bytes));
+    HIP_TRY(ks.off.alloc(off_bytes));
+    HIP_TRY(ks.res.alloc(res_bytes));
+    d = {{(char*)ks.in.p, g_ctx.stream}, {(char*)ks.off.p, g_ctx.stream}, {(char*)ks.res.p, g_ctx.stream}};
+    return HYPO_OK;
+}
 
 // rel[i] = off[i] - off[0], i = 0 .. n_seqs, of offsets that must not decrease
 int ks_rel_offsets(const uint64_t* off, uint32_t n_seqs, std::vector<uint64_t>& rel) {
@@ -1236,26 +1265,45 @@ int ks_rel_offsets(const uint64_t* off, uint32_t n_seqs, std::vector<uint64_t>& 
     return HYPO_OK;
 }
 
-// What the two sequence queries do alike once their arguments are checked, for the n = rel[n_seqs] > 0 bytes at `bytes`: the
-// arenas (ks.off of off_bytes, the offsets first), bytes and offsets up, zeroed sums, the caller's kernels through
-// launch(d_off, d_tot, d_mis), total / missing on their way down (the caller synchronises).
+// What the two sequence queries and the mark do alike once their arguments are checked, for the n = rel.back() > 0 bytes at
+// `bytes`: the arenas (ks.off of off_bytes, the offsets first; ks.res of n_sums pairs of sums), bytes and offsets up, zeroed sums,
+// the caller's kernels through launch(the arenas, the sums).  The caller brings down what it wants and synchronises.
 template <class Launch>
-int ks_query_seqs(Ctx::KSet& ks, const char* bytes, const std::vector<uint64_t>& rel, uint32_t n_seqs, size_t off_bytes, uint64_t* total,
-                  uint64_t* missing, Launch launch) {
-    hipStream_t st = g_ctx.stream;
-    const uint64_t n = rel[n_seqs];
-    HIP_TRY(ks.in.alloc(n));
-    HIP_TRY(ks.off.alloc(off_bytes));
-    HIP_TRY(ks.res.alloc((size_t)n_seqs * 16));
-    unsigned long long* d_tot = (unsigned long long*)ks.res.p;
-    unsigned long long* d_mis = d_tot + n_seqs;
-    HIP_TRY(h2d(ks.in.p, bytes, n, st));
-    HIP_TRY(hipMemcpyAsync(ks.off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-    HIP_TRY(hipMemsetAsync(ks.res.p, 0, (size_t)n_seqs * 16, st));
-    HIP_TRY(launch((char*)ks.off.p, d_tot, d_mis));
-    HIP_TRY(hipMemcpyAsync(total, d_tot, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(missing, d_mis, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+int ks_query_seqs(Ctx::KSet& ks, const char* bytes, const std::vector<uint64_t>& rel, size_t off_bytes, size_t n_sums, KsDev& d, Launch launch) {
+    if (const int rc = ks_arenas(ks, rel.back(), off_bytes, n_sums * 16, d)) return rc;
+    HIP_TRY(d.in.up(0, bytes, rel.back()));
+    HIP_TRY(hipMemcpyAsync(d.off.base, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, d.off.st));
+    HIP_TRY(hipMemsetAsync(d.res.base, 0, n_sums * 16, d.res.st));
+    HIP_TRY(launch(d, d.res.ull(0)));
     return HYPO_OK;
+}
+
+// What the two walk entries do alike before their kernel: the budget and the sites checked (the kernels trust what they are given),
+// the arenas (ks.res of res_bytes), the text and from | to | dlo | dhi up; `sites` names them on the device.
+int ks_walk_sites(Ctx::KSet& ks, const char* bytes, uint64_t n_bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi,
+                  uint32_t n_sites, uint32_t budget, size_t res_bytes, KsDev& d, hypo::KsetWalkSites& sites) {
+    const uint32_t k = ks.k;
+    if (budget < 1 || budget > hypo::KSET_MAX_WALK_BUDGET) return fail(HYPO_E_INVALID, "budget = %u out of range 1..%u (HYPO_KSET_MAX_WALK_BUDGET)", budget, hypo::KSET_MAX_WALK_BUDGET);
+    for (uint32_t s = 0; s < n_sites; ++s) {
+        if (n_bytes < k || from[s] > n_bytes - k || to[s] > n_bytes - k)
+            return fail(HYPO_E_INVALID, "site %u: the anchors at %llu and %llu (k = %u) do not lie inside %llu bytes", s, (unsigned long long)from[s], (unsigned long long)to[s], k,
+                        (unsigned long long)n_bytes);
+        if (dlo[s] < 1 || dlo[s] > dhi[s] || dhi[s] > hypo::KSET_MAX_WALK)
+            return fail(HYPO_E_INVALID, "site %u: 1 <= dlo <= dhi <= %u (HYPO_KSET_MAX_WALK) does not hold for %u .. %u", s, hypo::KSET_MAX_WALK, dlo[s], dhi[s]);
+    }
+    Carver co;
+    const size_t o_from = co.take((size_t)n_sites * 8), o_to = co.take((size_t)n_sites * 8), o_dlo = co.take((size_t)n_sites * 4), o_dhi = co.take((size_t)n_sites * 4);
+    if (const int rc = ks_arenas(ks, n_bytes, co.at, res_bytes, d)) return rc;
+    HIP_TRY(d.in.up(0, bytes, n_bytes));
+    HIP_TRY(d.off.up(o_from, from, (size_t)n_sites * 8)); HIP_TRY(d.off.up(o_to, to, (size_t)n_sites * 8));
+    HIP_TRY(d.off.up(o_dlo, dlo, (size_t)n_sites * 4)); HIP_TRY(d.off.up(o_dhi, dhi, (size_t)n_sites * 4));
+    sites = {d.in.u8(0), d.off.u64(o_from), d.off.u64(o_to), d.off.u32(o_dlo), d.off.u32(o_dhi), n_sites};
+    return HYPO_OK;
+}
+// Of a walk only its len bytes reach the caller: what lies beyond them in the caller's memory stays as it was.
+void ks_walk_out(uint8_t* walk, const std::vector<uint8_t>& h_walk, size_t at, uint32_t len) {
+    const size_t n = len <= hypo::KSET_MAX_WALK ? len : 0;
+    for (size_t i = 0; i < n; ++i) walk[at * hypo::KSET_MAX_WALK + i] = h_walk[at * hypo::KSET_MAX_WALK + i];
 }
 
 // A run of n_win windows as pieces of at most KSET_SPAN_PIECE: f(first window, the piece's bytes), each piece with the k - 1 bytes
@@ -1311,10 +1359,11 @@ int hypo_gpu_kset_add(const char* bytes, uint64_t n) {
         const uint64_t m = n - at < kKmerPiece ? n - at : kKmerPiece;
         unsigned long long ctr[2] = {0, 0};
         HIP_TRY(h2d(ks.in.p, bytes + at, m, st));
-        HIP_TRY(hipMemsetAsync(ks.ctr.p, 0, 16, st));
-        HIP_TRY(ks.planes ? hypo::kset_insert_count_run((const uint8_t*)ks.in.p, m, ks.k, ks.table, ks.slots, (unsigned long long*)ks.ctr.p, ks.planes, st)
-                          : hypo::kset_insert_run((const uint8_t*)ks.in.p, m, ks.k, ks.table, ks.slots, (unsigned long long*)ks.ctr.p, st));
-        HIP_TRY(hipMemcpyAsync(ctr, ks.ctr.p, 16, hipMemcpyDeviceToHost, st));
+        const hipError_t kset_insert = ks_counted(ks, ctr, st, [&](unsigned long long* d_ctr) {
+            return ks.planes ? hypo::kset_insert_count_run((const uint8_t*)ks.in.p, m, ks.k, ks.table, ks.slots, d_ctr, ks.planes, st)
+                             : hypo::kset_insert_run((const uint8_t*)ks.in.p, m, ks.k, ks.table, ks.slots, d_ctr, st);
+        });
+        HIP_TRY(kset_insert);
         HIP_TRY(hipStreamSynchronize(st));                   // (the caller may refill `bytes` when this returns)
         ks.count += ctr[0];
         if (ctr[1]) return fail(HYPO_E_HIP, "k-mer set: internal error: a table of %llu slots with %llu keys had no room", (unsigned long long)ks.slots, (unsigned long long)ks.count);
@@ -1344,10 +1393,12 @@ int hypo_gpu_kset_query(const char* bytes, const uint64_t* off, uint32_t n_seqs,
     if (!rel[n_seqs]) return HYPO_OK;
     if (!bytes) return fail(HYPO_E_INVALID, "NULL buffer");
     hipStream_t st = g_ctx.stream;
-    const int rc = ks_query_seqs(ks, bytes + off[0], rel, n_seqs, rel.size() * 8, total, missing, [&](char* d_off, unsigned long long* d_tot, unsigned long long* d_mis) {
-        return hypo::kset_query_run((const uint8_t*)ks.in.p, (const uint64_t*)d_off, n_seqs, rel[n_seqs], ks.k, ks.table, ks.slots, d_tot, d_mis, ks.planes, ks.min_count, st);
-    });
-    if (rc != HYPO_OK) return rc;
+    KsDev d;
+    if (const int rc = ks_query_seqs(ks, bytes + off[0], rel, rel.size() * 8, n_seqs, d, [&](const KsDev& a, unsigned long long* sums) {
+            return hypo::kset_query_run(ks.view(), a.in.u8(0), a.off.u64(0), n_seqs, rel[n_seqs], sums, sums + n_seqs, st);
+        })) return rc;
+    HIP_TRY(hipMemcpyAsync(total, d.res.u64(0), (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(missing, d.res.u64(0) + n_seqs, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     return HYPO_OK;
 }
@@ -1369,20 +1420,21 @@ int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n
     // `in`: the bytes.  `off`: the offsets, the want bytes, then what indexes the bytes: the two flag words per 32 positions, the
     // per-workgroup sums and their prefixes.  `res`: total / missing first.
     const uint32_t blocks = hypo::kset_track_blocks(n);
-    const size_t n_words = (size_t)blocks * 256;
+    const size_t n_words = (size_t)blocks * hypo::KS_THREADS;
     Carver co;
     co.take(rel.size() * 8);
     const size_t at_want = co.take(n_seqs), at_miss = co.take(n_words * 4), at_begin = co.take(n_words * 4), at_sums = co.take((size_t)blocks * 8),
                  at_pre = co.take(((size_t)blocks + 1) * 24);
-    const int rc = ks_query_seqs(ks, bytes + off[0], rel, n_seqs, co.at, total, missing, [&](char* d, unsigned long long* d_tot, unsigned long long* d_mis) {
-        if (want) { const hipError_t e = hipMemcpyAsync(d + at_want, want, n_seqs, hipMemcpyHostToDevice, st); if (e != hipSuccess) return e; }
-        return hypo::kset_track_count_run((const uint8_t*)ks.in.p, (const uint64_t*)d, n_seqs, n, ks.k, ks.table, ks.slots, d_tot, d_mis,
-                                          want ? (const uint8_t*)(d + at_want) : nullptr, (uint32_t*)(d + at_miss), (uint32_t*)(d + at_begin),
-                                          (uint64_t*)(d + at_sums), (uint64_t*)(d + at_pre), ks.planes, ks.min_count, st);
-    });
-    if (rc != HYPO_OK) return rc;
-    char* const d_off = (char*)ks.off.p;
-    const uint64_t* d_pre = (const uint64_t*)(d_off + at_pre);
+    KsDev d;
+    if (const int rc = ks_query_seqs(ks, bytes + off[0], rel, co.at, n_seqs, d, [&](const KsDev& a, unsigned long long* sums) {
+            const DevAt& o = a.off;
+            if (want) { const hipError_t e = hipMemcpyAsync(o.u8(at_want), want, n_seqs, hipMemcpyHostToDevice, st); if (e != hipSuccess) return e; }
+            return hypo::kset_track_count_run(ks.view(), a.in.u8(0), o.u64(0), n_seqs, n, sums, sums + n_seqs, want ? o.u8(at_want) : nullptr, o.u32(at_miss),
+                                              o.u32(at_begin), o.u64(at_sums), o.u64(at_pre), st);
+        })) return rc;
+    HIP_TRY(hipMemcpyAsync(total, d.res.u64(0), (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(missing, d.res.u64(0) + n_seqs, (size_t)n_seqs * 8, hipMemcpyDeviceToHost, st));
+    const uint64_t* d_pre = d.off.u64(at_pre);
     uint64_t sums[3] = {0, 0, 0};                               // starts, ends, missing windows of the wanted sequences
     HIP_TRY(hipMemcpyAsync(sums, d_pre + 3 * (size_t)blocks, 24, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -1394,16 +1446,12 @@ int hypo_gpu_kset_query_track(const char* bytes, const uint64_t* off, uint32_t n
     cv.take(rel.size() * 8);
     const size_t o_start = cv.take((size_t)n_iv * 8), o_end = cv.take((size_t)n_iv * 8), o_lo = cv.take((size_t)n_iv * 8), o_hi = cv.take((size_t)n_iv * 8);
     HIP_TRY(ks.res.alloc(cv.at));
-    char* const d_res = (char*)ks.res.p;
-    HIP_TRY(hypo::kset_track_emit_run((const uint64_t*)d_off, n_seqs, n, ks.k, (const uint32_t*)(d_off + at_miss), (const uint32_t*)(d_off + at_begin), d_pre, n_iv,
-                                      (uint64_t*)d_res, (uint64_t*)(d_res + o_start), (uint64_t*)(d_res + o_end), (uint64_t*)(d_res + o_lo), (uint64_t*)(d_res + o_hi), st));
-    HIP_TRY(hipMemcpyAsync(iv_off, d_res, rel.size() * 8, hipMemcpyDeviceToHost, st));
+    const DevAt r{(char*)ks.res.p, st};
+    HIP_TRY(hypo::kset_track_emit_run(d.off.u64(0), n_seqs, n, ks.k, d.off.u32(at_miss), d.off.u32(at_begin), d_pre, n_iv, r.u64(0), r.u64(o_start), r.u64(o_end),
+                                      r.u64(o_lo), r.u64(o_hi), st));
+    HIP_TRY(hipMemcpyAsync(iv_off, r.base, rel.size() * 8, hipMemcpyDeviceToHost, st));
     const bool fits = n_iv <= iv_cap;
-    if (fits && n_iv) {
-        HIP_TRY(d2h(iv_start, d_res + o_start, (size_t)n_iv * 8, st));
-        HIP_TRY(d2h(iv_end, d_res + o_end, (size_t)n_iv * 8, st));
-        HIP_TRY(d2h(iv_missing, d_res + o_hi, (size_t)n_iv * 8, st));
-    }
+    if (fits) { HIP_TRY(r.down(iv_start, o_start, (size_t)n_iv * 8)); HIP_TRY(r.down(iv_end, o_end, (size_t)n_iv * 8)); HIP_TRY(r.down(iv_missing, o_hi, (size_t)n_iv * 8)); }
     HIP_TRY(hipStreamSynchronize(st));
     if (!fits) return fail(HYPO_E_WORKSPACE, "%llu intervals, room for %llu: call again with arrays of that size", (unsigned long long)n_iv, (unsigned long long)iv_cap);
     return HYPO_OK;
@@ -1418,7 +1466,7 @@ int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_
     auto windows = [&](uint32_t s) { const uint64_t len = hi[s] - lo[s]; return len >= k ? len - k + 1 : 0; };
     uint64_t n_items = 0;
     for (uint32_t s = 0; s < n_spans; ++s) {
-        if (lo[s] > hi[s] || hi[s] > n_bytes) return fail(HYPO_E_INVALID, "span %u = [%llu, %llu) of %llu bytes", s, (unsigned long long)lo[s], (unsigned long long)hi[s], (unsigned long long)n_bytes);
+        KS_CHECK_RANGE("span", s, lo[s], hi[s], n_bytes);
         n_items += ks_n_pieces(windows(s));
     }
     for (uint32_t s = 0; s < n_spans; ++s) total[s] = missing[s] = 0;
@@ -1430,18 +1478,16 @@ int hypo_gpu_kset_query_spans(const char* bytes, uint64_t n_bytes, const uint64_
     size_t it = 0;
     for (uint32_t s = 0; s < n_spans; ++s)
         ks_pieces(windows(s), k, [&](uint64_t w, uint32_t bytes_) { item_lo[it] = lo[s] + w; item_len[it++] = bytes_; });
+    // ks.in: bytes.  ks.off: item_lo, then item_len at the next multiple of 256 bytes (the arena ends with it, unpadded).  ks.res: item pairs.
     hipStream_t st = g_ctx.stream;
-    const size_t lo_bytes = Carver::pad((size_t)n_items * 8);
-    HIP_TRY(ks.in.alloc(n_bytes));
-    HIP_TRY(ks.off.alloc(lo_bytes + (size_t)n_items * 4));
-    HIP_TRY(ks.res.alloc((size_t)n_items * 8));
-    HIP_TRY(h2d(ks.in.p, bytes, n_bytes, st));
-    HIP_TRY(h2d(ks.off.p, item_lo.data(), (size_t)n_items * 8, st));
-    HIP_TRY(h2d((char*)ks.off.p + lo_bytes, item_len.data(), (size_t)n_items * 4, st));
-    HIP_TRY(hypo::kset_spans_run((const uint8_t*)ks.in.p, (const uint64_t*)ks.off.p, (const uint32_t*)((const char*)ks.off.p + lo_bytes), (uint32_t)n_items, k,
-                                 ks.table, ks.slots, (uint2*)ks.res.p, ks_group(), ks.planes, ks.min_count, st));
+    const size_t o_len = Carver::pad((size_t)n_items * 8);
+    KsDev d;
+    if (const int rc = ks_arenas(ks, n_bytes, o_len + (size_t)n_items * 4, (size_t)n_items * 8, d)) return rc;
+    HIP_TRY(d.in.up(0, bytes, n_bytes));
+    HIP_TRY(d.off.up(0, item_lo.data(), (size_t)n_items * 8)); HIP_TRY(d.off.up(o_len, item_len.data(), (size_t)n_items * 4));
+    HIP_TRY(hypo::kset_spans_run(ks.view(), d.in.u8(0), d.off.u64(0), d.off.u32(o_len), (uint32_t)n_items, d.res.at<uint2>(0), ks_group(), st));
     std::vector<uint2> res((size_t)n_items);
-    HIP_TRY(d2h(res.data(), ks.res.p, (size_t)n_items * 8, st));
+    HIP_TRY(d.res.down(res.data(), 0, (size_t)n_items * 8));
     HIP_TRY(hipStreamSynchronize(st));
     it = 0;
     for (uint32_t s = 0; s < n_spans; ++s)
@@ -1463,7 +1509,7 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
         if (edit_off[s + 1] < edit_off[s]) return fail(HYPO_E_INVALID, "edit_off[] must not decrease (entry %u)", s + 1);
         const uint32_t n = edit_off[s + 1] - edit_off[s];
         if (n > hypo::KSET_MAX_EDITS) return fail(HYPO_E_INVALID, "site %u has %u edits, at most %u (HYPO_KSET_MAX_EDITS)", s, n, hypo::KSET_MAX_EDITS);
-        if (lo[s] > hi[s] || hi[s] > n_bytes) return fail(HYPO_E_INVALID, "site %u = [%llu, %llu) of %llu bytes", s, (unsigned long long)lo[s], (unsigned long long)hi[s], (unsigned long long)n_bytes);
+        KS_CHECK_RANGE("site", s, lo[s], hi[s], n_bytes);
         if (n && (!eb || !ee || !ao || !al)) return fail(HYPO_E_INVALID, "NULL buffer");
         uint64_t at = lo[s], longest = hi[s] - lo[s];
         for (uint32_t e = edit_off[s]; e < edit_off[s + 1]; ++e) {
@@ -1513,34 +1559,25 @@ int hypo_gpu_kset_query_variants(const char* bytes, uint64_t n_bytes, const char
                  o_sitem = co.take(((size_t)n_sites + 1) * 4), o_voff = co.take(((size_t)n_sites + 1) * 4);
     const size_t r_item = cr.take((size_t)n_items * 8), r_bt = cr.take((size_t)n_sites * 8), r_bm = cr.take((size_t)n_sites * 8),
                  r_vt = cr.take(want_vars ? (size_t)n_vars * 8 : 0), r_vm = cr.take(want_vars ? (size_t)n_vars * 8 : 0), r_mask = cr.take((size_t)n_sites * 4);
-    HIP_TRY(ks.in.alloc(alt_at + (size_t)n_alt_bytes));
-    HIP_TRY(ks.off.alloc(co.at));
-    HIP_TRY(ks.res.alloc(cr.at));
-    char* d_in = (char*)ks.in.p; char* d_off = (char*)ks.off.p; char* d_res = (char*)ks.res.p;
-    if (n_bytes) HIP_TRY(h2d(d_in, bytes, n_bytes, st));
-    if (n_alt_bytes) HIP_TRY(h2d(d_in + alt_at, alts, n_alt_bytes, st));
-    HIP_TRY(h2d(d_off + o_lo, lo, (size_t)n_sites * 8, st));
-    if (n_edits) {
-        HIP_TRY(h2d(d_off + o_eb, eb + e_first, (size_t)n_edits * 8, st));
-        HIP_TRY(h2d(d_off + o_ee, ee + e_first, (size_t)n_edits * 8, st));
-        HIP_TRY(h2d(d_off + o_ao, ao + e_first, (size_t)n_edits * 8, st));
-        HIP_TRY(h2d(d_off + o_al, al + e_first, (size_t)n_edits * 4, st));
+    KsDev d;
+    if (const int rc = ks_arenas(ks, alt_at + (size_t)n_alt_bytes, co.at, cr.at, d)) return rc;
+    HIP_TRY(d.in.up(0, bytes, n_bytes)); HIP_TRY(d.in.up(alt_at, alts, n_alt_bytes));
+    HIP_TRY(d.off.up(o_lo, lo, (size_t)n_sites * 8));
+    if (n_edits) {                                              // (with no edit the four arrays may be NULL)
+        HIP_TRY(d.off.up(o_eb, eb + e_first, (size_t)n_edits * 8)); HIP_TRY(d.off.up(o_ee, ee + e_first, (size_t)n_edits * 8));
+        HIP_TRY(d.off.up(o_ao, ao + e_first, (size_t)n_edits * 8)); HIP_TRY(d.off.up(o_al, al + e_first, (size_t)n_edits * 4));
     }
-    HIP_TRY(h2d(d_off + o_items, items.data(), (size_t)n_items * 16, st));
-    HIP_TRY(h2d(d_off + o_eoff, rel_off.data(), rel_off.size() * 4, st));
-    HIP_TRY(h2d(d_off + o_sitem, site_item.data(), site_item.size() * 4, st));
-    HIP_TRY(h2d(d_off + o_voff, var_off.data(), var_off.size() * 4, st));
-    HIP_TRY(hypo::kset_variants_run((const uint8_t*)d_in, (const uint8_t*)(d_in + alt_at), (const uint64_t*)(d_off + o_lo), (const uint32_t*)(d_off + o_eoff),
-                                    (const uint64_t*)(d_off + o_eb), (const uint64_t*)(d_off + o_ee), (const uint64_t*)(d_off + o_ao), (const uint32_t*)(d_off + o_al),
-                                    (const uint4*)(d_off + o_items), (uint32_t)n_items, (const uint32_t*)(d_off + o_sitem), (const uint32_t*)(d_off + o_voff), n_sites, k,
-                                    ks.table, ks.slots, (uint2*)(d_res + r_item), (uint32_t*)(d_res + r_mask), (unsigned long long*)(d_res + r_bt),
-                                    (unsigned long long*)(d_res + r_bm), want_vars ? (unsigned long long*)(d_res + r_vt) : nullptr,
-                                    want_vars ? (unsigned long long*)(d_res + r_vm) : nullptr, ks_group(), ks.planes, ks.min_count, st));
-    HIP_TRY(d2h(best_mask, d_res + r_mask, (size_t)n_sites * 4, st));
-    HIP_TRY(d2h(best_total, d_res + r_bt, (size_t)n_sites * 8, st));
-    HIP_TRY(d2h(best_missing, d_res + r_bm, (size_t)n_sites * 8, st));
-    if (var_total) HIP_TRY(d2h(var_total, d_res + r_vt, (size_t)n_vars * 8, st));
-    if (var_missing) HIP_TRY(d2h(var_missing, d_res + r_vm, (size_t)n_vars * 8, st));
+    HIP_TRY(d.off.up(o_items, items.data(), (size_t)n_items * 16)); HIP_TRY(d.off.up(o_eoff, rel_off.data(), rel_off.size() * 4));
+    HIP_TRY(d.off.up(o_sitem, site_item.data(), site_item.size() * 4)); HIP_TRY(d.off.up(o_voff, var_off.data(), var_off.size() * 4));
+    const hypo::KsetVariantsIn in{d.in.u8(0), d.in.u8(alt_at), d.off.u64(o_lo), d.off.u32(o_eoff), d.off.u64(o_eb), d.off.u64(o_ee), d.off.u64(o_ao), d.off.u32(o_al),
+                                  d.off.at<uint4>(o_items), (uint32_t)n_items, d.off.u32(o_sitem), d.off.u32(o_voff), n_sites};
+    const hypo::KsetVariantsOut out{d.res.at<uint2>(r_item), d.res.u32(r_mask), d.res.ull(r_bt), d.res.ull(r_bm), want_vars ? d.res.ull(r_vt) : nullptr,
+                                    want_vars ? d.res.ull(r_vm) : nullptr};
+    HIP_TRY(hypo::kset_variants_run(ks.view(), in, out, ks_group(), st));
+    HIP_TRY(d.res.down(best_mask, r_mask, (size_t)n_sites * 4));
+    HIP_TRY(d.res.down(best_total, r_bt, (size_t)n_sites * 8)); HIP_TRY(d.res.down(best_missing, r_bm, (size_t)n_sites * 8));
+    if (var_total) HIP_TRY(d.res.down(var_total, r_vt, (size_t)n_vars * 8));
+    if (var_missing) HIP_TRY(d.res.down(var_missing, r_vm, (size_t)n_vars * 8));
     HIP_TRY(hipStreamSynchronize(st));
     return HYPO_OK;
 }
@@ -1578,32 +1615,20 @@ int hypo_gpu_kset_query_fixes(const char* bytes, uint64_t n_bytes, const uint64_
     const size_t r_item = cr.take((size_t)n_items * 8), r_nt = cr.take((size_t)n_sites * 8), r_nm = cr.take((size_t)n_sites * 8), r_bt = cr.take((size_t)n_sites * 8),
                  r_bm = cr.take((size_t)n_sites * 8), r_ct = cr.take(want_cands ? (size_t)n_items * 8 : 0), r_cm = cr.take(want_cands ? (size_t)n_items * 8 : 0),
                  r_bc = cr.take((size_t)n_sites * 4), r_z = cr.take((size_t)n_sites * 4);
-    HIP_TRY(ks.in.alloc(n_bytes));
-    HIP_TRY(ks.off.alloc(co.at));
-    HIP_TRY(ks.res.alloc(cr.at));
-    char* d_off = (char*)ks.off.p; char* d_res = (char*)ks.res.p;
-    HIP_TRY(h2d(ks.in.p, bytes, n_bytes, st));
-    HIP_TRY(h2d(d_off + o_lo, lo, (size_t)n_sites * 8, st));
-    HIP_TRY(h2d(d_off + o_len, len.data(), (size_t)n_sites * 4, st));
-    HIP_TRY(h2d(d_off + o_c0, rc0.data(), (size_t)n_sites * 4, st));
-    HIP_TRY(h2d(d_off + o_w, w.data(), (size_t)n_sites * 4, st));
-    HIP_TRY(h2d(d_off + o_ioff, item_off.data(), item_off.size() * 4, st));
-    HIP_TRY(hypo::kset_fixes_run((const uint8_t*)ks.in.p, (const uint64_t*)(d_off + o_lo), (const uint32_t*)(d_off + o_len), (const uint32_t*)(d_off + o_c0),
-                                 (const uint32_t*)(d_off + o_w), (const uint32_t*)(d_off + o_ioff), n_sites, (uint32_t)n_items, ks.k, ks.table, ks.slots,
-                                 (uint2*)(d_res + r_item), (unsigned long long*)(d_res + r_nt), (unsigned long long*)(d_res + r_nm), (uint32_t*)(d_res + r_bc),
-                                 (unsigned long long*)(d_res + r_bt), (unsigned long long*)(d_res + r_bm), (uint32_t*)(d_res + r_z),
-                                 want_cands ? (unsigned long long*)(d_res + r_ct) : nullptr, want_cands ? (unsigned long long*)(d_res + r_cm) : nullptr, ks_group(),
-                                 ks.planes, ks.min_count, st));
-    HIP_TRY(d2h(none_total, d_res + r_nt, (size_t)n_sites * 8, st));
-    HIP_TRY(d2h(none_missing, d_res + r_nm, (size_t)n_sites * 8, st));
-    HIP_TRY(d2h(best_cand, d_res + r_bc, (size_t)n_sites * 4, st));
-    HIP_TRY(d2h(best_total, d_res + r_bt, (size_t)n_sites * 8, st));
-    HIP_TRY(d2h(best_missing, d_res + r_bm, (size_t)n_sites * 8, st));
-    HIP_TRY(d2h(zeros, d_res + r_z, (size_t)n_sites * 4, st));
-    if (want_cands) {
-        HIP_TRY(d2h(cand_total, d_res + r_ct, (size_t)n_items * 8, st));
-        HIP_TRY(d2h(cand_missing, d_res + r_cm, (size_t)n_items * 8, st));
-    }
+    KsDev d;
+    if (const int rc = ks_arenas(ks, n_bytes, co.at, cr.at, d)) return rc;
+    HIP_TRY(d.in.up(0, bytes, n_bytes)); HIP_TRY(d.off.up(o_lo, lo, (size_t)n_sites * 8));
+    HIP_TRY(d.off.up(o_len, len.data(), (size_t)n_sites * 4)); HIP_TRY(d.off.up(o_c0, rc0.data(), (size_t)n_sites * 4));
+    HIP_TRY(d.off.up(o_w, w.data(), (size_t)n_sites * 4)); HIP_TRY(d.off.up(o_ioff, item_off.data(), item_off.size() * 4));
+    const hypo::KsetFixesIn in{d.in.u8(0), d.off.u64(o_lo), d.off.u32(o_len), d.off.u32(o_c0), d.off.u32(o_w), d.off.u32(o_ioff), n_sites, (uint32_t)n_items};
+    const hypo::KsetFixesOut out{d.res.at<uint2>(r_item), d.res.ull(r_nt), d.res.ull(r_nm), d.res.u32(r_bc), d.res.ull(r_bt), d.res.ull(r_bm), d.res.u32(r_z),
+                                 want_cands ? d.res.ull(r_ct) : nullptr, want_cands ? d.res.ull(r_cm) : nullptr};
+    HIP_TRY(hypo::kset_fixes_run(ks.view(), in, out, ks_group(), st));
+    HIP_TRY(d.res.down(none_total, r_nt, (size_t)n_sites * 8)); HIP_TRY(d.res.down(none_missing, r_nm, (size_t)n_sites * 8));
+    HIP_TRY(d.res.down(best_cand, r_bc, (size_t)n_sites * 4));
+    HIP_TRY(d.res.down(best_total, r_bt, (size_t)n_sites * 8)); HIP_TRY(d.res.down(best_missing, r_bm, (size_t)n_sites * 8));
+    HIP_TRY(d.res.down(zeros, r_z, (size_t)n_sites * 4));
+    if (want_cands) { HIP_TRY(d.res.down(cand_total, r_ct, (size_t)n_items * 8)); HIP_TRY(d.res.down(cand_missing, r_cm, (size_t)n_items * 8)); }
     HIP_TRY(hipStreamSynchronize(st));
     return HYPO_OK;
 }
@@ -1614,46 +1639,24 @@ int hypo_gpu_kset_query_walks(const char* bytes, uint64_t n_bytes, const uint64_
     if (!n_sites) return HYPO_OK;
     if (!bytes || !from || !to || !dlo || !dhi || !status || !steps || !len || !walk) return fail(HYPO_E_INVALID, "NULL buffer");
     static_assert(hypo::KSET_MAX_WALK == HYPO_KSET_MAX_WALK && hypo::KSET_MAX_WALK_BUDGET == HYPO_KSET_MAX_WALK_BUDGET, "the header's limits");
-    // everything is checked before a buffer is touched: the kernel trusts what it is given
-    const uint32_t k = ks.k;
-    if (budget < 1 || budget > hypo::KSET_MAX_WALK_BUDGET) return fail(HYPO_E_INVALID, "budget = %u out of range 1..%u (HYPO_KSET_MAX_WALK_BUDGET)", budget, hypo::KSET_MAX_WALK_BUDGET);
-    for (uint32_t s = 0; s < n_sites; ++s) {
-        if (n_bytes < k || from[s] > n_bytes - k || to[s] > n_bytes - k)
-            return fail(HYPO_E_INVALID, "site %u: the anchors at %llu and %llu (k = %u) do not lie inside %llu bytes", s, (unsigned long long)from[s], (unsigned long long)to[s], k,
-                        (unsigned long long)n_bytes);
-        if (dlo[s] < 1 || dlo[s] > dhi[s] || dhi[s] > hypo::KSET_MAX_WALK)
-            return fail(HYPO_E_INVALID, "site %u: 1 <= dlo <= dhi <= %u (HYPO_KSET_MAX_WALK) does not hold for %u .. %u", s, hypo::KSET_MAX_WALK, dlo[s], dhi[s]);
-    }
     hipStream_t st = g_ctx.stream;
     // ks.in: bytes.  ks.off: from | to | dlo | dhi.  ks.res: status | steps | len | walk.  Every section starts at a multiple of 256 bytes.
-    Carver co, cr;
-    const size_t o_from = co.take((size_t)n_sites * 8), o_to = co.take((size_t)n_sites * 8), o_dlo = co.take((size_t)n_sites * 4), o_dhi = co.take((size_t)n_sites * 4);
+    Carver cr;
     const size_t r_st = cr.take((size_t)n_sites * 4), r_steps = cr.take((size_t)n_sites * 4), r_len = cr.take((size_t)n_sites * 4),
                  r_walk = cr.take((size_t)n_sites * hypo::KSET_MAX_WALK);
-    HIP_TRY(ks.in.alloc(n_bytes));
-    HIP_TRY(ks.off.alloc(co.at));
-    HIP_TRY(ks.res.alloc(cr.at));
-    char* d_off = (char*)ks.off.p; char* d_res = (char*)ks.res.p;
-    HIP_TRY(h2d(ks.in.p, bytes, n_bytes, st));
-    HIP_TRY(h2d(d_off + o_from, from, (size_t)n_sites * 8, st));
-    HIP_TRY(h2d(d_off + o_to, to, (size_t)n_sites * 8, st));
-    HIP_TRY(h2d(d_off + o_dlo, dlo, (size_t)n_sites * 4, st));
-    HIP_TRY(h2d(d_off + o_dhi, dhi, (size_t)n_sites * 4, st));
-    HIP_TRY(hypo::kset_walks_run((const uint8_t*)ks.in.p, (const uint64_t*)(d_off + o_from), (const uint64_t*)(d_off + o_to), (const uint32_t*)(d_off + o_dlo),
-                                 (const uint32_t*)(d_off + o_dhi), n_sites, budget, k, ks.table, ks.slots, (uint32_t*)(d_res + r_st), (uint32_t*)(d_res + r_steps),
-                                 (uint32_t*)(d_res + r_len), (uint8_t*)(d_res + r_walk), ks.planes, ks.min_count, st));
+    KsDev d;
+    hypo::KsetWalkSites sites;
+    if (const int rc = ks_walk_sites(ks, bytes, n_bytes, from, to, dlo, dhi, n_sites, budget, cr.at, d, sites)) return rc;
+    HIP_TRY(hypo::kset_walks_run(ks.view(), sites, budget, d.res.u32(r_st), d.res.u32(r_steps), d.res.u32(r_len), d.res.u8(r_walk), st));
     // through host buffers of the call's own: of a walk only its len bytes reach the caller, what lies beyond them stays as it was
     std::vector<uint32_t> h_st(n_sites), h_steps(n_sites), h_len(n_sites);
     std::vector<uint8_t> h_walk((size_t)n_sites * hypo::KSET_MAX_WALK);
-    HIP_TRY(d2h(h_st.data(), d_res + r_st, (size_t)n_sites * 4, st));
-    HIP_TRY(d2h(h_steps.data(), d_res + r_steps, (size_t)n_sites * 4, st));
-    HIP_TRY(d2h(h_len.data(), d_res + r_len, (size_t)n_sites * 4, st));
-    HIP_TRY(d2h(h_walk.data(), d_res + r_walk, h_walk.size(), st));
+    HIP_TRY(d.res.down(h_st.data(), r_st, (size_t)n_sites * 4)); HIP_TRY(d.res.down(h_steps.data(), r_steps, (size_t)n_sites * 4));
+    HIP_TRY(d.res.down(h_len.data(), r_len, (size_t)n_sites * 4)); HIP_TRY(d.res.down(h_walk.data(), r_walk, h_walk.size()));
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t s = 0; s < n_sites; ++s) {
         status[s] = h_st[s]; steps[s] = h_steps[s]; len[s] = h_len[s];
-        const uint32_t n = h_len[s] <= hypo::KSET_MAX_WALK ? h_len[s] : 0;
-        for (uint32_t i = 0; i < n; ++i) walk[(size_t)s * hypo::KSET_MAX_WALK + i] = h_walk[(size_t)s * hypo::KSET_MAX_WALK + i];
+        ks_walk_out(walk, h_walk, s, h_len[s]);
     }
     return HYPO_OK;
 }
@@ -1665,47 +1668,24 @@ int hypo_gpu_kset_query_walk_sets(const char* bytes, uint64_t n_bytes, const uin
     if (!n_sites) return HYPO_OK;
     if (!bytes || !from || !to || !dlo || !dhi || !status || !steps || !n_walks || !len || !low || !walk) return fail(HYPO_E_INVALID, "NULL buffer");
     static_assert(hypo::KSET_WALK_SETS == HYPO_KSET_MAX_WALKS, "the header's limits");
-    if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)");
-    // everything is checked before a buffer is touched: the kernel trusts what it is given
-    const uint32_t k = ks.k;
+    KS_NEEDS_COUNTS();
     constexpr size_t W = hypo::KSET_WALK_SETS, MW = hypo::KSET_MAX_WALK;
-    if (budget < 1 || budget > hypo::KSET_MAX_WALK_BUDGET) return fail(HYPO_E_INVALID, "budget = %u out of range 1..%u (HYPO_KSET_MAX_WALK_BUDGET)", budget, hypo::KSET_MAX_WALK_BUDGET);
-    for (uint32_t s = 0; s < n_sites; ++s) {
-        if (n_bytes < k || from[s] > n_bytes - k || to[s] > n_bytes - k)
-            return fail(HYPO_E_INVALID, "site %u: the anchors at %llu and %llu (k = %u) do not lie inside %llu bytes", s, (unsigned long long)from[s], (unsigned long long)to[s], k,
-                        (unsigned long long)n_bytes);
-        if (dlo[s] < 1 || dlo[s] > dhi[s] || dhi[s] > hypo::KSET_MAX_WALK)
-            return fail(HYPO_E_INVALID, "site %u: 1 <= dlo <= dhi <= %u (HYPO_KSET_MAX_WALK) does not hold for %u .. %u", s, hypo::KSET_MAX_WALK, dlo[s], dhi[s]);
-    }
     hipStream_t st = g_ctx.stream;
     // ks.in: bytes.  ks.off: from | to | dlo | dhi.  ks.res: status | steps | n_walks | len | low | walk.  Every section starts at a multiple of 256 bytes.
-    Carver co, cr;
-    const size_t o_from = co.take((size_t)n_sites * 8), o_to = co.take((size_t)n_sites * 8), o_dlo = co.take((size_t)n_sites * 4), o_dhi = co.take((size_t)n_sites * 4);
+    Carver cr;
     const size_t r_st = cr.take((size_t)n_sites * 4), r_steps = cr.take((size_t)n_sites * 4), r_nw = cr.take((size_t)n_sites * 4), r_len = cr.take((size_t)n_sites * W * 4),
                  r_low = cr.take((size_t)n_sites * W * 4), r_walk = cr.take((size_t)n_sites * W * MW);
-    HIP_TRY(ks.in.alloc(n_bytes));
-    HIP_TRY(ks.off.alloc(co.at));
-    HIP_TRY(ks.res.alloc(cr.at));
-    char* d_off = (char*)ks.off.p; char* d_res = (char*)ks.res.p;
-    HIP_TRY(h2d(ks.in.p, bytes, n_bytes, st));
-    HIP_TRY(h2d(d_off + o_from, from, (size_t)n_sites * 8, st));
-    HIP_TRY(h2d(d_off + o_to, to, (size_t)n_sites * 8, st));
-    HIP_TRY(h2d(d_off + o_dlo, dlo, (size_t)n_sites * 4, st));
-    HIP_TRY(h2d(d_off + o_dhi, dhi, (size_t)n_sites * 4, st));
-    HIP_TRY(hypo::kset_walk_sets_run((const uint8_t*)ks.in.p, (const uint64_t*)(d_off + o_from), (const uint64_t*)(d_off + o_to), (const uint32_t*)(d_off + o_dlo),
-                                     (const uint32_t*)(d_off + o_dhi), n_sites, budget, k, ks.table, ks.slots, ks.planes, ks.min_count, (uint32_t*)(d_res + r_st),
-                                     (uint32_t*)(d_res + r_steps), (uint32_t*)(d_res + r_nw), (uint32_t*)(d_res + r_len), (uint32_t*)(d_res + r_low),
-                                     (uint8_t*)(d_res + r_walk), st));
+    KsDev d;
+    hypo::KsetWalkSites sites;
+    if (const int rc = ks_walk_sites(ks, bytes, n_bytes, from, to, dlo, dhi, n_sites, budget, cr.at, d, sites)) return rc;
+    HIP_TRY(hypo::kset_walk_sets_run(ks.view(), sites, budget, d.res.u32(r_st), d.res.u32(r_steps), d.res.u32(r_nw), d.res.u32(r_len), d.res.u32(r_low), d.res.u8(r_walk), st));
     // through host buffers of the call's own: only the slots below n_walks and of a walk only its len bytes reach the caller, what lies
     // beyond them stays as it was (the arena is not cleared: a slot the search did not fill holds an earlier call's bytes)
     std::vector<uint32_t> h_st(n_sites), h_steps(n_sites), h_nw(n_sites), h_len(n_sites * W), h_low(n_sites * W);
     std::vector<uint8_t> h_walk((size_t)n_sites * W * MW);
-    HIP_TRY(d2h(h_st.data(), d_res + r_st, (size_t)n_sites * 4, st));
-    HIP_TRY(d2h(h_steps.data(), d_res + r_steps, (size_t)n_sites * 4, st));
-    HIP_TRY(d2h(h_nw.data(), d_res + r_nw, (size_t)n_sites * 4, st));
-    HIP_TRY(d2h(h_len.data(), d_res + r_len, h_len.size() * 4, st));
-    HIP_TRY(d2h(h_low.data(), d_res + r_low, h_low.size() * 4, st));
-    HIP_TRY(d2h(h_walk.data(), d_res + r_walk, h_walk.size(), st));
+    HIP_TRY(d.res.down(h_st.data(), r_st, (size_t)n_sites * 4)); HIP_TRY(d.res.down(h_steps.data(), r_steps, (size_t)n_sites * 4));
+    HIP_TRY(d.res.down(h_nw.data(), r_nw, (size_t)n_sites * 4)); HIP_TRY(d.res.down(h_len.data(), r_len, h_len.size() * 4));
+    HIP_TRY(d.res.down(h_low.data(), r_low, h_low.size() * 4)); HIP_TRY(d.res.down(h_walk.data(), r_walk, h_walk.size()));
     HIP_TRY(hipStreamSynchronize(st));
     for (uint32_t s = 0; s < n_sites; ++s) {
         status[s] = h_st[s]; steps[s] = h_steps[s]; n_walks[s] = h_nw[s];
@@ -1713,8 +1693,7 @@ int hypo_gpu_kset_query_walk_sets(const char* bytes, uint64_t n_bytes, const uin
         for (size_t w = 0; w < nw; ++w) {
             const size_t at = (size_t)s * W + w;
             len[at] = h_len[at]; low[at] = h_low[at];
-            const size_t n = h_len[at] <= MW ? h_len[at] : 0;
-            for (size_t i = 0; i < n; ++i) walk[at * MW + i] = h_walk[at * MW + i];
+            ks_walk_out(walk, h_walk, at, h_len[at]);
         }
     }
     return HYPO_OK;
@@ -1741,7 +1720,7 @@ int hypo_gpu_kset_counts_enable(uint32_t n_texts) {
 
 int hypo_gpu_kset_mark(uint32_t text, const char* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t* n_windows, uint64_t* n_unmarked) {
     HYPO_KSET_ENTRY();
-    if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)");
+    KS_NEEDS_COUNTS();
     if (text >= ks.n_texts) return fail(HYPO_E_INVALID, "text = %u, the set has %u", text, ks.n_texts);
     std::vector<uint64_t> rel(1, 0);
     if (n_seqs) {
@@ -1751,18 +1730,13 @@ int hypo_gpu_kset_mark(uint32_t text, const char* bytes, const uint64_t* off, ui
     }
     ks.marked = true;                                                  // from here on the copy bytes may be other than zero
     unsigned long long sums[2] = {0, 0};
-    const uint64_t n = rel.back();
-    if (n) {
+    if (rel.back()) {                                                  // one pair of sums for the whole text
         hipStream_t st = g_ctx.stream;
-        HIP_TRY(ks.in.alloc(n));
-        HIP_TRY(ks.off.alloc(rel.size() * 8));
-        HIP_TRY(ks.res.alloc(16));
-        HIP_TRY(h2d(ks.in.p, bytes + off[0], n, st));
-        HIP_TRY(hipMemcpyAsync(ks.off.p, rel.data(), rel.size() * 8, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemsetAsync(ks.res.p, 0, 16, st));
-        HIP_TRY(hypo::kset_mark_run((const uint8_t*)ks.in.p, (const uint64_t*)ks.off.p, n_seqs, n, ks.k, ks.table, ks.slots, ks.planes, text,
-                                    (unsigned long long*)ks.res.p, st));
-        HIP_TRY(hipMemcpyAsync(sums, ks.res.p, 16, hipMemcpyDeviceToHost, st));
+        KsDev d;
+        if (const int rc = ks_query_seqs(ks, bytes + off[0], rel, rel.size() * 8, 1, d, [&](const KsDev& a, unsigned long long* d_sums) {
+                return hypo::kset_mark_run(a.in.u8(0), a.off.u64(0), n_seqs, rel.back(), ks.k, ks.table, ks.slots, ks.planes, text, d_sums, st);
+            })) return rc;
+        HIP_TRY(hipMemcpyAsync(sums, d.res.base, 16, hipMemcpyDeviceToHost, st));
         HIP_TRY(hipStreamSynchronize(st));
     }
     if (n_windows) *n_windows = sums[0];
@@ -1772,7 +1746,7 @@ int hypo_gpu_kset_mark(uint32_t text, const char* bytes, const uint64_t* off, ui
 
 int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist) {
     HYPO_KSET_ENTRY();
-    if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)");
+    KS_NEEDS_COUNTS();
     if (text >= ks.n_texts) return fail(HYPO_E_INVALID, "text = %u, the set has %u", text, ks.n_texts);
     if (!hist) return fail(HYPO_E_INVALID, "NULL buffer");
     hipStream_t st = g_ctx.stream;
@@ -1789,7 +1763,7 @@ int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist) {
 // ---- a least count for the queries (hypo --qv-min-count) --------------------------------------------------------------------------
 int hypo_gpu_kset_min_count(uint32_t t) {
     HYPO_KSET_ENTRY();
-    if (!ks.n_texts) return fail(HYPO_E_INVALID, "the k-mer set keeps no counts (hypo_gpu_kset_counts_enable)");
+    KS_NEEDS_COUNTS();
     if (t < 1 || t > 255) return fail(HYPO_E_INVALID, "t = %u out of range 1..255 (the k-mer set counts up to 255)", t);
     ks.min_count = t;                                                  // read when a query launches: the counts are those of that moment
     return HYPO_OK;
@@ -1865,9 +1839,9 @@ int hypo_gpu_kset_import(const uint64_t* keys, const uint8_t* counts, uint64_t n
     }
     if (const int rc = ks_make_room(ks, n, "records", st)) return rc;
     unsigned long long ctr[2] = {0, 0}, sum = 0;
-    HIP_TRY(hipMemsetAsync(ks.ctr.p, 0, 16, st));
-    HIP_TRY(hypo::kset_import_run(d_keys, d_counts, n, ks.table, ks.slots, (unsigned long long*)ks.ctr.p, ks.planes, d_bad + 2, st));
-    HIP_TRY(hipMemcpyAsync(ctr, ks.ctr.p, 16, hipMemcpyDeviceToHost, st));
+    const hipError_t kset_import =
+        ks_counted(ks, ctr, st, [&](unsigned long long* d_ctr) { return hypo::kset_import_run(d_keys, d_counts, n, ks.table, ks.slots, d_ctr, ks.planes, d_bad + 2, st); });
+    HIP_TRY(kset_import);
     HIP_TRY(hipMemcpyAsync(&sum, d_bad + 2, 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     ks.count += ctr[0];

@@ -37,12 +37,13 @@
 // Bounds: bytes are read as kmer_roll.hpp says, slot indices are < slots by construction, total / missing indices are < n_seqs
 // (a lane's sequence comes from ks_seq_of, a search in off[0 .. n_seqs] for a position < n = off[n_seqs]).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "kset_kernel.hpp"
 #include "kmer_roll.hpp"
 
 namespace hypo {
 
-constexpr int KS_THREADS = KR_THREADS;                         // every kernel of this file
+static_assert(KS_THREADS == KR_THREADS, "every kernel of this file has the workgroup of kmer_roll.hpp");
 
 __device__ __forceinline__ uint64_t ks_mix64(uint64_t x) {      // the 64-bit finaliser of MurmurHash3 (public domain)
     x ^= x >> 33; x *= 0xff51afd7ed558ccdull;
@@ -493,18 +494,18 @@ __global__ void __launch_bounds__(KS_THREADS) kset_track_finish_kernel(const uin
 
 uint32_t kset_track_blocks(uint64_t n) { return (uint32_t)(n / KR_BLOCK_BYTES + 1); }
 
-hipError_t kset_track_count_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table, uint64_t slots,
-                                unsigned long long* total, unsigned long long* missing, const uint8_t* want, uint32_t* miss_bits, uint32_t* begin_bits,
-                                uint64_t* sums, uint64_t* pre, const uint32_t* planes, uint32_t min_count, hipStream_t st) {
+hipError_t kset_track_count_run(const KsetView& set, const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, unsigned long long* total,
+                                unsigned long long* missing, const uint8_t* want, uint32_t* miss_bits, uint32_t* begin_bits, uint64_t* sums, uint64_t* pre,
+                                hipStream_t st) {
     const uint32_t blocks = kset_track_blocks(n);
-    if (min_count > 1)
-        kset_track_flags_min_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits,
-                                                                               (const uint8_t*)planes, min_count);
+    if (set.min_count > 1)
+        kset_track_flags_min_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, set.k, set.table, set.slots, total, missing, want, miss_bits,
+                                                                               begin_bits, (const uint8_t*)set.planes, set.min_count);
     else
-        kset_track_flags_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing, want, miss_bits, begin_bits);
+        kset_track_flags_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, set.k, set.table, set.slots, total, missing, want, miss_bits, begin_bits);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    kset_track_count_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(miss_bits, begin_bits, k, sums);
+    kset_track_count_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(miss_bits, begin_bits, set.k, sums);
     if ((e = hipGetLastError()) != hipSuccess) return e;
     kset_track_scan_kernel<<<dim3(1), dim3(KS_SCAN_THREADS), 0, st>>>(sums, blocks, pre);
     return hipGetLastError();
@@ -595,6 +596,8 @@ __device__ __forceinline__ void ks_group_scan(Fetch fetch, bool have, uint32_t l
 
 // Bounds: a lane reads bytes[lo + x] for x < len only (lo + len <= n is checked by the caller); items and out are indexed below
 // n_items; the probe is ks_contains (slot indices < slots, at most `slots` steps).
+// (The two kernels do not share a body as the variants' and the fixes' do: through one, the compiler hands the two descriptor loads
+// each other's registers, and a refactor leaves the instruction stream as it is.)
 template <int G>
 __global__ void __launch_bounds__(KS_THREADS) kset_spans_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ item_lo,
                                                                  const uint32_t* __restrict__ item_len, uint32_t n_items, uint32_t k,
@@ -617,20 +620,25 @@ __global__ void __launch_bounds__(KS_THREADS) kset_spans_min_kernel(const uint8_
     ks_group_scan<G, true>([&](uint32_t x) { return (uint32_t)bytes[lo + x]; }, have, have ? item_len[item] : 0, k, table, slots, out, item, counts, t);
 }
 
-hipError_t kset_spans_run(const uint8_t* bytes, const uint64_t* item_lo, const uint32_t* item_len, uint32_t n_items, uint32_t k,
-                          const uint64_t* table, uint64_t slots, uint2* out, int group, const uint32_t* planes, uint32_t min_count, hipStream_t st) {
-    if (!n_items) return hipSuccess;
+// The grid of a kernel whose items take a group of `group` lanes each (32 or 64): launch(G, blocks), G the group as a compile-time
+// constant (decltype(G)::value), blocks the workgroups n_items need.  What it answers is hipGetLastError() after the launch.
+template <class Launch> hipError_t ks_launch_groups(uint32_t n_items, int group, Launch launch) {
     const uint32_t per_block = (uint32_t)KS_THREADS / (uint32_t)group;
-    const uint32_t blocks = (n_items + per_block - 1) / per_block;
-    if (min_count > 1) {
-        const uint8_t* counts = (const uint8_t*)planes;
-        if (group == 32) kset_spans_min_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out, counts, min_count);
-        else kset_spans_min_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out, counts, min_count);
-        return hipGetLastError();
-    }
-    if (group == 32) kset_spans_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out);
-    else kset_spans_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, k, table, slots, out);
+    const dim3 blocks((n_items + per_block - 1) / per_block);
+    if (group == 32) launch(std::integral_constant<int, 32>(), blocks); else launch(std::integral_constant<int, 64>(), blocks);
     return hipGetLastError();
+}
+
+hipError_t kset_spans_run(const KsetView& set, const uint8_t* bytes, const uint64_t* item_lo, const uint32_t* item_len, uint32_t n_items, uint2* out,
+                          int group, hipStream_t st) {
+    if (!n_items) return hipSuccess;
+    return ks_launch_groups(n_items, group, [&](auto g, dim3 blocks) {
+        constexpr int G = decltype(g)::value;
+        if (set.min_count > 1)
+            kset_spans_min_kernel<G><<<blocks, dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, set.k, set.table, set.slots, out, (const uint8_t*)set.planes,
+                                                                         set.min_count);
+        else kset_spans_kernel<G><<<blocks, dim3(KS_THREADS), 0, st>>>(bytes, item_lo, item_len, n_items, set.k, set.table, set.slots, out);
+    });
 }
 
 // ---- every subset of a site's edits (hypo --guard-records; DESIGN.md "k-mer guard by record") -------------------------------------------
@@ -669,6 +677,21 @@ __device__ __forceinline__ uint32_t ks_variant_byte(const uint8_t* __restrict__ 
     return bytes[sp + (p - vp)];
 }
 
+template <int G, bool MIN>
+__device__ __forceinline__ void ks_variants_body(const uint8_t* __restrict__ bytes, const uint8_t* __restrict__ alts, const uint64_t* __restrict__ site_lo,
+                                                 const uint32_t* __restrict__ edit_off, const uint64_t* __restrict__ eb, const uint64_t* __restrict__ ee,
+                                                 const uint64_t* __restrict__ ao, const uint32_t* __restrict__ al, const uint4* __restrict__ items,
+                                                 uint32_t n_items, uint32_t k, const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out,
+                                                 const uint8_t* __restrict__ counts, uint32_t t) {
+    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
+    const bool have = item < n_items;
+    const uint4 it = have ? items[item] : make_uint4(0, 0, 0, 0);
+    const uint64_t lo = have ? site_lo[it.x] : 0;
+    const uint32_t e0 = have ? edit_off[it.x] : 0, e1 = have ? edit_off[it.x + 1] : 0;
+    ks_group_scan<G, MIN>([&](uint32_t x) { return ks_variant_byte(bytes, alts, lo, e0, e1, eb, ee, ao, al, it.y, it.z + x); }, have, it.w, k, table, slots, out, item,
+                          counts, t);
+}
+
 template <int G>
 __global__ void __launch_bounds__(KS_THREADS) kset_variants_kernel(const uint8_t* __restrict__ bytes, const uint8_t* __restrict__ alts,
                                                                     const uint64_t* __restrict__ site_lo, const uint32_t* __restrict__ edit_off,
@@ -676,12 +699,7 @@ __global__ void __launch_bounds__(KS_THREADS) kset_variants_kernel(const uint8_t
                                                                     const uint64_t* __restrict__ ao, const uint32_t* __restrict__ al,
                                                                     const uint4* __restrict__ items, uint32_t n_items, uint32_t k,
                                                                     const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out) {
-    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
-    const bool have = item < n_items;
-    const uint4 it = have ? items[item] : make_uint4(0, 0, 0, 0);
-    const uint64_t lo = have ? site_lo[it.x] : 0;
-    const uint32_t e0 = have ? edit_off[it.x] : 0, e1 = have ? edit_off[it.x + 1] : 0;
-    ks_group_scan<G, false>([&](uint32_t x) { return ks_variant_byte(bytes, alts, lo, e0, e1, eb, ee, ao, al, it.y, it.z + x); }, have, it.w, k, table, slots, out, item);
+    ks_variants_body<G, false>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, out, nullptr, 1);
 }
 
 // kset_variants_kernel against R_t (hypo --qv-min-count; the section "a least count" above)
@@ -693,13 +711,7 @@ __global__ void __launch_bounds__(KS_THREADS) kset_variants_min_kernel(const uin
                                                                         const uint4* __restrict__ items, uint32_t n_items, uint32_t k,
                                                                         const uint64_t* __restrict__ table, uint64_t slots, uint2* __restrict__ out,
                                                                         const uint8_t* __restrict__ counts, uint32_t t) {
-    const uint64_t item = ((uint64_t)blockIdx.x * KS_THREADS + threadIdx.x) / G;
-    const bool have = item < n_items;
-    const uint4 it = have ? items[item] : make_uint4(0, 0, 0, 0);
-    const uint64_t lo = have ? site_lo[it.x] : 0;
-    const uint32_t e0 = have ? edit_off[it.x] : 0, e1 = have ? edit_off[it.x + 1] : 0;
-    ks_group_scan<G, true>([&](uint32_t x) { return ks_variant_byte(bytes, alts, lo, e0, e1, eb, ee, ao, al, it.y, it.z + x); }, have, it.w, k, table, slots, out, item,
-                           counts, t);
+    ks_variants_body<G, true>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, out, counts, t);
 }
 
 // One lane per site: the pieces of every variant are added up (the site's items are in mask order, a variant's pieces next to each
@@ -728,26 +740,21 @@ __global__ void __launch_bounds__(KS_THREADS) kset_variants_reduce_kernel(const 
     best_mask[s] = bm; best_total[s] = bt; best_missing[s] = bmis;
 }
 
-hipError_t kset_variants_run(const uint8_t* bytes, const uint8_t* alts, const uint64_t* site_lo, const uint32_t* edit_off, const uint64_t* eb,
-                             const uint64_t* ee, const uint64_t* ao, const uint32_t* al, const uint4* items, uint32_t n_items,
-                             const uint32_t* site_item, const uint32_t* var_off, uint32_t n_sites, uint32_t k, const uint64_t* table, uint64_t slots,
-                             uint2* item_res, uint32_t* best_mask, unsigned long long* best_total, unsigned long long* best_missing,
-                             unsigned long long* var_total, unsigned long long* var_missing, int group, const uint32_t* planes, uint32_t min_count,
-                             hipStream_t st) {
-    if (!n_sites || !n_items) return hipSuccess;
-    const uint32_t per_block = (uint32_t)KS_THREADS / (uint32_t)group;
-    const uint32_t blocks = (n_items + per_block - 1) / per_block;
-    const uint8_t* counts = (const uint8_t*)planes;
-    if (min_count > 1 && group == 32)
-        kset_variants_min_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res, counts, min_count);
-    else if (min_count > 1)
-        kset_variants_min_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res, counts, min_count);
-    else if (group == 32) kset_variants_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res);
-    else kset_variants_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, alts, site_lo, edit_off, eb, ee, ao, al, items, n_items, k, table, slots, item_res);
-    hipError_t e = hipGetLastError();
+hipError_t kset_variants_run(const KsetView& set, const KsetVariantsIn& in, const KsetVariantsOut& out, int group, hipStream_t st) {
+    if (!in.n_sites || !in.n_items) return hipSuccess;
+    const hipError_t e = ks_launch_groups(in.n_items, group, [&](auto g, dim3 blocks) {
+        constexpr int G = decltype(g)::value;
+        if (set.min_count > 1)
+            kset_variants_min_kernel<G><<<blocks, dim3(KS_THREADS), 0, st>>>(in.bytes, in.alts, in.site_lo, in.edit_off, in.eb, in.ee, in.ao, in.al, in.items, in.n_items, set.k,
+                                                                            set.table, set.slots, out.item_res, (const uint8_t*)set.planes, set.min_count);
+        else
+            kset_variants_kernel<G><<<blocks, dim3(KS_THREADS), 0, st>>>(in.bytes, in.alts, in.site_lo, in.edit_off, in.eb, in.ee, in.ao, in.al, in.items, in.n_items, set.k,
+                                                                        set.table, set.slots, out.item_res);
+    });
     if (e != hipSuccess) return e;
-    kset_variants_reduce_kernel<<<dim3((n_sites + KS_THREADS - 1) / KS_THREADS), dim3(KS_THREADS), 0, st>>>(items, item_res, site_item, var_off, n_sites, best_mask, best_total,
-                                                                                                              best_missing, var_total, var_missing);
+    kset_variants_reduce_kernel<<<dim3((in.n_sites + KS_THREADS - 1) / KS_THREADS), dim3(KS_THREADS), 0, st>>>(in.items, out.item_res, in.site_item, in.var_off, in.n_sites,
+                                                                                                                 out.best_mask, out.best_total, out.best_missing, out.var_total,
+                                                                                                                 out.var_missing);
     return hipGetLastError();
 }
 
@@ -863,26 +870,22 @@ __global__ void __launch_bounds__(KS_THREADS) kset_fixes_reduce_kernel(const uin
     best_cand[s] = bc; best_total[s] = bt; best_missing[s] = bm; zeros[s] = nz;
 }
 
-hipError_t kset_fixes_run(const uint8_t* bytes, const uint64_t* site_lo, const uint32_t* site_len, const uint32_t* site_c0, const uint32_t* site_w,
-                          const uint32_t* item_off, uint32_t n_sites, uint32_t n_items, uint32_t k, const uint64_t* table, uint64_t slots, uint2* item_res,
-                          unsigned long long* none_total, unsigned long long* none_missing, uint32_t* best_cand, unsigned long long* best_total,
-                          unsigned long long* best_missing, uint32_t* zeros, unsigned long long* cand_total, unsigned long long* cand_missing, int group,
-                          const uint32_t* planes, uint32_t min_count, hipStream_t st) {
-    if (!n_sites || !n_items) return hipSuccess;
-    const uint32_t per_block = (uint32_t)KS_THREADS / (uint32_t)group;
-    const uint32_t blocks = (n_items + per_block - 1) / per_block;
-    const uint8_t* counts = (const uint8_t*)planes;
-    if (min_count > 1 && group == 32)
-        kset_fixes_min_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, item_res, counts, min_count);
-    else if (min_count > 1)
-        kset_fixes_min_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, item_res, counts, min_count);
-    else if (group == 32) kset_fixes_kernel<32><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, item_res);
-    else kset_fixes_kernel<64><<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_len, site_c0, site_w, item_off, n_sites, n_items, k, table, slots, item_res);
-    hipError_t e = hipGetLastError();
+hipError_t kset_fixes_run(const KsetView& set, const KsetFixesIn& in, const KsetFixesOut& out, int group, hipStream_t st) {
+    if (!in.n_sites || !in.n_items) return hipSuccess;
+    const hipError_t e = ks_launch_groups(in.n_items, group, [&](auto g, dim3 blocks) {
+        constexpr int G = decltype(g)::value;
+        if (set.min_count > 1)
+            kset_fixes_min_kernel<G><<<blocks, dim3(KS_THREADS), 0, st>>>(in.bytes, in.site_lo, in.site_len, in.site_c0, in.site_w, in.item_off, in.n_sites, in.n_items, set.k,
+                                                                         set.table, set.slots, out.item_res, (const uint8_t*)set.planes, set.min_count);
+        else
+            kset_fixes_kernel<G><<<blocks, dim3(KS_THREADS), 0, st>>>(in.bytes, in.site_lo, in.site_len, in.site_c0, in.site_w, in.item_off, in.n_sites, in.n_items, set.k,
+                                                                     set.table, set.slots, out.item_res);
+    });
     if (e != hipSuccess) return e;
-    kset_fixes_reduce_kernel<<<dim3((n_sites + KS_THREADS - 1) / KS_THREADS), dim3(KS_THREADS), 0, st>>>(bytes, site_lo, site_c0, site_w, item_off, item_res, n_sites, none_total,
-                                                                                                           none_missing, best_cand, best_total, best_missing, zeros,
-                                                                                                           cand_total, cand_missing);
+    kset_fixes_reduce_kernel<<<dim3((in.n_sites + KS_THREADS - 1) / KS_THREADS), dim3(KS_THREADS), 0, st>>>(in.bytes, in.site_lo, in.site_c0, in.site_w, in.item_off, out.item_res,
+                                                                                                              in.n_sites, out.none_total, out.none_missing, out.best_cand,
+                                                                                                              out.best_total, out.best_missing, out.zeros, out.cand_total,
+                                                                                                              out.cand_missing);
     return hipGetLastError();
 }
 
@@ -1007,16 +1010,16 @@ __global__ void __launch_bounds__(KS_THREADS) kset_walks_min_kernel(const uint8_
     ks_walks_body<true>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, status, steps, len, walk, counts, t);
 }
 
-hipError_t kset_walks_run(const uint8_t* bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites,
-                          uint32_t budget, uint32_t k, const uint64_t* table, uint64_t slots, uint32_t* status, uint32_t* steps, uint32_t* len, uint8_t* walk,
-                          const uint32_t* planes, uint32_t min_count, hipStream_t st) {
-    if (!n_sites) return hipSuccess;
+hipError_t kset_walks_run(const KsetView& set, const KsetWalkSites& s, uint32_t budget, uint32_t* status, uint32_t* steps, uint32_t* len, uint8_t* walk,
+                          hipStream_t st) {
+    if (!s.n_sites) return hipSuccess;
     static_assert(KSET_MAX_WALK <= KS_WALK_STACK, "a stack byte per depth");
-    const uint32_t blocks = (n_sites + KS_WALK_SITES - 1) / KS_WALK_SITES;
-    if (min_count > 1)
-        kset_walks_min_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, status, steps, len, walk,
-                                                                         (const uint8_t*)planes, min_count);
-    else kset_walks_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, status, steps, len, walk);
+    const uint32_t blocks = (s.n_sites + KS_WALK_SITES - 1) / KS_WALK_SITES;
+    if (set.min_count > 1)
+        kset_walks_min_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(s.bytes, s.from, s.to, s.dlo, s.dhi, s.n_sites, budget, set.k, set.table, set.slots, status, steps, len,
+                                                                         walk, (const uint8_t*)set.planes, set.min_count);
+    else
+        kset_walks_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(s.bytes, s.from, s.to, s.dlo, s.dhi, s.n_sites, budget, set.k, set.table, set.slots, status, steps, len, walk);
     return hipGetLastError();
 }
 
@@ -1120,13 +1123,12 @@ __global__ void __launch_bounds__(KS_THREADS) kset_walk_sets_kernel(const uint8_
     }
 }
 
-hipError_t kset_walk_sets_run(const uint8_t* bytes, const uint64_t* from, const uint64_t* to, const uint32_t* dlo, const uint32_t* dhi, uint32_t n_sites,
-                              uint32_t budget, uint32_t k, const uint64_t* table, uint64_t slots, const uint32_t* planes, uint32_t min_count, uint32_t* status,
-                              uint32_t* steps, uint32_t* n_walks, uint32_t* len, uint32_t* low, uint8_t* walk, hipStream_t st) {
-    if (!n_sites) return hipSuccess;
-    const uint32_t blocks = (n_sites + KS_WALK_SITES - 1) / KS_WALK_SITES;
-    kset_walk_sets_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(bytes, from, to, dlo, dhi, n_sites, budget, k, table, slots, (const uint8_t*)planes,
-                                                                     min_count < 1 ? 1u : min_count, status, steps, n_walks, len, low, walk);
+hipError_t kset_walk_sets_run(const KsetView& set, const KsetWalkSites& s, uint32_t budget, uint32_t* status, uint32_t* steps, uint32_t* n_walks,
+                              uint32_t* len, uint32_t* low, uint8_t* walk, hipStream_t st) {
+    if (!s.n_sites) return hipSuccess;
+    const uint32_t blocks = (s.n_sites + KS_WALK_SITES - 1) / KS_WALK_SITES;
+    kset_walk_sets_kernel<<<dim3(blocks), dim3(KS_THREADS), 0, st>>>(s.bytes, s.from, s.to, s.dlo, s.dhi, s.n_sites, budget, set.k, set.table, set.slots,
+                                                                     (const uint8_t*)set.planes, set.min_count < 1 ? 1u : set.min_count, status, steps, n_walks, len, low, walk);
     return hipGetLastError();
 }
 
@@ -1181,13 +1183,14 @@ hipError_t kset_spectrum_run(const uint32_t* planes, uint64_t slots, uint32_t te
     return hipGetLastError();
 }
 
-hipError_t kset_query_run(const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, uint32_t k, const uint64_t* table,
-                          uint64_t slots, unsigned long long* total, unsigned long long* missing, const uint32_t* planes, uint32_t min_count, hipStream_t st) {
+hipError_t kset_query_run(const KsetView& set, const uint8_t* bytes, const uint64_t* off, uint32_t n_seqs, uint64_t n, unsigned long long* total,
+                          unsigned long long* missing, hipStream_t st) {
     if (!n || !n_seqs) return hipSuccess;
     const uint64_t blocks = (n + KR_BLOCK_BYTES - 1) / KR_BLOCK_BYTES;
-    if (min_count > 1)
-        kset_query_min_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing, (const uint8_t*)planes, min_count);
-    else kset_query_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, k, table, slots, total, missing);
+    if (set.min_count > 1)
+        kset_query_min_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, set.k, set.table, set.slots, total, missing,
+                                                                                   (const uint8_t*)set.planes, set.min_count);
+    else kset_query_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, n_seqs, n, set.k, set.table, set.slots, total, missing);
     return hipGetLastError();
 }
 
