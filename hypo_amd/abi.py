@@ -42,6 +42,12 @@ KSET_MAX_TEXTS = 4
 KSET_SPECTRUM_ROWS, KSET_SPECTRUM_COLS = 256, 5
 KSET_SPECTRUM_BINS = KSET_SPECTRUM_ROWS * KSET_SPECTRUM_COLS
 
+# hypo_gpu_kset_query_depth (HYPO_KSET_DEPTH_MIN_BIN, HYPO_KSET_DEPTH_MAX_BIN); hypo_amd.capi fills the outputs with the sentinels
+# before a call (no bin has that many windows; a median of 255 is possible, so a test that looks for untouched bytes uses the u32 arrays)
+KSET_DEPTH_MIN_BIN, KSET_DEPTH_MAX_BIN = 32, 65536
+DEPTH_UNTOUCHED32 = 0xFFFFFFFF
+DEPTH_UNTOUCHED8 = 0xFF
+
 # hypo_gpu_kset_export / _import (HYPO_KSET_EXPORT_END): the cursor a finished export sequence leaves
 KSET_EXPORT_END = 0xFFFFFFFFFFFFFFFF
 

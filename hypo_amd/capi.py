@@ -33,7 +33,7 @@ EXPORTS = [
     "hypo_gpu_kset_query_spans", "hypo_gpu_kset_query_variants", "hypo_gpu_kset_query_track", "hypo_gpu_kset_query_fixes",
     "hypo_gpu_kset_query_walks", "hypo_gpu_kset_query_walk_sets",
     "hypo_gpu_kset_counts_enable", "hypo_gpu_kset_mark", "hypo_gpu_kset_spectrum", "hypo_gpu_kset_min_count",
-    "hypo_gpu_kset_export", "hypo_gpu_kset_import",
+    "hypo_gpu_kset_export", "hypo_gpu_kset_import", "hypo_gpu_kset_query_depth",
 ]
 KSET_SPAN_PIECE = 2048        # windows per piece of a long span (kset_kernel.hpp)
 KSET_MAX_EDITS = 12           # edits of a site of hypo_gpu_kset_query_variants (HYPO_KSET_MAX_EDITS)
@@ -508,6 +508,35 @@ class HypoGpu:
         """on a set that counts: from the next call on the four queries answer against the k-mers the reads have at least t times
         (1..255; 1 = the set itself)"""
         self._check(self.kset_min_count_rc(t))
+
+    def kset_query_depth_rc(self, seqs_or_text, off=None, bin=1024, text=0, unit=1, n_bins=None):
+        """(return code, windows, missing, rated, over, under: u32[n_bins], med_count u8[n_bins]) of one call of
+        hypo_gpu_kset_query_depth; nothing is checked here.  A list of byte strings, or one text with its n + 1 offsets.  n_bins None:
+        the sum of ceil(length / bin).  The arrays are filled with abi.DEPTH_UNTOUCHED32 / 8 before the call."""
+        if off is None:
+            seqs = [s.encode() if isinstance(s, str) else bytes(s) for s in seqs_or_text]
+            off = np.zeros(len(seqs) + 1, dtype=np.uint64)
+            off[1:] = np.cumsum([len(s) for s in seqs], dtype=np.uint64)
+            data = b"".join(seqs)
+        else:
+            data = seqs_or_text.encode() if isinstance(seqs_or_text, str) else bytes(seqs_or_text)
+            off = np.ascontiguousarray(off, dtype=np.uint64)
+        n = off.size - 1
+        if n_bins is None:
+            n_bins = int(sum(-(-int(l) // bin) for l in np.diff(off.astype(np.int64)))) if bin > 0 else 0
+        buf = np.frombuffer(data + b"\0", dtype=np.uint8)                # (an empty text still has an address)
+        u32 = [np.full(max(n_bins, 1), abi.DEPTH_UNTOUCHED32, dtype=np.uint32) for _ in range(5)]
+        med = np.full(max(n_bins, 1), abi.DEPTH_UNTOUCHED8, dtype=np.uint8)
+        rc = int(self.lib.hypo_gpu_kset_query_depth(_p(buf), _p(off), C.c_uint32(n), C.c_uint32(bin), C.c_uint32(text), C.c_uint32(unit), C.c_uint64(n_bins),
+                                                    *[_p(a) for a in u32], _p(med)))
+        return (rc,) + tuple(a[:n_bins] for a in u32) + (med[:n_bins],)
+
+    def kset_query_depth(self, seqs_or_text, off=None, bin=1024, text=0, unit=1):
+        """per bin of `bin` window starts of every sequence (bins numbered sequence by sequence): (windows, missing, rated, over,
+        under, med_count) of the read count bytes against the copy bytes of plane `text`, a copy being worth `unit` reads"""
+        out = self.kset_query_depth_rc(seqs_or_text, off, bin, text, unit)
+        self._check(out[0])
+        return out[1:]
 
     def kset_export_rc(self, cursor: int, cap: int, keys, counts=None):
         """(return code, cursor after the call, n_out, digest of the call) of ONE call of hypo_gpu_kset_export into the caller's arrays:

@@ -1769,6 +1769,49 @@ int hypo_gpu_kset_min_count(uint32_t t) {
     return HYPO_OK;
 }
 
+// ---- read count against copy number per bin (hypo --qv-cn) -------------------------------------------------------------------------
+// Arenas: ks.in the bytes; ks.off the offsets and, behind them, the bin offsets; ks.res the six arrays.  The kernel writes every
+// entry below n_bins, so nothing is cleared and nothing of the caller's is touched before the results are down.
+int hypo_gpu_kset_query_depth(const char* bytes, const uint64_t* off, uint32_t n_seqs, uint32_t bin, uint32_t text, uint32_t unit, uint64_t n_bins,
+                              uint32_t* windows, uint32_t* missing, uint32_t* rated, uint32_t* over, uint32_t* under, uint8_t* med_count) {
+    HYPO_KSET_ENTRY();
+    KS_NEEDS_COUNTS();
+    static_assert(hypo::KSET_DEPTH_MIN_BIN == HYPO_KSET_DEPTH_MIN_BIN && hypo::KSET_DEPTH_MAX_BIN == HYPO_KSET_DEPTH_MAX_BIN, "the header's range of bin");
+    if (text >= ks.n_texts) return fail(HYPO_E_INVALID, "text = %u, the set has %u", text, ks.n_texts);
+    if (bin < hypo::KSET_DEPTH_MIN_BIN || bin > hypo::KSET_DEPTH_MAX_BIN)
+        return fail(HYPO_E_INVALID, "bin = %u out of range %u..%u (HYPO_KSET_DEPTH_MIN_BIN, HYPO_KSET_DEPTH_MAX_BIN)", bin, hypo::KSET_DEPTH_MIN_BIN, hypo::KSET_DEPTH_MAX_BIN);
+    if (unit < 1 || unit > 255) return fail(HYPO_E_INVALID, "unit = %u out of range 1..255 (the k-mer set counts up to 255)", unit);
+    if (!n_seqs) return n_bins ? fail(HYPO_E_INVALID, "n_bins = %llu, no sequence has a bin", (unsigned long long)n_bins) : HYPO_OK;
+    if (!off) return fail(HYPO_E_INVALID, "NULL buffer");
+    std::vector<uint64_t> rel;
+    if (const int rc = ks_rel_offsets(off, n_seqs, rel)) return rc;
+    std::vector<uint64_t> bin_off((size_t)n_seqs + 1, 0);
+    for (uint32_t s = 0; s < n_seqs; ++s) bin_off[s + 1] = bin_off[s] + (rel[s + 1] - rel[s] + bin - 1) / bin;
+    if (bin_off[n_seqs] != n_bins)
+        return fail(HYPO_E_INVALID, "n_bins = %llu, the sequences have %llu bins of %u", (unsigned long long)n_bins, (unsigned long long)bin_off[n_seqs], bin);
+    if (!n_bins) return HYPO_OK;                                       // (every sequence is empty)
+    if (!bytes || !windows || !missing || !rated || !over || !under || !med_count) return fail(HYPO_E_INVALID, "NULL buffer");
+    if (n_bins >= ((uint64_t)1 << 32)) return fail(HYPO_E_INVALID, "n_bins = %llu: at most 2^32 - 1 bins a call", (unsigned long long)n_bins);
+    hipStream_t st = g_ctx.stream;
+    Carver co, cr;
+    co.take(rel.size() * 8);
+    const size_t at_bin = co.take(bin_off.size() * 8);
+    const size_t o_win = cr.take((size_t)n_bins * 4), o_mis = cr.take((size_t)n_bins * 4), o_rat = cr.take((size_t)n_bins * 4), o_ov = cr.take((size_t)n_bins * 4),
+                 o_un = cr.take((size_t)n_bins * 4), o_med = cr.take((size_t)n_bins);
+    KsDev d;
+    if (const int rc = ks_arenas(ks, rel.back(), co.at, cr.at, d)) return rc;
+    HIP_TRY(d.in.up(0, bytes + off[0], rel.back()));
+    HIP_TRY(d.off.up(0, rel.data(), rel.size() * 8));
+    HIP_TRY(d.off.up(at_bin, bin_off.data(), bin_off.size() * 8));
+    const hypo::KsetDepthOut out{d.res.u32(o_win), d.res.u32(o_mis), d.res.u32(o_rat), d.res.u32(o_ov), d.res.u32(o_un), d.res.u8(o_med)};
+    HIP_TRY(hypo::kset_depth_run(ks.view(), d.in.u8(0), d.off.u64(0), d.off.u64(at_bin), n_seqs, n_bins, bin, text, unit, out, st));
+    HIP_TRY(d.res.down(windows, o_win, (size_t)n_bins * 4)); HIP_TRY(d.res.down(missing, o_mis, (size_t)n_bins * 4));
+    HIP_TRY(d.res.down(rated, o_rat, (size_t)n_bins * 4)); HIP_TRY(d.res.down(over, o_ov, (size_t)n_bins * 4));
+    HIP_TRY(d.res.down(under, o_un, (size_t)n_bins * 4)); HIP_TRY(d.res.down(med_count, o_med, (size_t)n_bins));
+    HIP_TRY(hipStreamSynchronize(st));
+    return HYPO_OK;
+}
+
 // ---- the set's records out and in (hypo --qv-save / --qv-load) ---------------------------------------------------------------------
 // The cursor of an export sequence is the first slot the next call looks at: a call takes at most `cap` slots, so it never has more
 // than `cap` records.  Arenas: ks.in holds the call's keys and, behind them, its count bytes; ks.off the tile sums and prefixes;

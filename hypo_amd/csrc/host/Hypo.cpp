@@ -10,6 +10,7 @@
 #include "QvReport.hpp"
 #include "ReadKmerSet.hpp"
 #include "SpectraReport.hpp"
+#include "CnReport.hpp"
 #include <ctime>
 #include <omp.h>
 #include <sys/resource.h>
@@ -21,7 +22,7 @@
 namespace hypo {
 extern std::atomic<uint64_t> g_stage_counters[5];      // host/Contig.cpp
 
-// --vcf, --qv, --qv-bed, --qv-spectra, --kmer-guard, --kmer-fix, --kmer-bridge: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
+// --vcf, --qv, --qv-bed, --qv-spectra, --qv-cn, --kmer-guard, --kmer-fix, --kmer-bridge: the entry points Hypo::bind_extras bound and what they keep from the reads to the last contig
 struct Extras {
     EditScriptsFn edit_fn = nullptr, guard_edit_fn = nullptr;
     ReadKmerSet set;                                       // the k-mers of the reads, on context 0 from bind_extras to commit_outputs
@@ -30,11 +31,12 @@ struct Extras {
     SpectraReport spectra{set};
     KmerFix fix{set};
     KmerBridge bridge{set};
-    bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false, fix_on = false, bridge_on = false, vote_on = false;
+    CnReport cn{set};
+    bool qv_on = false, bed_on = false, guard_on = false, spectra_on = false, fix_on = false, bridge_on = false, vote_on = false, cn_on = false;
     uint32_t min_given = 1;                                // --qv-min-count: 1 = off, 0 = the valley
     bool min_on() const { return min_given != 1; }
     bool ask_on = false;                                   // --qv or --qv-bed: every contig's texts are put to the set
-    bool text_on = false;                                  // ... or --qv-spectra: every contig's texts are needed as strings
+    bool text_on = false;                                  // ... or --qv-spectra or --qv-cn: every contig's texts are needed as strings
     bool set_on = false;                                   // ... or --kmer-guard, --kmer-fix, --kmer-bridge or --qv-save: the set is built
     std::string save_to, load_from;                        // --qv-save / --qv-load: the set also goes to a file / comes from one, not from the reads
     bool save_on() const { return !save_to.empty(); }
@@ -50,6 +52,7 @@ struct Extras {
     // one contig's two texts to whoever wants them: the set's queries, then the marks of --qv-spectra
     int texts(size_t contig, const std::string& draft, const std::string& polished) {
         const int rc = ask_on ? qv.push(contig, draft, polished) : HYPO_OK;
+        if (rc == HYPO_OK && cn_on) cn.push(contig, polished);                    // (kept until the last contig: CnReport::run)
         return rc == HYPO_OK && spectra_on ? spectra.push(draft, polished) : rc;
     }
     int texts_flush() {
@@ -238,7 +241,8 @@ void Hypo::bind_extras(Extras& ex) {
     ex.guard_on = _cFlags.kmer_guard;
     ex.qv_on = !_cFlags.qv_filename.empty();
     ex.ask_on = ex.qv_on || ex.bed_on;
-    ex.text_on = ex.ask_on || ex.spectra_on;
+    ex.cn_on = !_cFlags.qv_cn_filename.empty();
+    ex.text_on = ex.ask_on || ex.spectra_on || ex.cn_on;
     ex.save_to = _cFlags.qv_save_filename;
     ex.load_from = _cFlags.qv_load_filename;
     ex.set_on = ex.text_on || ex.guard_on || ex.fix_on || ex.bridge_on || ex.save_on();
@@ -282,6 +286,13 @@ void Hypo::bind_extras(Extras& ex) {
     // --qv-min-count: counts on the set and the threshold of its queries (1 is the run without it)
     if (ex.min_on())
         require("--qv-min-count", {{" hypo_gpu_kset_counts_enable, hypo_gpu_kset_spectrum and hypo_gpu_kset_min_count,", ex.set.bind_counts()}, {" and " + the_set, have_set}});
+    // --qv-cn: the depth query, counts on the set, and the mark of the final text (--qv-spectra's own when both are given)
+    if (ex.cn_on) {
+        (void)ex.set.bind_counts();
+        require("--qv-cn", {{" hypo_gpu_kset_query_depth", ex.set.bind_depth()}, {" hypo_gpu_kset_counts_enable, hypo_gpu_kset_mark and hypo_gpu_kset_spectrum", ex.cn.bind() && ex.set.have_counts()},
+                            {" " + the_set, have_set}}, true);
+        ex.cn.configure(_cFlags.qv_cn_bin, _cFlags.qv_cn_unit, ex.spectra_on ? (uint32_t)SpectraReport::POLISHED : 0u, !ex.spectra_on);
+    }
     // --qv-spectra: counts on the set, and the marks
     if (ex.spectra_on) {
         (void)ex.set.bind_counts();
@@ -309,9 +320,9 @@ void Hypo::bind_extras(Extras& ex) {
         const uint64_t cap = _cFlags.qv_mem_gib > 0 ? (uint64_t)(_cFlags.qv_mem_gib * (double)(1ull << 30)) : 0;
         if (ex.set.begin(_cFlags.qv_k, ex.load_on() ? load_keys : _cFlags.genome_size, cap) != HYPO_OK) ex.set_fail("the k-mer set could not be created");
         ex.set_sink = ex.set.sink();
-        // --qv-spectra, --qv-min-count, --kmer-bridge-vote, --qv-save: the set counts from its first k-mer on, with a plane of copy bytes for each
+        // --qv-spectra, --qv-cn, --qv-min-count, --kmer-bridge-vote, --qv-save: the set counts from its first k-mer on, with a plane of copy bytes for each
         // text that is going to be marked (one at the least), and the reads reach it window by window, each once
-        if (ex.spectra_on || ex.min_on() || ex.vote_on || ex.save_on()) {
+        if (ex.spectra_on || ex.cn_on || ex.min_on() || ex.vote_on || ex.save_on()) {
             if (ex.set.enable_counts(ex.spectra_on ? SpectraReport::N_TEXTS : 1) != HYPO_OK) ex.set_fail("the k-mer set could not be made to count");
             ex.set_sink.exact = true;
         }
@@ -888,6 +899,17 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         if (hypo_gpu_use_device(0) != HYPO_OK || ex.spectra.fetch(_cFlags.qv_reliable_min) != HYPO_OK) ex.set_fail("hypo_gpu_kset_spectrum");
         ex.spectra.write(out.open_spectra(_cFlags.qv_spectra_filename));
     }
+    // --qv-cn: every contig's final text is marked (here, or by --qv-spectra above); the depth pass runs before the set goes
+    if (ex.cn_on) {
+        const char* what = "";
+        const int rc = hypo_gpu_use_device(0) != HYPO_OK ? HYPO_E_HIP : ex.cn.run(what);
+        if (rc == CnReport::E_NO_PEAK) {
+            std::fprintf(stderr, "[Hypo::QV] Error: --qv-cn: the read k-mer histogram has no peak at or above its valley, so the read count of one copy is unknown: give it with --qv-cn-unit\n");
+            ex.set.end();
+            std::exit(1);
+        }
+        if (rc != HYPO_OK) ex.set_fail(what);
+    }
     if (ex.fix_on) ex.fix.write(out.open_fixes(_cFlags.kmer_fix_filename));
     if (ex.bridge_on) ex.bridge.write(out.open_bridges(_cFlags.kmer_bridge_filename));
     // the set has answered its last query
@@ -898,6 +920,11 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
         for (const auto& c : _contigs) names.push_back(c->get_name());
         if (ex.qv_on) ex.qv.write(out.open_qv(_cFlags.qv_filename), names);
         if (ex.bed_on) ex.qv.write_track(out.open_bed(_cFlags.qv_bed_filename), names);
+    }
+    if (ex.cn_on) {
+        std::vector<std::string> names;
+        for (const auto& c : _contigs) names.push_back(c->get_name());
+        ex.cn.write(out.open_cn(_cFlags.qv_cn_filename), names);
     }
     out.commit([&](RunOutputs::Which w) {
         if (w == RunOutputs::FASTA && ex.guard_on && ex.guard.by_record()) {
@@ -941,6 +968,12 @@ void Hypo::commit_outputs(Extras& ex, RunOutputs& out) {
                              ex.bridge.vote_ratio(), (unsigned)HYPO_KSET_MAX_WALKS, (unsigned long long)vs.asked, (unsigned long long)vs.chosen, (unsigned long long)vs.close,
                              (unsigned long long)vs.many, (unsigned)HYPO_KSET_MAX_WALKS, (unsigned long long)vs.over_budget);
             }
+        }
+        if (w == RunOutputs::CN) {
+            const CnReport::Sums cs = ex.cn.sums();
+            std::fprintf(stdout, "[Hypo::Hypo] Info: copy number %s (k = %u, bin = %u, unit = %u %s): %llu bins, %llu collapsed (%llu bases), %llu duplicated (%llu bases)\n",
+                         _cFlags.qv_cn_filename.c_str(), ex.cn.k(), ex.cn.bin(), ex.cn.unit(), ex.cn.unit_given() ? "given" : "peak", (unsigned long long)cs.bins,
+                         (unsigned long long)cs.collapsed, (unsigned long long)cs.collapsed_bases, (unsigned long long)cs.duplicated, (unsigned long long)cs.duplicated_bases);
         }
         if (w == RunOutputs::BED) {
             const QvReport::TrackSums ts = ex.qv.track_sums();

@@ -97,4 +97,61 @@ int ReadKmerSet::query_track(const std::string& text, const std::vector<uint64_t
     return rc;
 }
 
+bool ReadKmerSet::bind_depth() {
+    _depth = (decltype(_depth))dlsym(RTLD_DEFAULT, "hypo_gpu_kset_query_depth");
+    return have_depth();
+}
+
+uint32_t ReadKmerSet::peak(const uint64_t* h) {
+    uint32_t best = 0;
+    for (uint32_t c = valley(h); c < kRows - 1; ++c) if (h[c] > (best ? h[best] : 0)) best = c;
+    return best;
+}
+
+int ReadKmerSet::query_depth(const std::string& text, const std::vector<uint64_t>& off, uint32_t bin, uint32_t plane, uint32_t unit, Depth& out,
+                             size_t per_call) const {
+    const size_t n = off.size() - 1;
+    auto bins_of = [&](uint64_t len) { return (len + bin - 1) / bin; };
+    out = Depth();
+    Depth got;
+    // one call over the sequences `o`; the first `keep` of its bins are the answer's next ones
+    auto call = [&](const uint64_t* o, uint32_t n_seqs, uint64_t keep) {
+        uint64_t n_bins = 0;
+        for (uint32_t s = 0; s < n_seqs; ++s) n_bins += bins_of(o[s + 1] - o[s]);
+        got.windows.assign(n_bins, 0); got.missing.assign(n_bins, 0); got.rated.assign(n_bins, 0); got.over.assign(n_bins, 0); got.under.assign(n_bins, 0);
+        got.median.assign(n_bins, 0);
+        const int rc = _depth(text.data(), o, n_seqs, bin, plane, unit, n_bins, got.windows.data(), got.missing.data(), got.rated.data(), got.over.data(),
+                              got.under.data(), got.median.data());
+        if (rc != HYPO_OK) return rc;
+        if (keep > n_bins) keep = n_bins;
+        out.windows.insert(out.windows.end(), got.windows.begin(), got.windows.begin() + keep);
+        out.missing.insert(out.missing.end(), got.missing.begin(), got.missing.begin() + keep);
+        out.rated.insert(out.rated.end(), got.rated.begin(), got.rated.begin() + keep);
+        out.over.insert(out.over.end(), got.over.begin(), got.over.begin() + keep);
+        out.under.insert(out.under.end(), got.under.begin(), got.under.begin() + keep);
+        out.median.insert(out.median.end(), got.median.begin(), got.median.begin() + keep);
+        return (int)HYPO_OK;
+    };
+    for (size_t s = 0; s < n;) {
+        const uint64_t len = off[s + 1] - off[s];
+        if (len > per_call) {                                    // one long sequence, in pieces of whole bins
+            const uint64_t n_bins = bins_of(len);
+            const uint64_t step = per_call > (uint64_t)bin + _k ? (per_call - (_k - 1)) / bin : 1;
+            for (uint64_t j = 0; j < n_bins; j += step) {
+                const uint64_t j1 = j + step < n_bins ? j + step : n_bins;
+                const uint64_t lo = j * bin, hi = j1 == n_bins ? len : j1 * bin + (_k - 1) < len ? j1 * bin + (_k - 1) : len;
+                const uint64_t o[2] = {off[s] + lo, off[s] + hi};
+                if (const int rc = call(o, 1, j1 - j)) return rc;
+            }
+            ++s;
+            continue;
+        }
+        size_t e = s + 1;                                        // whole sequences as far as they fit
+        while (e < n && off[e + 1] - off[s] <= per_call) ++e;
+        if (const int rc = call(off.data() + s, (uint32_t)(e - s), ~0ull)) return rc;
+        s = e;
+    }
+    return HYPO_OK;
+}
+
 }  // namespace hypo

@@ -3,7 +3,8 @@
 // --qv and --qv-bed (QvReport), --qv-spectra (SpectraReport), --kmer-guard (KmerGuard) and --kmer-fix (KmerFix) ask it, each with
 // an entry point of its own, bound where it is used.  What more than one of them needs is here: the set's k, its counts and the
 // least count of --qv-min-count (DESIGN.md "k-mer min count"), the shape of the count histogram, the track query with its retry,
-// and the bound on the text of one call.
+// and the bound on the text of one call.  --qv-cn (CnReport; DESIGN.md "k-mer copy number") asks through query_depth, which cuts
+// the text into calls here.
 #pragma once
 #include <cstdint>
 #include <string>
@@ -65,7 +66,23 @@ public:
     // with that room asks the set everything again (rare at one interval per kbp).  HYPO_OK or the C-ABI's error.
     struct Track { std::vector<uint64_t> total, missing, iv_off, start, end, count; };
     int query_track(const std::string& text, const std::vector<uint64_t>& off, const uint8_t* want, Track& out) const;
+
+    // --qv-cn: hypo_gpu_kset_query_depth, bound by name (false: the device library lacks it)
+    bool bind_depth();
+    bool have_depth() const { return _depth != nullptr; }
+    // the default unit of --qv-cn, of a read histogram h[0 .. kRows): the c in [valley(h), 254] with the largest h[c], the smallest such
+    // c among equals; 0 when every h[c] in that range is 0
+    static uint32_t peak(const uint64_t* h);
+    // hypo_gpu_kset_query_depth over the sequences text[off[s], off[s + 1]) in bins of `bin` window starts against plane `plane`, a
+    // copy worth `unit` reads: the six arrays of all bins, sequence by sequence.  The text goes in calls of at most per_call bytes
+    // cut at sequence ends; a single longer sequence is cut at multiples of `bin`, each piece with the k - 1 bytes its last windows
+    // need (the bin those bytes alone would open holds no window and is dropped), so the pieces' arrays concatenate to the answer of
+    // one call.  HYPO_OK or the C-ABI's error.
+    struct Depth { std::vector<uint32_t> windows, missing, rated, over, under; std::vector<uint8_t> median; };
+    int query_depth(const std::string& text, const std::vector<uint64_t>& off, uint32_t bin, uint32_t plane, uint32_t unit, Depth& out,
+                    size_t per_call = kTextPerCall) const;
 private:
+    int (*_depth)(const char*, const uint64_t*, uint32_t, uint32_t, uint32_t, uint32_t, uint64_t, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint32_t*, uint8_t*) = nullptr;
     int (*_begin)(uint32_t, uint64_t, uint64_t) = nullptr;
     int (*_add)(const char*, uint64_t) = nullptr;
     int (*_size)(uint64_t*, uint64_t*) = nullptr;

@@ -42,7 +42,10 @@ struct InputFlags {                        // include/globalDefs.hpp:68-87
     uint32_t kmer_bridge_vote = 0;         // new, opt-in: --kmer-bridge-vote (2..255, 0 = off: an ambiguous bridge goes to the walk the reads support this many times better)
     std::string qv_save_filename;          // new, opt-in: --qv-save <file> (the k-mer set of the reads, with its counts, is also written to the file)
     std::string qv_load_filename;          // new, opt-in: --qv-load <file> (the k-mer set comes from the file of --qv-save; the reads are not parsed for it)
-    uint64_t genome_size = 0;              // -s as a number (sizes the k-mer set of --qv)
+    std::string qv_cn_filename;            // new, opt-in: --qv-cn <file> (per bin of the written text, the read counts of its k-mers against their copy numbers: collapsed and duplicated stretches)
+    uint32_t qv_cn_bin = 1024;             // new, opt-in: --qv-cn-bin (32..65536: window starts per line of --qv-cn)
+    uint32_t qv_cn_unit = 0;               // new, opt-in: --qv-cn-unit (1..255: the read count of one copy; 0 = the peak of the read histogram)
+    uint64_t genome_size = 0;             // -s as a number (sizes the k-mer set of --qv)
 };
 
 enum class RegionType : uint8_t { SWS, SW, WS, MWM, MW, WM, SWM, MWS, OTHER, LONG, SR, MSR };   // globalDefs.hpp:95-108

@@ -37,7 +37,8 @@ const struct option long_options[] = {
     {"kmer-fix", required_argument, nullptr, 1018}, {"kmer-bridge", required_argument, nullptr, 1019},
     {"kmer-bridge-max", required_argument, nullptr, 1020}, {"kmer-bridge-slack", required_argument, nullptr, 1021},
     {"kmer-bridge-vote", required_argument, nullptr, 1022}, {"qv-save", required_argument, nullptr, 1023},
-    {"qv-load", required_argument, nullptr, 1024}, {nullptr, 0, nullptr, 0}};
+    {"qv-load", required_argument, nullptr, 1024}, {"qv-cn", required_argument, nullptr, 1025},
+    {"qv-cn-bin", required_argument, nullptr, 1026}, {"qv-cn-unit", required_argument, nullptr, 1027}, {nullptr, 0, nullptr, 0}};
 
 // Same layout as the reference's usage() (src/main.cpp:363-430): "Usage: hypo <args>", the mandatory block, the optional
 // block, every flag as "-x, --long <type>" followed by what it does and its default.  The wording is this build's own.
@@ -89,6 +90,9 @@ void usage() {
         {"    --kmer-bridge-max <int>", "[MI355X build] Largest distance of the two anchors --kmer-bridge still tries, 2 to 192 bases. Needs --kmer-bridge.", "64"},
         {"    --kmer-bridge-slack <int>", "[MI355X build] Most bases a bridge of --kmer-bridge may add to or remove from the stretch it replaces, 0 to 64. Needs --kmer-bridge.", "8"},
         {"    --kmer-bridge-vote <int>", "[MI355X build] Settle the stretches --kmer-bridge leaves as ambiguous by read count: such a stretch is searched again for up to 4 walks, each with its support, the smallest number of times the short reads contain a k-mer of the walk, and when the best walk's support is at least this many times the second best's, 2 to 255, its text replaces the stretch (a read error seen once against an allele seen 30 times). Walks of similar support (a heterozygous site, a repeat), more than 4 walks or a search that gives up leave it alone. The file of --kmer-bridge gains two columns: the walks found (1 for a bridge that needed no vote) and the two supports as best/second (`.` without a vote). The k-mer set then counts as for --qv-min-count (one more byte a slot under --qv-mem), with or without --qv-min-count. Needs --kmer-bridge.", "no vote"},
+        {"    --qv-cn <str>", "[MI355X build] Also write where the copy number of the text that is written (after --kmer-guard, --kmer-fix and --kmer-bridge) disagrees with the short reads, as a tab-separated file: a collapsed repeat, a collapsed pair of haplotypes or a falsely duplicated stretch loses no k-mer, so --qv and --qv-bed do not see it. The k-mer set of --qv also counts how often the short reads contain every k-mer, and once the last contig is written, how often the whole text does. Per bin of --qv-cn-bin k-mer starts of every contig the file tells the k-mers, the missing ones (those of --qv), the rated ones (present, neither count at its cap of 255), how many of those the reads contain at least 1.5 times as often as the text's copies at --qv-cn-unit reads each ask for (over) and at most 0.75 times as often (under), and the median read count; a bin is called collapsed when more than half of its rated k-mers are over, duplicated when more than half are under. The two factors are the rounded geometric midpoints between one copy and two, and between a half and one; the raw columns are there to apply others. Every contig's text is kept until the last one is written (one byte a base of host memory). Uses --qv-k, --qv-mem, --qv-min-count, --qv-save and --qv-load, with or without the other flags; the k-mer set counts as for --qv-spectra (one or two more bytes a slot under --qv-mem); counted and compared on the device.", "no copy-number file"},
+        {"    --qv-cn-bin <int>", "[MI355X build] k-mer starts per line of --qv-cn, 32 to 65536. Needs --qv-cn.", "1024"},
+        {"    --qv-cn-unit <int>", "[MI355X build] How often the short reads contain a k-mer the genome holds once, 1 to 255: the read count --qv-cn takes for one copy. Needs --qv-cn.", "the peak of the read k-mer histogram: the most frequent multiplicity from its valley on (a run whose histogram has none ends with an error that asks for this flag)"},
         {"-h, --help", "Print the usage.", nullptr}};
     std::printf("\n Usage: hypo <args>\n\n ** Mandatory args:\n");
     for (const auto& e : mandatory) std::printf("\t%s\n\t%s\n\n", e.flag, e.what);
@@ -152,6 +156,7 @@ int main(int argc, char** argv) {
     bool is_sr = false, is_draft = false, is_size = false, is_cov = false, is_bamsr = false;
     std::string given_sz, kind = "sr";
     int opt;
+    bool cn_opts = false;                                                  // --qv-cn-bin or --qv-cn-unit was given
     bool bridge_opts = false;                                              // --kmer-bridge-max or --kmer-bridge-slack was given
     auto int_in = [](const char* flag, const char* arg, long lo, long hi) {
         char* end = nullptr;
@@ -239,6 +244,9 @@ int main(int argc, char** argv) {
             case 1022: flags.kmer_bridge_vote = int_in("--kmer-bridge-vote", optarg, 2, 255); break;
             case 1023: flags.qv_save_filename = optarg; break;
             case 1024: flags.qv_load_filename = optarg; break;
+            case 1025: flags.qv_cn_filename = optarg; break;
+            case 1026: flags.qv_cn_bin = int_in("--qv-cn-bin", optarg, 32, 65536); cn_opts = true; break;
+            case 1027: flags.qv_cn_unit = int_in("--qv-cn-unit", optarg, 1, 255); cn_opts = true; break;
             case 1002: {
                 flags.devices.clear();
                 for (const char* c = optarg; *c;) { flags.devices.push_back(std::atoi(c)); while (*c && *c != ',') ++c; if (*c == ',') ++c; }
@@ -247,8 +255,12 @@ int main(int argc, char** argv) {
             default: usage(); return 0;                                    // -h and unknown options alike (src/main.cpp:302-304)
         }
     }
+    if (cn_opts && flags.qv_cn_filename.empty()) {
+        std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-cn-bin and --qv-cn-unit set how --qv-cn reads the text: they need --qv-cn!\n");
+        std::exit(1);
+    }
     if (flags.qv_min_count != 1 && flags.qv_filename.empty() && flags.qv_bed_filename.empty() && !flags.kmer_guard && flags.kmer_fix_filename.empty() &&
-        flags.kmer_bridge_filename.empty()) {   // (1 is the run without the flag)
+        flags.kmer_bridge_filename.empty() && flags.qv_cn_filename.empty()) {   // (1 is the run without the flag)
         std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-min-count changes what --qv, --qv-bed, --kmer-guard, --guard-records and --kmer-fix ask the reads: it needs at least one of them!\n");
         std::exit(1);
     }
@@ -265,7 +277,7 @@ int main(int argc, char** argv) {
         std::exit(1);
     }
     if (!flags.qv_load_filename.empty() && flags.qv_filename.empty() && flags.qv_bed_filename.empty() && flags.qv_spectra_filename.empty() && !flags.kmer_guard &&
-        flags.kmer_fix_filename.empty() && flags.kmer_bridge_filename.empty()) {
+        flags.kmer_fix_filename.empty() && flags.kmer_bridge_filename.empty() && flags.qv_cn_filename.empty()) {
         std::fprintf(stderr, "[Hypo::] Error: Arg Error: --qv-load fills the k-mer set that --qv, --qv-bed, --qv-spectra, --kmer-guard, --kmer-fix and --kmer-bridge ask: it needs at least one of them!\n");
         std::exit(1);
     }

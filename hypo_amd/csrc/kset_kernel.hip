@@ -31,6 +31,8 @@
 //     They are instances of the same bodies with a compile-time switch; the kernels above do not know of t.
 //   * export and import (hypo --qv-save / --qv-load; at the end, with comments of their own): the table's records out in slot order
 //     by a stream compaction, and records back in with a saturating add of their count bytes.
+//   * depth (hypo --qv-cn; at the end, with comments of its own): per bin of a text the read count byte of every window against its
+//     copy byte, a wave per bin, a histogram of the count bytes in LDS for the median.
 // Forward progress: every probe loop runs at most `slots` steps.  A lane of the insert or rehash kernel that finds neither its key
 // nor a free slot sets the overflow flag and leaves; lanes in a long probe look at the flag every 64 steps and leave too.  The host
 // keeps the table at most half full, so the flag says "internal error", but no input can make a kernel spin.
@@ -1374,6 +1376,110 @@ hipError_t kset_import_run(const uint64_t* keys, const uint8_t* counts, uint64_t
     uint64_t blocks = (n + KS_THREADS - 1) / KS_THREADS;
     if (blocks > 16384) blocks = 16384;
     kset_import_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(keys, counts, n, table, slots, ctr, planes, digest);
+    return hipGetLastError();
+}
+
+// ---- read count against copy number, bin by bin (hypo --qv-cn; DESIGN.md "k-mer copy number") ----------------------------------------
+// A bin is `bin` consecutive window STARTS of one sequence; a bin never crosses a sequence, and bin_off[s] = the bins of the sequences
+// before s (bin_off[n_seqs] = n_bins), so the sequence of bin b is ks_seq_of(bin_off, n_seqs, b).  One wave owns one bin, a workgroup
+// four of them: nothing is summed across waves and no atomic touches global memory.
+//   * The wave walks its bin in passes of 64 stretches.  A lane's stretch is `per` consecutive starts, per = ceil(starts / 64) capped
+//     at KS_DEPTH_STRETCH: a bin of up to 64 * KS_DEPTH_STRETCH starts is one pass with every lane at work, a larger one loops.  The lane
+//     rolls fwd / rc over the per + k - 1 bytes of its stretch (KmerRoll: any byte other than ACGTacgt restarts the run, and a run that
+//     starts at the stretch's first byte yields only windows that start in the stretch), probes with ks_find, and loads the slot's
+//     count byte c and, for a present window (c >= t), its copy byte m of the text plane.
+//   * Present windows bump the wave's own 256 x 32-bit histogram of c in LDS (1 KiB a wave).  windows / missing / rated / over /
+//     under are lane counters, summed over the wave with shuffles.
+//   * The lower median: lane l holds bins 4 l .. 4 l + 3, a wave-wide inclusive scan of the lanes' sums finds the one lane whose bins
+//     reach the rank ceil(present / 2), and that lane walks its four bins.
+// The work is the dependent probe loads, as in the other query kernels.  Lane 0 stores the bin's six values: a bin without a window
+// gets zeros, and every bin below n_bins has a wave.  The answer is a function of the bytes, the planes and t alone.
+// Bounds: a lane reads bytes[off[s] + lo + w0 + i], i < w1 - w0 + k - 1, with lo + w1 <= hi <= len - k + 1, so below off[s + 1] <= n;
+// the two plane bytes of a slot < slots (a plane has ks_plane_words(slots) * 4 >= slots bytes); LDS bins at a byte, below 256; outputs
+// at b < n_bins.  Loops: passes = ceil(starts / (64 * per)) <= bin / 64 + 1, a stretch's bytes <= KS_DEPTH_STRETCH + 30, probes <=
+// slots, the search <= 32 steps.  The two barriers are reached by every lane: nothing between them leaves the kernel.
+constexpr uint32_t KS_DEPTH_STRETCH = 32;
+constexpr int KS_DEPTH_WAVES = KS_THREADS / 64;
+
+__device__ __forceinline__ uint32_t ks_wave_sum32(uint32_t v) {
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+__global__ void __launch_bounds__(KS_THREADS) kset_depth_kernel(const uint8_t* __restrict__ bytes, const uint64_t* __restrict__ off,
+                                                                 const uint64_t* __restrict__ bin_off, uint32_t n_seqs, uint64_t n_bins, uint32_t bin,
+                                                                 uint32_t k, const uint64_t* __restrict__ table, uint64_t slots,
+                                                                 const uint8_t* __restrict__ counts, const uint8_t* __restrict__ copies, uint32_t t,
+                                                                 uint32_t unit, KsetDepthOut out) {
+    __shared__ __attribute__((aligned(16))) uint32_t hist[KS_DEPTH_WAVES][256];
+    const uint32_t wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    uint32_t* h = hist[wave];
+    *(uint4*)(h + 4 * lane) = make_uint4(0, 0, 0, 0);
+    __syncthreads();
+    const uint64_t b = (uint64_t)blockIdx.x * KS_DEPTH_WAVES + wave;
+    const bool have = b < n_bins;                               // (wave-uniform)
+    uint32_t win = 0, mis = 0, rat = 0, ov = 0, un = 0;
+    if (have) {
+        const uint32_t s = ks_seq_of(bin_off, n_seqs, b);
+        const uint64_t base = off[s], len = off[s + 1] - base;
+        const uint64_t lo = (b - bin_off[s]) * bin;             // the bin's window starts: [lo, hi) of the sequence
+        uint64_t hi = len >= k ? len - k + 1 : 0;
+        if (hi > lo + bin) hi = lo + bin;
+        const uint32_t n_starts = hi > lo ? (uint32_t)(hi - lo) : 0;
+        uint32_t per = (n_starts + 63) / 64;
+        per = per < 1 ? 1 : per > KS_DEPTH_STRETCH ? KS_DEPTH_STRETCH : per;
+        const uint32_t um3 = 3 * unit;
+        for (uint32_t p0 = 0; p0 < n_starts; p0 += 64 * per) {
+            const uint32_t w0 = p0 + lane * per;
+            if (w0 >= n_starts) continue;
+            const uint32_t w1 = w0 + per < n_starts ? w0 + per : n_starts;
+            const uint8_t* __restrict__ src = bytes + base + lo + w0;
+            const uint32_t n_src = w1 - w0 + k - 1;
+            KmerRoll roll(k);
+            for (uint32_t i = 0; i < n_src; ++i) {
+                if (!roll.push(src[i])) continue;
+                ++win;
+                const uint64_t at = ks_find(table, slots, roll.canon());
+                const uint32_t c = at != KSET_EMPTY ? counts[at] : 0u;
+                if (c < t) { ++mis; continue; }                 // (t >= 1: a k-mer the set does not hold is missing)
+                atomicAdd(&h[c], 1u);
+                const uint32_t m = copies[at];
+                if (m >= 1 && m <= 254 && c <= 254) {           // (a saturated byte says "at least")
+                    ++rat;
+                    if (2 * c >= um3 * m) ++ov;
+                    if (4 * c <= um3 * m) ++un;
+                }
+            }
+        }
+    }
+    __syncthreads();
+    win = ks_wave_sum32(win); mis = ks_wave_sum32(mis); rat = ks_wave_sum32(rat); ov = ks_wave_sum32(ov); un = ks_wave_sum32(un);
+    const uint4 mine = *(const uint4*)(h + 4 * lane);
+    const uint32_t sum = mine.x + mine.y + mine.z + mine.w;
+    uint32_t inc = sum;
+    for (int o = 1; o < 64; o <<= 1) { const uint32_t u = __shfl_up(inc, o); if (lane >= (uint32_t)o) inc += u; }
+    const uint32_t present = __shfl(inc, 63), rank = (present + 1) / 2;
+    uint32_t med = 256;
+    if (present && inc - sum < rank && rank <= inc) {           // the one lane whose bins reach the rank
+        uint32_t cum = inc - sum;
+        med = 4 * lane;
+        if ((cum += mine.x) < rank) { ++med; if ((cum += mine.y) < rank) { ++med; if ((cum += mine.z) < rank) ++med; } }
+    }
+    for (int o = 32; o > 0; o >>= 1) { const uint32_t u = __shfl_xor(med, o); if (u < med) med = u; }
+    if (have && lane == 0) {
+        out.windows[b] = win; out.missing[b] = mis; out.rated[b] = rat; out.over[b] = ov; out.under[b] = un;
+        out.med_count[b] = (uint8_t)(present ? med : 0u);
+    }
+}
+
+hipError_t kset_depth_run(const KsetView& set, const uint8_t* bytes, const uint64_t* off, const uint64_t* bin_off, uint32_t n_seqs, uint64_t n_bins,
+                          uint32_t bin, uint32_t text, uint32_t unit, const KsetDepthOut& out, hipStream_t st) {
+    if (!n_bins || !n_seqs) return hipSuccess;
+    const uint64_t n_words = ks_plane_words(set.slots);
+    const uint64_t blocks = (n_bins + KS_DEPTH_WAVES - 1) / KS_DEPTH_WAVES;
+    kset_depth_kernel<<<dim3((uint32_t)blocks), dim3(KS_THREADS), 0, st>>>(bytes, off, bin_off, n_seqs, n_bins, bin, set.k, set.table, set.slots,
+                                                                           (const uint8_t*)set.planes, (const uint8_t*)(set.planes + (1 + (uint64_t)text) * n_words),
+                                                                           set.min_count > 1 ? set.min_count : 1u, unit, out);
     return hipGetLastError();
 }
 

@@ -148,4 +148,16 @@ hipError_t kset_import_check_run(const uint64_t* keys, const uint8_t* counts, ui
 hipError_t kset_import_run(const uint64_t* keys, const uint8_t* counts, uint64_t n, uint64_t* table, uint64_t slots, unsigned long long* ctr,
                            uint32_t* planes, unsigned long long* digest, hipStream_t st);
 
+// Read count against copy number per bin of a text (hypo --qv-cn; DESIGN.md "k-mer copy number"), on a set that counts (`planes` must
+// not be NULL).  The sequences are those of kset_query_run; sequence s has ceil(len / bin) bins, bin j of it owns the windows that
+// start in [j bin, (j + 1) bin), and bin_off[s] = the bins of the sequences before s (n_seqs + 1 entries, bin_off[n_seqs] = n_bins).
+// With c the window's count byte, m its copy byte of plane `text` and t = max(min_count, 1), per bin: windows; missing (not in the
+// table, or c < t); rated (present, 1 <= m <= 254, c <= 254); over (rated, 2 c >= 3 unit m); under (rated, 4 c <= 3 unit m);
+// med_count (the lower median of c over the present windows, 0 without one).  Every entry below n_bins is written; nothing needs
+// clearing.  The caller has checked bin in KSET_DEPTH_MIN_BIN .. KSET_DEPTH_MAX_BIN, unit in 1..255 and bin_off.
+constexpr uint32_t KSET_DEPTH_MIN_BIN = 32, KSET_DEPTH_MAX_BIN = 65536;
+struct KsetDepthOut { uint32_t *windows, *missing, *rated, *over, *under; uint8_t* med_count; };
+hipError_t kset_depth_run(const KsetView& set, const uint8_t* bytes, const uint64_t* off, const uint64_t* bin_off, uint32_t n_seqs, uint64_t n_bins,
+                          uint32_t bin, uint32_t text, uint32_t unit, const KsetDepthOut& out, hipStream_t st);
+
 }  // namespace hypo

@@ -598,6 +598,30 @@ int hypo_gpu_kset_spectrum(uint32_t text, uint64_t* hist);
  * R_255 holds the k-mers seen 255 times or more.  HYPO_E_INVALID: no set, a set without counts, t outside 1..255; a refused call
  * changes nothing.  On the calling thread's context. */
 int hypo_gpu_kset_min_count(uint32_t t);
+/* Read count against copy number along a text, bin by bin (hypo --qv-cn; DESIGN.md "k-mer copy number").  Additive to ABI 11:
+ * callers bind it by name.  The set must count (hypo_gpu_kset_counts_enable) and plane `text` should hold the marks of the whole
+ * text the caller compares against (hypo_gpu_kset_mark).  bytes, off, n_seqs and the byte rules are those of hypo_gpu_kset_query.
+ * Sequence s, of length L_s = off[s + 1] - off[s], has ceil(L_s / bin) bins; bin j of s owns the length-k windows that START in
+ * [j bin, (j + 1) bin) relative to off[s].  Bins are numbered sequence by sequence, and each of the six arrays has n_bins = the sum
+ * of ceil(L_s / bin) entries: the caller computes n_bins, and a value that disagrees is refused.  For a window, c is the count byte
+ * of its k-mer, m its copy byte of plane `text`, t the least count in force (hypo_gpu_kset_min_count, 1 otherwise).  Per bin:
+ *  - windows:   its windows made of ACGTacgt only;
+ *  - missing:   those whose k-mer is not in the set or has c < t (over a sequence they add up to hypo_gpu_kset_query's missing[s]);
+ *               the present windows are the others;
+ *  - rated:     the present windows with 1 <= m <= 254 and c <= 254 (a byte at 255 says "at least"; m = 0: the text was not marked);
+ *  - over:      the rated windows with 2 c >= 3 unit m  (the reads hold the k-mer 1.5 times as often as m copies at `unit` each ask);
+ *  - under:     the rated windows with 4 c <= 3 unit m  (0.75 times); over and under are disjoint, and every product fits 32 bits;
+ *  - med_count: the lower median of c over the present windows, the least v with #{c <= v} >= ceil(present / 2); 0 without one.
+ * A bin without a window gets zeros in all six, and every entry is written.  The call does not close the set and changes no byte of
+ * it; the answer is a function of the input, the planes and t alone.  HYPO_E_INVALID: no set, a set without counts, text not below
+ * the n_texts of _counts_enable, bin outside HYPO_KSET_DEPTH_MIN_BIN .. HYPO_KSET_DEPTH_MAX_BIN, unit outside 1..255, off[]
+ * decreasing, n_bins other than the sum above (or 2^32 and more), a NULL required pointer with n_bins > 0; a refused call changes
+ * nothing.  n_seqs == 0 touches nothing.  Synchronous, on the calling thread's context. */
+#define HYPO_KSET_DEPTH_MIN_BIN 32
+#define HYPO_KSET_DEPTH_MAX_BIN 65536
+int hypo_gpu_kset_query_depth(const char* bytes, const uint64_t* off, uint32_t n_seqs,
+    uint32_t bin, uint32_t text, uint32_t unit, uint64_t n_bins,
+    uint32_t* windows, uint32_t* missing, uint32_t* rated, uint32_t* over, uint32_t* under, uint8_t* med_count);
 /* The set's records out of the table and back in (hypo --qv-save / --qv-load; DESIGN.md "k-mer set file").  Additive to ABI 11:
  * callers bind them by name.  A record is a canonical code as the table stores it (min(fwd, rc), A0 C1 G2 T3, MSB-first, below
  * 4^k) and a count byte: 1..255 on a set that counts (hypo_gpu_kset_counts_enable), 1 on a set that does not.  The digest of a
