@@ -811,9 +811,10 @@ static hipError_t issue_sequential(const PoaIssue& I, const PoaSchedule& S) {
     return hipSuccess;
 }
 
-// first pass of class `cls` (0 - 2) on its stream: class 2 on the caller's, classes 0 and 1 on the side streams
+// first pass of class `cls` (0 - 2) on its stream: S.main_class on the caller's, the other two on aux[0] and aux[1] in class order
 static hipError_t first_pass(const PoaIssue& I, const PoaSchedule& S, int cls, uint32_t* producers) {
-    const hipStream_t st = cls == 2 ? I.stream : I.A->aux[cls];
+    const int lower_side = S.main_class == 0 ? 1 : 0;
+    const hipStream_t st = cls == (int)S.main_class ? I.stream : I.A->aux[cls == lower_side ? 0 : 1];
     const TimedBy t = I.timed(cls);
     return cls == 2 ? I.launch<PoaClass2, true>(2, I.n_windows, kNoScratch, st, t, S.caps[2], false, producers)
          : cls == 1 ? I.launch<PoaClass1, true>(1, I.n_windows, kNoScratch, st, t, S.caps[1], false, producers)
@@ -835,49 +836,53 @@ static hipError_t issue_concurrent(const PoaIssue& I, const PoaSchedule& S) {
         }
         if ((e = hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming)) != hipSuccess) return e;
     }
+    // Every side stream that runs something in this call is joined into the caller's stream before poa_run returns: the next call's
+    // header fill and plan, queued on the caller's stream alone, rely on that.  fork() lets side stream i start behind the caller's stream,
+    // join() makes the caller's stream wait for all it has been given since; a side stream that gets nothing in this call is not touched
+    // (each wait and each record is a packet some queue has to work through), and the two sets are compared at the end.
+    unsigned forked = 0, joined = 0;
     (void)hipEventRecord(fork_ev, stream);
-    (void)hipStreamWaitEvent(aux[0], fork_ev, 0);
-    (void)hipStreamWaitEvent(aux[1], fork_ev, 0);
-    (void)hipStreamWaitEvent(aux[2], fork_ev, 0);
+    auto fork = [&](int i) { (void)hipStreamWaitEvent(aux[i], fork_ev, 0); forked |= 1u << i; };
+    auto join = [&](int i) { (void)hipEventRecord(join_ev[i], aux[i]); (void)hipStreamWaitEvent(stream, join_ev[i], 0); joined |= 1u << i; };
+    fork(0);
+    fork(1);
+    // the third side stream: the LONG first pass if there is one, else the polling launch if there is one
+    if (S.long_first_pass || S.poll_waves > 0) fork(2);
     uint32_t producers = 0;                              // lane groups of every launch of classes 0 - 2 (what class 3's polling pass waits for)
     for (int i = 0; i < 3; ++i)
         if ((e = first_pass(I, S, S.order[i] == '2' ? 2 : (S.order[i] == '0' ? 0 : 1), &producers)) != hipSuccess) return e;
     // (Classes 1 and 2 receive no re-queued windows: every SHORT class hands over to class 3, see poa_class_kernel.)
-    (void)hipEventRecord(join_ev[0], aux[0]);
-    (void)hipEventRecord(join_ev[1], aux[1]);
-    (void)hipStreamWaitEvent(stream, join_ev[0], 0);
-    (void)hipStreamWaitEvent(stream, join_ev[1], 0);
+    join(0);
+    join(1);
     // then the rare classes
     if (S.long_first_pass) {
         if ((e = I.launch<PoaClass4, false>(4, S.first4, I.scr4, aux[2], I.timed(4), 8)) != hipSuccess) return e;
-        (void)hipEventRecord(join_ev[2], aux[2]);
     }
     // the polling launch's stream: the third side stream, unless the LONG first pass is on it (then a fourth one, created on first use)
-    hipStream_t poll_stream = aux[2];
-    if (S.long_first_pass) {
-        if (!aux[3]) {
-            if ((e = hipStreamCreateWithFlags(&aux[3], hipStreamNonBlocking)) != hipSuccess) return e;
-            if ((e = hipEventCreateWithFlags(&join_ev[3], hipEventDisableTiming)) != hipSuccess) return e;
-        }
-        (void)hipStreamWaitEvent(aux[3], fork_ev, 0);
-        poll_stream = aux[3];
-    }
+    const int poll_aux = S.long_first_pass ? 3 : 2;
     uint32_t poll_groups = 0;                            // (class 3's profile value is the polling launch: 0.0 in a call without one)
     if (S.poll_waves > 0) {
-        if ((e = I.launch<PoaClass3, true, true>(3, S.poll_waves, I.scr3, poll_stream, I.timed(3), S.poll_cap, false, &poll_groups, producers)) != hipSuccess) return e;
+        if (poll_aux == 3) {
+            if (!aux[3]) {
+                if ((e = hipStreamCreateWithFlags(&aux[3], hipStreamNonBlocking)) != hipSuccess) return e;
+                if ((e = hipEventCreateWithFlags(&join_ev[3], hipEventDisableTiming)) != hipSuccess) return e;
+            }
+            fork(3);
+        }
+        if ((e = I.launch<PoaClass3, true, true>(3, S.poll_waves, I.scr3, aux[poll_aux], I.timed(3), S.poll_cap, false, &poll_groups, producers)) != hipSuccess) return e;
     }
-    hipEvent_t& poll_join = S.long_first_pass ? join_ev[3] : join_ev[2];
-    (void)hipEventRecord(poll_join, poll_stream);
+    // (nothing else goes on the polling launch's stream in this call: joining it behind the regular launch is the join of the polling launch)
     const bool side_by_side = poa_side_by_side(I.scr3.groups, poll_groups);
-    if (!side_by_side) (void)hipStreamWaitEvent(stream, poll_join, 0);
+    if (S.poll_waves > 0 && !side_by_side) join(poll_aux);
     if ((e = I.launch<PoaClass3, true>(3, S.hint3, I.scr3, stream, TimedBy{}, 0, false, nullptr, 0, side_by_side ? (int)poll_groups : 0)) != hipSuccess) return e;
-    if (side_by_side) (void)hipStreamWaitEvent(stream, poll_join, 0);
+    if (S.poll_waves > 0 && side_by_side) join(poll_aux);
     if (S.long_first_pass) {
-        (void)hipStreamWaitEvent(stream, join_ev[2], 0);
+        join(2);
         if ((e = I.launch<PoaClass4, false>(4, S.mopup4, I.scr4, stream, TimedBy{}, 8, true)) != hipSuccess) return e;
     } else {
         if ((e = I.launch<PoaClass4, false>(4, S.hint4, I.scr4, stream, I.timed(4))) != hipSuccess) return e;
     }
+    if (forked != joined) return hipErrorAssert;         // (a side stream left unjoined)
     return I.launch<PoaClass5, false>(5, S.hint5, I.scr5, stream, I.timed(5));
 }
 
@@ -921,8 +926,8 @@ hipError_t poa_run(const PoaParams& P_in, uint32_t n_windows, void* workspace, s
     const bool wait_for_plan = !have_history || knobs.sync_plan;
     PoaHistory H;
     if (!wait_for_plan) H = poa_history(A->pinned, have_history, false, A->last_planned, n_windows, A->history_windows);
-    (void)hipEventRecord(A->planned_ev, stream);
-    if (wait_for_plan) {
+    if (wait_for_plan) {                                   // (the event is recorded only for a call that waits: a marker packet on the caller's stream)
+        if ((e = hipEventRecord(A->planned_ev, stream)) != hipSuccess) return e;
         if ((e = hipEventSynchronize(A->planned_ev)) != hipSuccess) return e;
         H = poa_history(A->pinned, have_history, true, A->last_planned, n_windows, A->history_windows);
     }

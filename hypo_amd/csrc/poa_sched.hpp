@@ -63,6 +63,7 @@ struct PoaKnobs {
     int adapt = -1;              // HYPO_POA_ADAPT=0|1: wave shares from the last call's work never / everywhere (-1: four-group batches)
     bool adapt_log = false;      // HYPO_POA_ADAPT_LOG: print the shares picked
     int waves_per_cu = 0;        // HYPO_POA_WAVES_PER_CU: cap on every launch (tuning / diagnostics)
+    int main_class = -1;         // HYPO_POA_MAIN=0|1|2: the first pass that goes on the caller's stream (-1: the history decides)
     static PoaKnobs from_env() {
         PoaKnobs k;
         if (const char* v = getenv("HYPO_POA_CLASS0")) k.class0 = atoi(v);
@@ -75,6 +76,7 @@ struct PoaKnobs {
         if (const char* v = getenv("HYPO_POA_ADAPT")) k.adapt = atoi(v) != 0;
         k.adapt_log = getenv("HYPO_POA_ADAPT_LOG") != nullptr;
         if (const char* v = getenv("HYPO_POA_WAVES_PER_CU")) k.waves_per_cu = atoi(v);
+        if (const char* v = getenv("HYPO_POA_MAIN")) if (v[0] >= '0' && v[0] <= '2' && !v[1]) k.main_class = v[0] - '0';
         return k;
     }
 };
@@ -147,11 +149,14 @@ inline uint32_t rare_grid_hint(const PoaHistory& h, int cls, uint32_t n_windows)
 // leaves), less what the polling class-3 waves hold.  Among shares within 3 % of the best the one with most waves wins (latency).
 struct WaveFootprint { size_t lds; int vgprs; int max_waves; };
 struct PoaFootprints { WaveFootprint c0, c0w, c1, c2, c3; uint64_t gw0, gw0w; };      // c0 / c0w: class 0 with four / two groups per wave, of gw0 / gw0w lanes
+// something measured, and plausibly (not the first call, not a torn read: a wave lives < 10 s = 1e9 ticks, a launch has < 1e5 waves)
+inline bool poa_work_plausible(const uint64_t work[3]) {
+    if ((double)work[0] + (double)work[1] + (double)work[2] <= 0.0) return false;
+    for (int c = 0; c < 3; ++c) if (work[c] > (uint64_t)1e14) return false;
+    return true;
+}
 inline void pick_wave_shares(const uint64_t work[3], const WaveFootprint fp[3], const WaveFootprint& fp3, int poll_waves_per_cu, bool log, int caps[]) {
-    const double total = (double)work[0] + (double)work[1] + (double)work[2];
-    // nothing measured (first call, or a torn / implausible read: a wave lives < 10 s = 1e9 ticks, a launch has < 1e5 waves)
-    if (total <= 0.0) return;
-    for (int c = 0; c < 3; ++c) if (work[c] > (uint64_t)1e14) return;
+    if (!poa_work_plausible(work)) return;
     double lds_budget = 160.0 * 1024.0 * 1.05 - (double)poll_waves_per_cu * (double)fp3.lds;
     double vgpr_budget = 2048.0 - (double)poll_waves_per_cu * (double)fp3.vgprs * 0.5;      // (a polling wave sleeps most of the time, but it holds its registers)
     double best_t = 1e300; int best[3] = {caps[0], caps[1], caps[2]}, best_sum = 0;
@@ -188,12 +193,15 @@ struct PoaSchedule {
     int caps[3];                 // waves per CU of the three concurrent first passes
     char order[4];               // ... and the order they are submitted in
     bool long_first_pass;        // class 4's planned windows on a side stream next to the short-window kernels
+    uint8_t main_class;          // the first pass (0 - 2) on the caller's stream; the other two on the side streams in class order
     uint32_t first4;             // ... that many
     uint32_t poll_waves;         // windows the polling launch of class 3 is sized for (0: no polling launch)
     int poll_cap;                // its waves per CU
     uint32_t hint3, hint4, hint5;// windows the regular launches of the rare classes are sized for
     uint32_t mopup4;             // ... and class 4's mop-up pass behind a first pass of its own
 };
+static_assert(sizeof(PoaSchedule) == 52 && offsetof(PoaSchedule, main_class) == 21 && offsetof(PoaSchedule, first4) == 24 && offsetof(PoaSchedule, mopup4) == 48,
+              "main_class sits in the padding behind long_first_pass: tests/test_poa_schedule_cpu.py mirrors the struct field by field");
 // The regular class-3 launch starts when classes 0 - 2 are done (the queue is final then) and does NOT wait for the polling launch's last
 // window: the two drain the queue side by side (one cursor; the polling waves claim with a compare-and-swap below the count, the
 // regular ones with a fetch-add that may run past it), each with direction-code slices of its own.  Behind the polling launch it
@@ -203,6 +211,7 @@ inline bool poa_side_by_side(int groups3, uint32_t poll_groups) { return poll_gr
 
 inline PoaSchedule poa_schedule(const PoaHistory& h, uint32_t n_windows, int groups4, const PoaKnobs& k, const PoaFootprints& fp) {
     PoaSchedule s = {};
+    s.main_class = 2;
     s.hint3 = rare_grid_hint(h, 3, n_windows); s.hint4 = rare_grid_hint(h, 4, n_windows); s.hint5 = rare_grid_hint(h, 5, n_windows);
     s.mopup4 = late_arrivals(h, 4, n_windows);
     // One kernel after the other instead: when the last call left more than a tenth of its windows to class 3 (read error of
@@ -262,6 +271,19 @@ inline PoaSchedule poa_schedule(const PoaHistory& h, uint32_t n_windows, int gro
     // left and grows when class 0 runs dry.  Measured on C2 (ms per call): 201 3.89, 021 4.28, 120 4.38, 210 4.69, 102 4.72,
     // 012 4.76 (HYPO_POA_ORDER, for experiments).
     memcpy(s.order, k.order, 4);
+    // Which first pass rides the caller's stream (the other two take aux[0] and aux[1] in class order): everything behind the first passes
+    // is queued there, so it follows that kernel as a dependency within one queue, and the caller's stream needs no fork, so that kernel
+    // starts first.  It is the class with the strictly largest wave-time per wave of its share in the last finished call, if that call ran
+    // class 0 in this call's geometry and its values are plausible.  Anything else, a tie included, leaves class 2 there (the assignment
+    // until round 8).  HYPO_POA_MAIN=0|1|2 forces.  On the C2 batch the rule keeps class 2; class 0 forced there starts first, takes issue
+    // slots from class 2 and the step is slower (1.469 against 1.371 ms: DESIGN.md 3.1, profiles/r08_c2_step_trace.txt).
+    if (k.main_class >= 0) s.main_class = (uint8_t)k.main_class;
+    else if (h.valid && same_kind && poa_work_plausible(h.work)) {
+        double t[3];
+        for (int c = 0; c < 3; ++c) t[c] = (double)h.work[c] / (double)(s.caps[c] < 1 ? 1 : s.caps[c]);
+        if (t[0] > t[1] && t[0] > t[2]) s.main_class = 0;
+        else if (t[1] > t[0] && t[1] > t[2]) s.main_class = 1;
+    }
     // LONG windows are planned straight into class 4, so its first pass does not have to wait for
     // anybody: it runs on a third stream next to the short-window kernels (a LONG window occupies one wave for ~0.1 s; its
     // latency is the floor of the whole call), and only the few windows escalated into class 4 later wait for the mop-up
